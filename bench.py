@@ -10,6 +10,10 @@ One process per GPU; a step = one forward of this rank's 8 clips (inputs residen
 for N > 1, the single all-gather of logits (RCCL).  Weak scaling: 8 clips per GPU.
 Rank 0 prints ONE JSON line.
 
+A plain run sets up (including the tile tuner), warms up, times the K steps and prints the line.  `--full` adds what
+the headline figure does not need: the CPU baseline and parity, the other clip-lane setting, the per-kernel rooflines
+and the split-operand (x3) leg.  `--dump-outputs DIR` writes the last timed step's output as DIR/<name>.npy (float32).
+
 `--workload` selects another BASELINE.json configuration through the same harness (same JSON schema;
 the default, and what the driver runs, is config 2):
     cfg1  resnet18 2-D, 1x3x224x224 (plumbing case)      cfg3  (2+1)D-50 + NL blocks, 8x3x32x112x112
@@ -112,10 +116,32 @@ def timed_steps(run, total_units, steps, warmup, dev, sync):
     return elapsed, out, verify, rank_ms
 
 
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(out, directory, name):
+    """Write `out` (the last timed step's output) as DIR/<name>.npy in float32.  An output larger than DUMP_LIMIT_BYTES is
+    replaced by a fixed, seeded sample of its flat elements: DIR/<name>_sample.npy plus the flat positions of the sample
+    as DIR/<name>_sample_index.npy (float64, exact below 2**53)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    a = out.detach().float().cpu().contiguous().numpy()
+    if a.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, name + ".npy"), a)
+        return [name]
+    n = DUMP_LIMIT_BYTES // (4 + 8) // 2
+    g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+    idx = torch.randperm(a.size, generator=g)[:n].sort().values.numpy()
+    np.save(os.path.join(directory, name + "_sample.npy"), a.reshape(-1)[idx])
+    np.save(os.path.join(directory, name + "_sample_index.npy"), idx.astype(np.float64))
+    return [name + "_sample", name + "_sample_index"]
+
+
 def self_launch(n):
-    """Replace this process by `python -m torch.distributed.run --nnodes=1 --nproc-per-node n ... bench.py <same args>`.
-    Fails loudly when the node has fewer than n GPUs (PTX_BENCH_BACKEND=gloo -- the functional check in which ranks share
-    devices -- is exempt)."""
+    """Run `python -m torch.distributed.run --nnodes=1 --nproc-per-node n ... bench.py <same args>` as a child process and
+    exit with its status.  Fails loudly when the node has fewer than n GPUs (PTX_BENCH_BACKEND=gloo -- the functional
+    check in which ranks share devices -- is exempt)."""
     import torch
     have = torch.cuda.device_count()
     if os.environ.get("PTX_BENCH_BACKEND", "nccl") == "nccl" and have < n:
@@ -129,7 +155,10 @@ def self_launch(n):
            "--nproc-per-node", str(n), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    # a fresh child, never an exec: the device count above may already have opened the GPU runtime in this process
+    import subprocess
+    rc = subprocess.run(cmd).returncode
+    sys.exit(128 - rc if rc < 0 else rc)
 
 
 def measure(args, scaling, world, rank, local, dev, backend, first=True):
@@ -202,6 +231,11 @@ def measure(args, scaling, world, rank, local, dev, backend, first=True):
                 save_tuned_table(os.environ["PTX_TUNED_OUT"])
 
     elapsed, out, verify, rank_ms = timed_steps(run, total_units, args.steps, args.warmup, dev, sync)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any secondary leg runs the model again: what the caller of the timed path received in its last step
+        name = "logits" if out.dim() == 2 else "images" if out.dim() == 4 else "output"
+        dumped = dump_outputs(out, args.dump_outputs, name if first else "%s_%s" % (name, scaling))
     n_dev = torch.cuda.device_count()
     me = {"rank": rank, "local_rank": local, "device": torch.cuda.current_device() if n_dev and not standin else None,
           "name": torch.cuda.get_device_name(local) if n_dev and not standin else "cpu", "pid": os.getpid(),
@@ -236,6 +270,7 @@ def measure(args, scaling, world, rank, local, dev, backend, first=True):
         "scaling": scaling, "vs_baseline": None, "dtype": "f16" if f16 else "f32", "data": "synthetic",
         "config": {"workload": workload_label, "clips_per_gpu": units_per_gpu, "global_batch": total_units,
                    "parallelism": parallelism},
+        "full": bool(args.full), "dumped_outputs": dumped,
     }
     if standin:
         result.update({"standin": True, "roofline": None, "cpu_baseline": None, "distributed_check": verify,
@@ -246,6 +281,14 @@ def measure(args, scaling, world, rank, local, dev, backend, first=True):
     import pretorched_x_amd as ptx
     lanes_used = eng.lanes_for(units_per_gpu, model, x.shape) if fwd is None else 1
     result["config"]["clip_lanes"] = lanes_used
+    if not args.full:
+        # a plain run stops at the headline: no CPU baseline, no secondary legs, no per-kernel rooflines (--full)
+        result.update({
+            "commit": os.environ.get("PTX_COMMIT"),
+            "binary": {"version": ptx._lib.lib().ptx_version().decode(), "source_sha256_matches_tree": ptx._lib.binary_source_hash() == ptx._lib.source_hash()},
+            "distributed_check": verify, "ranks_seen": ranks_seen, "rank_ms_per_step": rank_ms,
+        })
+        return result
 
     # ---- CPU baseline: the oracle restatement of the reference path on this box's host cores ----
     def sample_indices():
@@ -315,6 +358,11 @@ def main():
                          "that disagrees with the launcher is an error")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline + parity, the other clip-lane setting, "
+                         "the per-kernel rooflines and the split-operand (x3) leg (the --no-* switches below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-autotune", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--verbose", action="store_true")
@@ -327,6 +375,8 @@ def main():
                          "clips, cfg4: 16) sharded over the ranks -- at 8 GPUs the headline batch leaves 1 clip per GPU; "
                          "both: the weak line, then the strong line, in one invocation")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
 

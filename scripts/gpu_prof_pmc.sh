@@ -1,15 +1,16 @@
 #!/bin/bash
-# rocprofv3 kernel trace + separate PMC passes (MFMA / LDS / FETCH / WRITE) of bench.py for one workload.
-#   W=cfg5 [ENVS="PTX_PRECISION=x3"] bash scripts/gpu_prof_pmc.sh   ->  gpurun_out/prof_$W$TAG/summary.txt
+# rocprofv3 kernel trace + separate PMC passes (MFMA / LDS / FETCH / WRITE) of bench.py --full for one workload.
+#   W=cfg5 [ENVS="PTX_PRECISION=x3"] bash scripts/gpu_prof_pmc.sh   ->  $LOG/prof_$W$TAG/summary.txt
 #   W=stem PROF_CMD="python scripts/gpu_stem_scale_probe.py 8" PASSES="0 1" bash scripts/gpu_prof_pmc.sh    (a probe script)
+LOG=${LOG:-logs}        # output folder, relative to the repository root
 export PYTHONDONTWRITEBYTECODE=1
 for e in $ENVS; do export $e; done
 REPO=$(pwd)
 W=${W:-cfg5}
-OUT=$REPO/gpurun_out/prof_$W$TAG
+OUT=$REPO/$LOG/prof_$W$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --workload $W --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-x3 --no-lanes --lanes 1 ${BENCH_ARGS}"   # (single plan: under clip lanes two kernels share the chip)
+CMD="python $REPO/bench.py --full --workload $W --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-x3 --no-lanes --lanes 1 ${BENCH_ARGS}"   # (single plan: under clip lanes two kernels share the chip)
 NOTUNE="--no-autotune"
 if [ -n "$PROF_CMD" ]; then CMD="$PROF_CMD"; NOTUNE=""; fi      # any other command (a kernel probe script): W / TAG only name the output
 # the trace pass runs with the tuned table too (--no-autotune): tuner launches would pollute the per-kernel averages

@@ -1,11 +1,12 @@
 #!/bin/bash
 # rocprofv3 evidence for profiles/: (1) kernel trace + stats of the bench command, (2) PMC passes.
+LOG=${LOG:-logs}        # output folder, relative to the repository root
 export PYTHONDONTWRITEBYTECODE=1
 REPO=$(pwd)
-OUT=$REPO/gpurun_out/prof
+OUT=$REPO/$LOG/prof
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-x3 ${BENCH_ARGS}"
+CMD="python $REPO/bench.py --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-x3 ${BENCH_ARGS}"
 echo "== kernel trace"
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- $CMD > $OUT/trace.log 2>&1
 echo "trace exit $?"

@@ -1082,7 +1082,7 @@ def test_bench_line_launch_times_sum_to_the_step(ptx):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--no-autotune",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--no-autotune",
                         "--no-cpu-baseline", "--no-x3", "--no-lanes", "--lanes", "1"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1100,3 +1100,21 @@ def test_bench_line_launch_times_sum_to_the_step(ptx):
     # (profiled passes clock lower: MI355X_MICROARCH.md, DVFS note)
     if roof["rocprof"] is not None and roof["rocprof"].get("hip_event_over_rocprof") is not None:
         assert 0.90 <= roof["rocprof"]["hip_event_over_rocprof"] <= 1.06, roof["rocprof"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_dumps_the_timed_output(ptx, tmp_path):
+    """A plain bench run (no --full): the headline fields only, and --dump-outputs writes the logits of the last timed step."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--no-autotune",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["dtype"] == "f32" and line["full"] is False
+    assert "roofline" not in line and "cpu_baseline" not in line and line["binary"]["source_sha256_matches_tree"]
+    logits = np.load(str(tmp_path / "logits.npy"))
+    assert logits.dtype == np.float32 and logits.shape == (8, 339) and np.isfinite(logits).all()

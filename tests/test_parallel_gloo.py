@@ -297,3 +297,35 @@ def test_bench_gpus_8_self_launch_standin_lines():
     # the stand-in refuses to pose as an RCCL run
     r = subprocess.run([sys.executable, bench, "--gpus", "1"], env=dict(env, PTX_BENCH_BACKEND="nccl"), capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "PTX_BENCH_STANDIN" in r.stderr
+
+
+def test_bench_dump_outputs_and_steps():
+    """`--dump-outputs DIR` writes the last timed step's output as DIR/<name>.npy (float32), identical from run to run with
+    the same arguments; `--steps` is the number of timed steps in the line; a plain run carries no secondary legs.  Driven
+    through the CPU stand-in forward (PTX_BENCH_STANDIN=1), the same measure() / timed_steps path a GPU run takes."""
+    import json
+    import subprocess
+    import tempfile
+
+    import numpy as np
+    env = dict(os.environ, PTX_BENCH_STANDIN="1", PTX_BENCH_BACKEND="gloo", PYTHONDONTWRITEBYTECODE="1", OMP_NUM_THREADS="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PTX_BENCH_LAUNCH_CHECK"):
+        env.pop(k, None)
+    bench = os.path.join(ROOT, "bench.py")
+    with tempfile.TemporaryDirectory() as tmp:
+        arrays = []
+        for i, steps in enumerate((3, 5)):
+            d = os.path.join(tmp, "run%d" % i)
+            r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--dump-outputs", d],
+                               env=env, capture_output=True, text=True, timeout=300)
+            assert r.returncode == 0, r.stderr[-1500:]
+            line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+            assert line["steps"] == steps and line["ms_per_step"] > 0 and line["full"] is False, line
+            assert line["dumped_outputs"] == ["logits"] and os.listdir(d) == ["logits.npy"]
+            a = np.load(os.path.join(d, "logits.npy"))
+            assert a.dtype == np.float32 and a.shape == (8, 339) and np.isfinite(a).all()
+            arrays.append(a)
+        assert np.array_equal(arrays[0], arrays[1])
+        r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "0"], env=env, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode != 0 and "--steps" in r.stderr
