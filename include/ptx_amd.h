@@ -86,6 +86,11 @@ typedef void* ptx_stream_t; /* hipStream_t */
 #define PTX_PRO_UP2 0x2000u     /* the input is read through a nearest 2x upsample in H and W: desc.Hi / Wi are the
                                    UPSAMPLED extents the filter slides over, x stores [N][1][Hi/2][Wi/2][ldx]      */
 #define PTX_EPI_TANH 0x4000u    /* tanh on the output (the generator's image conv)                                 */
+#define PTX_BF16_OPERANDS 0x20000u /* with PTX_F16_OPERANDS: the 16-bit operands are bfloat16 (v_mfma_f32_32x32x16_bf16 /
+                                16x16x32_bf16, fp32 accumulate), and PTX_EPI_OUT_F16 / PTX_RES_F16 mean bf16 output / skip.
+                                Same descriptor conventions as the fp16 operands (Ci, ldx, Kc count 32-bit words); pack with
+                                ptx_pack_desc.f16 == 3.  Each output is rounded to bf16 once, after bias + residual + ReLU.
+                                Runs on the ".../bf16" tile configurations (the bf16 video ResNets).                        */
 #define PTX_PRO_RELU 8u      /* ptx_linear_fwd only: ReLU on the input while loading (trn.py:39-45) */
 #define PTX_EPI_ACCUM 16u    /* ptx_linear_fwd only: y += result (trn.py:110 stack(...).sum(0))   */
 
@@ -125,6 +130,9 @@ typedef struct ptx_conv3d_desc {
 
 /* number of compiled tile configurations, and a printable name "BMxBNxBK/WMxWN/mfmaMT" */
 int ptx_conv3d_num_configs(void);
+/* the ".../bf16" tile configurations (PTX_BF16_OPERANDS) follow at indices [ptx_conv3d_num_configs(),
+ * ptx_conv3d_num_configs() + ptx_conv3d_num_configs_bf16()); every config-index entry point takes them */
+int ptx_conv3d_num_configs_bf16(void);
 const char* ptx_conv3d_config_name(int config);
 /* 1 if `config` can run `desc` (tile K-step divides Kc, etc.), else 0 */
 int ptx_conv3d_config_supported(const ptx_conv3d_desc* desc, int config);
@@ -322,7 +330,8 @@ typedef struct ptx_pack_desc {
      * halfs) for PTX_F16_OPERANDS convs.  2: split halfs for PTX_F16X3_OPERANDS convs -- Kc, ld_k, k_off count
      * channels as in the fp32 layout (multiples of 8) and the buffer has the fp32 layout's size, but every 8-channel
      * block of a row holds 8 hi halfs then 8 lo halfs (hi = half(w), lo = half((w - hi) * 2^12): the SCALED lo of
-     * PTX_F16X3_OPERANDS, whose cross terms the kernels accumulate separately and fold back by 2^-12).  bias_out stays fp32. */
+     * PTX_F16X3_OPERANDS, whose cross terms the kernels accumulate separately and fold back by 2^-12).  bias_out stays fp32.
+     * 3: as 1, but bfloat16 (PTX_BF16_OPERANDS convs): the BN fold runs in fp32 and the folded filter is rounded once. */
     int32_t f16;
 } ptx_pack_desc;
 
@@ -337,6 +346,9 @@ int ptx_pack_conv_weight(const ptx_pack_desc* desc, const float* w /* [Co][Ci][k
  * effect immediately): *out += a 64-bit position-sensitive sum over the bit patterns of n fp32 tensors,
  * table[i] = (device pointer, element count) as int64 pairs in device memory; the caller zeroes *out first. */
 int ptx_checksum_f32(const int64_t* table, int32_t n, uint64_t* out, ptx_stream_t stream);
+/* The same sum over the bit patterns of n 16-bit tensors (bf16 / fp16 parameters): table[i] = (device pointer, count of
+ * 16-bit elements); *out += the sum (so one zeroed word may collect both checksums). */
+int ptx_checksum_b16(const int64_t* table, int32_t n, uint64_t* out, ptx_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * Layout transforms at the API edge (the reference's tensors are NCDHW, torchvision_models.py:448).
@@ -347,6 +359,19 @@ int ptx_ncdhw_to_ndhwc(const float* x, float* y, int32_t N, int32_t C, int64_t S
 /* x [N][S][ld] -> y [N][C][S] */
 int ptx_ndhwc_to_ncdhw(const float* x, float* y, int32_t N, int32_t C, int64_t S, int32_t ld,
                        ptx_stream_t stream);
+/* The same two transposes on bf16 tensors (bit-exact moves; channels [C, ld) of y zero-filled): the NCDHW edge of the
+ * bf16 plans -- `features()` out, `logits(features)` in.  ld % 8 == 0, 16-byte aligned channels-last side. */
+int ptx_ncdhw_to_ndhwc_bf16(const void* x, void* y, int32_t N, int32_t C, int64_t S, int32_t ld, ptx_stream_t stream);
+int ptx_ndhwc_to_ncdhw_bf16(const void* x, void* y, int32_t N, int32_t C, int64_t S, int32_t ld, ptx_stream_t stream);
+/* bf16 RGB stem operand: the (kh, kw) taps of a small-Cin first conv folded into the channel axis of a bf16
+ *   y[n][t][ho][wo][(kh*kW + kw)*C + c] = x[n][c][t][ho*sH - pH + kh][wo*sW - pW + kw]   (0 outside the image)
+ * columns [kH*kW*C, ld) zero; ld a multiple of 32.  x: the caller's contiguous bf16 NCDHW clip at any 2-byte alignment.
+ * The stem (resnet3D.py:153 Conv3d 3->64 k7 s(1,2,2) p3; r2plus1d.py:73-88 spatial (1,7,7)) then is a (kT,1,1) conv
+ * over kH*kW*C = 147 channels (padded to 160: 1.09x the algorithmic MACs) on the ".../bf16" tiles.                  */
+int ptx_im2col_hw_bf16(const void* x, void* y, int32_t N, int32_t C, int32_t T, int32_t H, int32_t W, int32_t kH, int32_t kW,
+                       int32_t sH, int32_t sW, int32_t pH, int32_t pW, int32_t Ho, int32_t Wo, int32_t ld, ptx_stream_t stream);
+/* y[i] = bf16(x[i]) for i < n (round to nearest even; NaN stays NaN): the single rounding of a bf16 plan's logits */
+int ptx_f32_to_bf16(const float* x, void* y, int64_t n, ptx_stream_t stream);
 /*
  * Small-Cin stem input: x NCDHW [N][C][T][H][W]  ->  y [N][T][H][Wo][ld] with
  *   y[n][t][h][wo][kw*C + c] = x[n][c][t][h][wo*sW - pW + kw]   (0 outside the image / k >= kW*C)
@@ -395,6 +420,7 @@ int ptx_fold_kw_frames_u8(const uint8_t* frames, float* y, int32_t N, int32_t C,
 #define PTX_POOL_SAME 1u      /* To/Ho/Wo are given (TF "SAME": ceil(in/stride)); pT/pH/pW are the FRONT
                                  pads, the back pads are whatever the output extent implies        */
 #define PTX_POOL_PAD_ZERO 2u  /* padded taps contribute 0 (F.pad then MaxPool3d) instead of -inf     */
+#define PTX_POOL_BF16 4u      /* ptx_maxpool3d_fwd: x / y hold bf16 (ld / ldy count bf16, multiples of 8): exact         */
 typedef struct ptx_pool3d_desc {
     int32_t N, Ti, Hi, Wi, C, ld; /* input NDHWC, ld = input row stride */
     int32_t To, Ho, Wo;
@@ -439,6 +465,8 @@ int ptx_window_mean(const float* x, float* y, int32_t outer, int32_t T, int32_t 
  * -> y [N][C]   (torchvision_models.py:461) */
 int ptx_global_avgpool(const float* x, float* y, int32_t N, int32_t C, int64_t S, int32_t ld,
                        int32_t channels_first, ptx_stream_t stream);
+/* The same pool over a channels-last bf16 map x [N][S][ld] (ld % 8 == 0), summed in fp32 into fp32 y [N][C] */
+int ptx_global_avgpool_bf16(const void* x, float* y, int32_t N, int32_t C, int64_t S, int32_t ld, ptx_stream_t stream);
 /* y[m][j] = act_out( sum_k act_in(x[m][k]) * w[j][k] + b[j] ), small M (GEMV-class, weight-
  * bandwidth bound): last_linear (torchvision_models.py:463) and the TRN relation MLP at small
  * batch (trn.py:39-45).  flags: PTX_PRO_RELU | PTX_EPI_RELU | PTX_EPI_ACCUM.  b may be NULL. */

@@ -21,6 +21,8 @@ PTX_EPI_RES_UP = 64
 PTX_F16_OPERANDS = 128
 PTX_F16X3_OPERANDS = 0x8000
 PTX_SPLITK_FUSED = 0x10000
+PTX_BF16_OPERANDS = 0x20000      # with PTX_F16_OPERANDS: bfloat16 operands / 16-bit outputs and skips (bf16 plans)
+PTX_PACK_BF16 = 3                # ptx_pack_desc.f16: filter written as bf16
 PTX_ACT_OUT_F16 = 0x100
 PTX_EPI_OUT_F16, PTX_EPI_AFFINE, PTX_EPI_DUAL_RAW, PTX_RES_F16, PTX_PRO_UP2, PTX_EPI_TANH = 0x200, 0x400, 0x800, 0x1000, 0x2000, 0x4000
 
@@ -91,7 +93,7 @@ class NormDesc(C.Structure):
         return d
 
 
-PTX_POOL_SAME, PTX_POOL_PAD_ZERO = 1, 2
+PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
 
 
@@ -126,6 +128,7 @@ SIGNATURES = {
     "ptx_version": (C.c_char_p, []),
     "ptx_last_error": (C.c_char_p, []),
     "ptx_conv3d_num_configs": (C.c_int, []),
+    "ptx_conv3d_num_configs_bf16": (C.c_int, []),
     "ptx_conv3d_config_name": (C.c_char_p, [C.c_int]),
     "ptx_conv3d_config_supported": (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
     "ptx_conv3d_pick_config": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int)]),
@@ -170,6 +173,12 @@ SIGNATURES = {
     "ptx_packed_weight_elems": (_Z, [C.POINTER(PackDesc)]),
     "ptx_pack_conv_weight": (C.c_int, [C.POINTER(PackDesc), _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P]),
     "ptx_checksum_f32": (C.c_int, [_P, _I, _P, _P]),
+    "ptx_checksum_b16": (C.c_int, [_P, _I, _P, _P]),
+    "ptx_ncdhw_to_ndhwc_bf16": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
+    "ptx_ndhwc_to_ncdhw_bf16": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
+    "ptx_im2col_hw_bf16": (C.c_int, [_P, _P] + [_I] * 14 + [_P]),
+    "ptx_f32_to_bf16": (C.c_int, [_P, _P, _L, _P]),
+    "ptx_global_avgpool_bf16": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
     "ptx_ncdhw_to_ndhwc": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
     "ptx_ndhwc_to_ncdhw": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
     "ptx_fold_kw_ncdhw": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -57,7 +57,11 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ConvArgs p) {
                 fused_value(p, acc4[c], m, co + c, p.bias ? p.bias[co + c] : 0.f, sc, sh, raw[c], out[c]);
             }
             typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-            if (p.flags & PTX_EPI_OUT_F16)
+            typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+            if ((p.flags & PTX_EPI_OUT_F16) && p.bf16)           // bf16 plans: the one rounding of the output
+                *reinterpret_cast<bf16x4_t*>(reinterpret_cast<__bf16*>(p.y) + (size_t)m * p.ldy + co) =
+                    bf16x4_t{(__bf16)out[0], (__bf16)out[1], (__bf16)out[2], (__bf16)out[3]};
+            else if (p.flags & PTX_EPI_OUT_F16)
                 *reinterpret_cast<half4_t*>(reinterpret_cast<_Float16*>(p.y) + (size_t)m * p.ldy + co) =
                     half4_t{(_Float16)out[0], (_Float16)out[1], (_Float16)out[2], (_Float16)out[3]};
             else
@@ -81,7 +85,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ConvArgs p) {
 // ------------------------------------------------------------------------------------------
 typedef int (*launch_fn)(const ConvArgs&, dim3, hipStream_t);
 
-template <int BM, int BN, int BK, int WM, int WN, int MT, bool KTAIL, bool K22, bool DMA, int NSTAGE, bool F16 = false,
+template <int BM, int BN, int BK, int WM, int WN, int MT, bool KTAIL, bool K22, bool DMA, int NSTAGE, int F16 = 0,
           bool X3 = false, int KWR = 0, bool REPI = false>
 static int launch_one(const ConvArgs& a, dim3 grid, hipStream_t st) {
     // fp16 tiles: the fused epilogue parks one MT-row block per wave ([MT][BN / WN + 4] floats) in the tile buffers
@@ -103,24 +107,24 @@ static int launch_one(const ConvArgs& a, dim3 grid, hipStream_t st) {
 }
 
 // KTAIL instantiation only when the K extent of either operand is not a multiple of BK
-template <int BM, int BN, int BK, int WM, int WN, int MT, bool F16, bool X3, int KWR>
+template <int BM, int BN, int BK, int WM, int WN, int MT, int F16, bool X3, int KWR>
 static int launch_cfg_kwr(const ConvArgs& a, dim3 grid, hipStream_t st) {
     if ((a.kA % BK) || (a.kB % BK))
         return launch_one<BM, BN, BK, WM, WN, MT, true, false, true, 2, F16, X3, KWR>(a, grid, st);
     return launch_one<BM, BN, BK, WM, WN, MT, false, false, true, 2, F16, X3, KWR>(a, grid, st);
 }
 
-template <int BM, int BN, int BK, int WM, int WN, int MT, bool DMA, int NSTAGE, bool F16 = false, bool X3 = false>
+template <int BM, int BN, int BK, int WM, int WN, int MT, bool DMA, int NSTAGE, int F16 = 0, bool X3 = false>
 static int launch_cfg(const ConvArgs& a, dim3 grid, hipStream_t st) {
     if constexpr (X3) {
         if ((a.kA % BK) || (a.kB % BK) || (a.dual && ((a.kA2 % BK) || (a.wcol2 % BK))))
             return launch_one<BM, BN, BK, WM, WN, MT, true, false, true, NSTAGE, false, true>(a, grid, st);
         return launch_one<BM, BN, BK, WM, WN, MT, false, false, true, NSTAGE, false, true>(a, grid, st);
     }
-    if constexpr (F16) {
+    if constexpr (F16) {       // 1: fp16 operands, 2: bf16 operands
         if ((a.kA % BK) || (a.kB % BK))
-            return launch_one<BM, BN, BK, WM, WN, MT, true, false, DMA, NSTAGE, true>(a, grid, st);
-        return launch_one<BM, BN, BK, WM, WN, MT, false, false, DMA, NSTAGE, true>(a, grid, st);
+            return launch_one<BM, BN, BK, WM, WN, MT, true, false, DMA, NSTAGE, F16>(a, grid, st);
+        return launch_one<BM, BN, BK, WM, WN, MT, false, false, DMA, NSTAGE, F16>(a, grid, st);
     }
     if constexpr (BK == 24 && MT == 32 && !DMA) {
         // kW-folded stem: one 24-wide chunk per tap of which at most 22 columns are live
@@ -294,6 +298,7 @@ struct ConvConfig {
     bool f16;         // fp16 operands (PTX_F16_OPERANDS)
     bool x3;          // split fp32 operands on the fp16 matrix cores (PTX_F16X3_OPERANDS)
     int kwr;          // kw-reuse tile (3-wide stride-1 filters, BM a whole number of output rows)
+    bool bf16;        // with f16: bfloat16 operands (PTX_BF16_OPERANDS)
 };
 
 #define PTX_CFG(BM, BN, BK, WM, WN, MT) \
@@ -317,6 +322,9 @@ struct ConvConfig {
 #define PTX_CFG_F16(BM, BN, BK, WM, WN, MT) \
     { BM, BN, BK, WM, WN, MT, #BM "x" #BN "x" #BK "/" #WM "x" #WN "/m" #MT "/dma/f16", \
       launch_cfg<BM, BN, BK, WM, WN, MT, true, 2, true>, false, true, false, 0 }
+#define PTX_CFG_BF16(BM, BN, BK, WM, WN, MT) \
+    { BM, BN, BK, WM, WN, MT, #BM "x" #BN "x" #BK "/" #WM "x" #WN "/m" #MT "/dma/bf16", \
+      launch_cfg<BM, BN, BK, WM, WN, MT, true, 2, 2>, false, true, false, 0, true }
 #define PTX_CFG_X3(BM, BN, BK, WM, WN, MT) \
     { BM, BN, BK, WM, WN, MT, #BM "x" #BN "x" #BK "/" #WM "x" #WN "/m" #MT "/dma/x3", \
       launch_cfg<BM, BN, BK, WM, WN, MT, true, 2, false, true>, false, false, true, 0 }
@@ -505,6 +513,23 @@ static const ConvConfig kConfigs[] = {
     PTX_CFG_X3RE(32, 64, 64, 2, 2, 16, 3),    // 150
     PTX_CFG_X3RE(32, 128, 64, 2, 2, 16, 2),   // 151
     PTX_CFG_X3RE(128, 64, 32, 2, 2, 32, 2),   // 152
+    // bf16 operands (the bf16 video ResNets): the f16 tile family on v_mfma_f32_32x32x16_bf16 / 16x16x32_bf16.  BK counts
+    // 32-bit words (2 channels); BK 16 serves the folded stem (kH*kW*3 = 147 -> 160 channels = 5 chunks of 16 words)
+    PTX_CFG_BF16(128, 128, 32, 4, 2, 32),  // 153
+    PTX_CFG_BF16(128, 64, 32, 4, 2, 32),   // 154
+    PTX_CFG_BF16(64, 64, 32, 2, 2, 32),    // 155
+    PTX_CFG_BF16(64, 128, 32, 2, 2, 32),   // 156
+    PTX_CFG_BF16(256, 128, 32, 4, 2, 32),  // 157
+    PTX_CFG_BF16(256, 64, 32, 4, 1, 32),   // 158
+    PTX_CFG_BF16(128, 64, 32, 2, 2, 32),   // 159
+    PTX_CFG_BF16(32, 64, 32, 2, 2, 16),    // 160 small M
+    PTX_CFG_BF16(32, 128, 32, 2, 2, 16),   // 161 small M, wide
+    PTX_CFG_BF16(64, 32, 32, 2, 2, 16),    // 162 narrow outputs ((2+1)D mid widths)
+    PTX_CFG_BF16(128, 128, 16, 4, 2, 32),  // 163
+    PTX_CFG_BF16(128, 64, 16, 4, 2, 32),   // 164 stem
+    PTX_CFG_BF16(256, 64, 16, 4, 1, 32),   // 165 stem
+    PTX_CFG_BF16(64, 64, 16, 2, 2, 32),    // 166
+    PTX_CFG_BF16(128, 32, 16, 4, 1, 32),   // 167 the (2+1)D spatial stem (83 channels: 3 x 32 columns)
 };
 constexpr int kNumConfigs = sizeof(kConfigs) / sizeof(kConfigs[0]);
 
@@ -563,6 +588,8 @@ int validate_desc(const ptx_conv3d_desc* d) {
             return fail(PTX_ERR_INVALID, "conv3d: PTX_PRO_UP2 needs a unit-stride 2-D conv over even (upsampled) extents");
     }
     if ((d->flags & PTX_EPI_RELU) && (d->flags & PTX_EPI_TANH)) return fail(PTX_ERR_INVALID, "conv3d: RELU and TANH are exclusive");
+    if ((d->flags & PTX_BF16_OPERANDS) && !(d->flags & PTX_F16_OPERANDS))
+        return fail(PTX_ERR_INVALID, "conv3d: PTX_BF16_OPERANDS modifies PTX_F16_OPERANDS (16-bit operands, bf16 flavour)");
     if (d->flags & PTX_F16X3_OPERANDS) {
         if (d->flags & PTX_F16_OPERANDS) return fail(PTX_ERR_INVALID, "conv3d: PTX_F16_OPERANDS and PTX_F16X3_OPERANDS are exclusive");
         if (d->Kc % 8 || d->groups > 1)
@@ -576,7 +603,21 @@ int validate_desc(const ptx_conv3d_desc* d) {
 
 using namespace ptx;
 
-extern "C" int ptx_conv3d_num_configs(void) { return kNumConfigs; }
+// The bf16 tiles close the table: indices [ptx_conv3d_num_configs(), + ptx_conv3d_num_configs_bf16()).  The first count keeps
+// meaning "the fp32 / f16 / x3 tiles", so a caller that enumerates it and classifies tiles by name never meets a bf16 tile.
+static int first_bf16_config() {
+    static const int first = [] {
+        int f = kNumConfigs;
+        while (f > 0 && kConfigs[f - 1].bf16) --f;
+        for (int i = 0; i < f; ++i)
+            if (kConfigs[i].bf16) { fprintf(stderr, "libptx_amd: bf16 tile configurations must close the table\n"); abort(); }
+        return f;
+    }();
+    return first;
+}
+
+extern "C" int ptx_conv3d_num_configs(void) { return first_bf16_config(); }
+extern "C" int ptx_conv3d_num_configs_bf16(void) { return kNumConfigs - first_bf16_config(); }
 
 extern "C" const char* ptx_conv3d_config_name(int config) {
     if (config < 0 || config >= kNumConfigs) return "invalid";
@@ -596,6 +637,7 @@ extern "C" int ptx_conv3d_config_supported(const ptx_conv3d_desc* d, int config)
     const ConvConfig& c = kConfigs[config];
     if (((d->flags & PTX_F16_OPERANDS) != 0) != (c.f16 != 0)) return 0;          // operand kind <-> tile kind
     if (((d->flags & PTX_F16X3_OPERANDS) != 0) != (c.x3 != 0)) return 0;
+    if (((d->flags & PTX_BF16_OPERANDS) != 0) != c.bf16) return 0;
     const int groups = d->groups > 1 ? d->groups : 1;
     const bool dual = d->x2_C > 0;
     if (c.kwr) {                                                                  // kw-reuse tiles: whole output rows of a
@@ -616,6 +658,16 @@ extern "C" int ptx_conv3d_pick_config(const ptx_conv3d_desc* d, int* split_k) {
     const int taps = d->kT * d->kH * d->kW;
     const int ncol = (d->Co + 3) / 4 * 4;
     int cfg;
+    if (d->flags & PTX_BF16_OPERANDS) {          // bf16 operands: defaults; the tuner refines them
+        if (d->Kc % 32 && d->Kc % 16 == 0) {     // the folded stem (80 words per tap): BK 16
+            if (ncol <= 96) return PTX_TILE("128x32x16/4x1/m32/dma/bf16");
+            return M >= 256 * 1024 ? PTX_TILE("256x64x16/4x1/m32/dma/bf16") : PTX_TILE("64x64x16/2x2/m32/dma/bf16");
+        }
+        if (M < 8192) return ncol >= 128 ? PTX_TILE("32x128x32/2x2/m16/dma/bf16") : PTX_TILE("32x64x32/2x2/m16/dma/bf16");
+        if (ncol <= 48) return PTX_TILE("64x32x32/2x2/m16/dma/bf16");
+        if (ncol >= 128 && cdiv64(M, 128) * cdiv(ncol, 128) >= 2 * kNumCU) return PTX_TILE("128x128x32/4x2/m32/dma/bf16");
+        return ncol >= 128 ? PTX_TILE("64x128x32/2x2/m32/dma/bf16") : PTX_TILE("128x64x32/4x2/m32/dma/bf16");
+    }
     if (d->flags & PTX_F16_OPERANDS) {
         const int64_t Mrows = (int64_t)d->N * d->To * d->Ho * d->Wo;
         return ncol <= 16 ? PTX_TILE("256x16x32/8x1/m16/dma/f16") : ncol <= 32 ? PTX_TILE("64x32x32/2x2/m16/dma/f16")
@@ -747,6 +799,8 @@ int launch_conv(ConvArgs& a, int config, int split_k, int batch, void* workspace
         return fail(PTX_ERR_UNSUPPORTED, "conv3d: fp16-operand problems run on the /f16 tile configurations only (and vice versa)");
     if ((a.x3 != 0) != c.x3)
         return fail(PTX_ERR_UNSUPPORTED, "conv3d: split-operand problems run on the /x3 tile configurations only (and vice versa)");
+    if ((a.bf16 != 0) != c.bf16)
+        return fail(PTX_ERR_UNSUPPORTED, "conv3d: bf16-operand problems run on the /bf16 tile configurations only (and vice versa)");
     {
         const int fs = finalize_conv_args(a, c.BM, c.BN, c.BK, c.kwr, c.direct, split_k, batch);
         if (fs != PTX_OK) return fs;
@@ -860,6 +914,7 @@ int make_conv_args(const ptx_conv3d_desc* d, const float* x, const float* x2, co
     }
     a.f16 = (d->flags & PTX_F16_OPERANDS) ? 1 : 0;
     a.x3 = (d->flags & PTX_F16X3_OPERANDS) ? 1 : 0;
+    a.bf16 = (a.f16 && (d->flags & PTX_BF16_OPERANDS)) ? 1 : 0;
     if (a.f16 && (x2 || d->groups > 1)) return fail(PTX_ERR_UNSUPPORTED, "conv3d: fp16 operands: single-source dense convs only");
     a.up2 = (d->flags & PTX_PRO_UP2) ? 1 : 0;
     a.Hp = a.up2 ? d->Hi / 2 : d->Hi;

@@ -39,6 +39,7 @@ struct ConvArgs {
     unsigned x2_bytes;
     int groups, cig, cog;  // grouped conv: input / output channels per group
     int f16;               // A / B operands are halfs; K extents count 32-bit words
+    int bf16;              // with f16: the 16-bit operands (and PTX_EPI_OUT_F16 / PTX_RES_F16 tensors) are bfloat16
     unsigned dv_hw[2];     // KWR tiles: fast division by the halo'd run length Wo + kW - 1
     int x3;                // fp32 A split into half (hi, lo) pairs on the fly, B packed as (hi8 | lo8) blocks: 3 f16 MFMAs
     unsigned x_bytes, w_bytes, y_bytes, r_bytes;   // extents of one batch item (buffer-resource bounds)
@@ -108,6 +109,7 @@ __device__ __forceinline__ void post_barrier_offsets(int& a, int& b) {
 }
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 template <int MT> struct Mfma;
 template <> struct Mfma<32> {
     using acc_t = f32x16;
@@ -118,6 +120,10 @@ template <> struct Mfma<32> {
     // fp16 operands: the same 16-byte fragment holds 8 halfs = K 16 per lane group pair, one instruction
     static __device__ __forceinline__ acc_t mma16(f32x4 a, f32x4 b, acc_t c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
+    }
+    // bf16 operands: same fragment layout (gfx950 A / B lane maps and C / D layout match the f16 form)
+    static __device__ __forceinline__ acc_t mma16bf(f32x4 a, f32x4 b, acc_t c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
     }
     static __device__ __forceinline__ int row(int r, int lane) {
         return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -131,6 +137,9 @@ template <> struct Mfma<16> {
     }
     static __device__ __forceinline__ acc_t mma16(f32x4 a, f32x4 b, acc_t c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ acc_t mma16bf(f32x4 a, f32x4 b, acc_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
     }
     static __device__ __forceinline__ int row(int r, int lane) { return (lane >> 4) * 4 + r; }
 };
@@ -192,6 +201,7 @@ __device__ __forceinline__ float fused_skip(const ConvArgs& p, int m, int co) {
                   rw = up ? wo >> p.res_sW : wo * p.res_sW;
         idx = ((((size_t)n * p.res_T + rt) * p.res_H + rh) * p.res_W + rw) * p.ldr + co;
     }
+    if (r16 && p.bf16) return (float)reinterpret_cast<const __bf16*>(p.res)[idx];
     return r16 ? (float)reinterpret_cast<const _Float16*>(p.res)[idx] : p.res[idx];
 }
 
@@ -213,6 +223,32 @@ __device__ __forceinline__ void fused_value(const ConvArgs& p, float acc, int m,
 // segments.  (Straight from the MFMA layout -- one column per lane -- the same work was 2-byte skip loads and
 // 4-byte stores: config-5's 1x1 convs, which are all epilogue, ran at 1.6-2.1 TB/s.)
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+
+// 8 fp32 values -> 8 16-bit values in one 16-byte word: halfs, or (BF) bfloat16 by a plain cast (v_cvt_pk_bf16_f32:
+// round to nearest even, NaN preserved); and back
+template <bool BF>
+__device__ __forceinline__ f32x4 pack16x8(f32x4 a, f32x4 b) {
+    if constexpr (BF) {
+        const bf16x8 h = {(__bf16)a[0], (__bf16)a[1], (__bf16)a[2], (__bf16)a[3], (__bf16)b[0], (__bf16)b[1], (__bf16)b[2], (__bf16)b[3]};
+        return __builtin_bit_cast(f32x4, h);
+    } else {
+        const half8_t h = {(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3],
+                           (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
+        return __builtin_bit_cast(f32x4, h);
+    }
+}
+template <bool BF>
+__device__ __forceinline__ void unpack16x8(f32x4 w, f32x4& lo, f32x4& hi) {
+    if constexpr (BF) {
+        const bf16x8 h = __builtin_bit_cast(bf16x8, w);
+        lo = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+        hi = f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+    } else {
+        const half8_t h = __builtin_bit_cast(half8_t, w);
+        lo = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+        hi = f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+    }
+}
 
 // How many of a row block's passes get their skip operand early: 16 bytes per lane and pass stay live across the k-loop, and
 // the 8-wave 128x128 tile has ten registers to spare below the 128 that keep two workgroups on a CU.
@@ -260,7 +296,7 @@ __device__ __forceinline__ void fused_stage_skip_prefetch(const ConvArgs& p, f32
     }
 }
 
-template <class MF, int TM, int TN, int WTM, int WTN, int MT>
+template <class MF, int TM, int TN, int WTM, int WTN, int MT, bool BF = false>
 __device__ __forceinline__ void fused_stage_epilogue(const ConvArgs& p, typename MF::acc_t (&acc)[TM][TN], int m0, int n0,
                                                      int wm, int wn, int lane, float* smem, int wave, const f32x4* rq, bool have_rq) {
     constexpr int NACC = MF::NACC;
@@ -337,11 +373,11 @@ __device__ __forceinline__ void fused_stage_epilogue(const ConvArgs& p, typename
                 const unsigned e = pos * (unsigned)p.ldr + (unsigned)co8;
                 const bool q0 = ok0 && co8 < res_lim, q1 = ok1 && co8 + 4 < res_lim;
                 if (r16) {               // 8 halfs = one 16-byte load (channels beyond res_lim inside it are masked below)
-                    const half8_t h = (have_rq && ps < kSkipEarlyPasses)
-                                          ? __builtin_bit_cast(half8_t, rq[i * (NP < kSkipEarlyPasses ? NP : kSkipEarlyPasses) + ps])   // requested before the k-loop
-                                              : __builtin_bit_cast(half8_t, __builtin_amdgcn_raw_buffer_load_b128(rs_res, q0 ? e * 2u : kOOB, 0, 0));
-                    k0 = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-                    k1 = q1 ? f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]} : f32x4{0.f, 0.f, 0.f, 0.f};
+                    const f32x4 h = (have_rq && ps < kSkipEarlyPasses)
+                                        ? rq[i * (NP < kSkipEarlyPasses ? NP : kSkipEarlyPasses) + ps]   // requested before the k-loop
+                                        : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, q0 ? e * 2u : kOOB, 0, 0));
+                    unpack16x8<BF>(h, k0, k1);
+                    if (!q1) k1 = f32x4{0.f, 0.f, 0.f, 0.f};
                 } else {
                     k0 = ld4(rs_res, q0 ? e * 4u : kOOB);
                     k1 = ld4(rs_res, q1 ? e * 4u + 16u : kOOB);
@@ -368,8 +404,7 @@ __device__ __forceinline__ void fused_stage_epilogue(const ConvArgs& p, typename
                 for (int e = 0; e < 4; ++e) { v0[e] = tanhf(v0[e]); v1[e] = tanhf(v1[e]); }
             }
             if (out16) {
-                const half8_t h = {(_Float16)v0[0], (_Float16)v0[1], (_Float16)v0[2], (_Float16)v0[3],
-                                   (_Float16)v1[0], (_Float16)v1[1], (_Float16)v1[2], (_Float16)v1[3]};
+                const f32x4 h = pack16x8<BF>(v0, v1);
                 // ldy % 8 == 0 halfs and co8 % 8 == 0: the 16-byte store stays inside the row (pad columns get
                 // the affine of zero -- finite, and multiplied by zero filter columns downstream)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, h), rs_y,
@@ -380,8 +415,7 @@ __device__ __forceinline__ void fused_stage_epilogue(const ConvArgs& p, typename
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v1), rs_y, ok1 ? off + 16u : kOOB, 0, 0);
             }
             if (dual) {
-                const half8_t h = {(_Float16)r0[0], (_Float16)r0[1], (_Float16)r0[2], (_Float16)r0[3],
-                                   (_Float16)r1[0], (_Float16)r1[1], (_Float16)r1[2], (_Float16)r1[3]};
+                const f32x4 h = pack16x8<BF>(r0, r1);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, h), rs_raw,
                                                        ok0 ? ((unsigned)m * (unsigned)p.ld_raw + (unsigned)co8) * 2u : kOOB, 0, 0);
             }
@@ -558,7 +592,7 @@ static __device__ unsigned long long* g_ig_tl = nullptr;
 // Args: ConvArgs as a kernel argument (plain launch), or the same struct read through a constant-address-space reference
 // (conv program: the stage table in global memory is never written during the launch, so its fields are scalar loads the
 // compiler may repeat instead of keeping ~120 SGPRs alive across the k-loop -- a by-value copy spilled 269 of them).
-template <int BM, int BN, int BK, int WM, int WN, int MT, bool KTAIL, bool K22, bool DMA, int NSTAGE, bool F16 = false,
+template <int BM, int BN, int BK, int WM, int WN, int MT, bool KTAIL, bool K22, bool DMA, int NSTAGE, int F16 = 0,
           bool X3 = false, int KWR = 0, bool CHAIN = false, bool REPI = false, int COH = 0, class Args = ConvArgs>
 __device__ __forceinline__ void conv_igemm_tile(const Args& p, const int tile, const int zb, const int zs, float* smem) {
     PTX_IG_TL(0);
@@ -1068,7 +1102,10 @@ __device__ __forceinline__ void conv_igemm_tile(const Args& p, const int tile, c
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = MF::mma16(fa[slot][i][0], fb[slot][j][0], acc[i][j]);
+                for (int j = 0; j < TN; ++j) {
+                    if constexpr (F16 == 2) acc[i][j] = MF::mma16bf(fa[slot][i][0], fb[slot][j][0], acc[i][j]);
+                    else acc[i][j] = MF::mma16(fa[slot][i][0], fb[slot][j][0], acc[i][j]);
+                }
             return;
         }
         if constexpr (X3) {
@@ -1466,7 +1503,7 @@ __device__ __forceinline__ void conv_igemm_tile(const Args& p, const int tile, c
     }
     if constexpr (F16) {
         if (fused_epi) {          // generator stage: per-sample affine / halfs out / dual output / half skip / tanh
-            fused_stage_epilogue<MF, TM, TN, WTM, WTN, MT>(p, acc, m0, n0, wm, wn, lane, smem, wave_u, skip_rq, skip_early);
+            fused_stage_epilogue<MF, TM, TN, WTM, WTN, MT, F16 == 2>(p, acc, m0, n0, wm, wn, lane, smem, wave_u, skip_rq, skip_early);
             return;
         }
     }
@@ -1606,7 +1643,7 @@ __device__ __forceinline__ void conv_igemm_tile(const Args& p, const int tile, c
 }
 
 // one tile per workgroup: the plain launch
-template <int BM, int BN, int BK, int WM, int WN, int MT, bool KTAIL, bool K22, bool DMA, int NSTAGE, bool F16 = false,
+template <int BM, int BN, int BK, int WM, int WN, int MT, bool KTAIL, bool K22, bool DMA, int NSTAGE, int F16 = 0,
           bool X3 = false, int KWR = 0, bool CHAIN = false, bool REPI = false>
 __global__ void __launch_bounds__(64 * WM * WN) conv_igemm_kernel(const ConvArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];

@@ -66,7 +66,8 @@ __global__ void __launch_bounds__(256) pack_weight_kernel(ptx_pack_desc d, const
             _Float16* o = reinterpret_cast<_Float16*>(out) + row_h + (size_t)(k >> 3) * 16 + (k & 7);
             o[0] = hi;
             o[8] = lo;
-        } else if (d.f16) reinterpret_cast<_Float16*>(out)[dst] = (_Float16)v;     // round-to-nearest-even
+        } else if (d.f16 == 3) reinterpret_cast<__bf16*>(out)[dst] = (__bf16)v;       // bf16: one rounding of the folded value
+        else if (d.f16) reinterpret_cast<_Float16*>(out)[dst] = (_Float16)v;     // round-to-nearest-even
         else out[dst] = v;
     }
 }
@@ -298,6 +299,112 @@ __global__ void __launch_bounds__(256) checksum_f32_kernel(const long long* __re
     if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out, acc);
 }
 
+// the same sum over 16-bit elements (bf16 / fp16 parameter tensors); table counts are 16-bit elements
+__global__ void __launch_bounds__(256) checksum_b16_kernel(const long long* __restrict__ table, int n,
+                                                           unsigned long long* __restrict__ out) {
+    const int t = blockIdx.y;
+    const unsigned short* __restrict__ p = reinterpret_cast<const unsigned short*>(table[2 * t]);
+    const long long cnt = table[2 * t + 1];
+    unsigned long long acc = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (long long)gridDim.x * 256)
+        acc += (unsigned long long)(p[i] + 1u) * (unsigned long long)(2654435761u * (unsigned)i | 1u);
+    acc *= (unsigned long long)(2 * t + 1);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)acc, o, 64);
+        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(acc >> 32), o, 64);
+        acc += ((unsigned long long)hi << 32) | lo;
+    }
+    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out, acc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// bf16 plans: 16-bit NCDHW <-> NDHWC tile transposes (bit-exact moves, 32 x 32 elements through LDS), the (kh, kw) fold
+// of the RGB stem, and the rounding of the logits
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) ncs_to_nsc_b16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
+                                                             int C, long long S, int ld) {
+    __shared__ unsigned short tile[32][33];
+    const int n = blockIdx.z;
+    const long long s0 = (long long)blockIdx.x * 32;
+    const int c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const unsigned short* xn = x + (size_t)n * C * S;
+    unsigned short* yn = y + (size_t)n * S * ld;
+#pragma unroll
+    for (int j = 0; j < 32; j += 8) {
+        const int c = c0 + ty + j;
+        const long long s = s0 + tx;
+        tile[ty + j][tx] = (c < C && s < S) ? xn[(size_t)c * S + s] : (unsigned short)0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 32; j += 8) {
+        const long long s = s0 + ty + j;
+        const int c = c0 + tx;
+        if (s < S && c < ld) yn[(size_t)s * ld + c] = tile[tx][ty + j];   // zero beyond C by construction
+    }
+}
+
+__global__ void __launch_bounds__(256) nsc_to_ncs_b16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
+                                                             int C, long long S, int ld) {
+    __shared__ unsigned short tile[32][33];
+    const int n = blockIdx.z;
+    const long long s0 = (long long)blockIdx.x * 32;
+    const int c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const unsigned short* xn = x + (size_t)n * S * ld;
+    unsigned short* yn = y + (size_t)n * C * S;
+#pragma unroll
+    for (int j = 0; j < 32; j += 8) {
+        const long long s = s0 + ty + j;
+        const int c = c0 + tx;
+        tile[ty + j][tx] = (s < S && c < C) ? xn[(size_t)s * ld + c] : (unsigned short)0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 32; j += 8) {
+        const int c = c0 + ty + j;
+        const long long s = s0 + tx;
+        if (c < C && s < S) yn[(size_t)c * S + s] = tile[tx][ty + j];
+    }
+}
+
+// one thread per 8 output columns (one 16-byte store) of one output position: column k = (kh * kW + kw) * C + c gathers
+// x[n][c][t][ho*sH - pH + kh][wo*sW - pW + kw] (zero outside the image and for k >= kH * kW * C)
+__global__ void __launch_bounds__(256) im2col_hw_bf16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
+                                                             int C, int T, int H, int W, int kH, int kW, int sH, int sW,
+                                                             int pH, int pW, int Ho, int Wo, int ld, long long total) {
+    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+    const int g8 = ld / 8, kk = kH * kW * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long pos = i / g8;
+        const int k0 = (int)(i - pos * g8) * 8;
+        const int wo = (int)(pos % Wo);
+        long long r = pos / Wo;
+        const int ho = (int)(r % Ho);
+        r /= Ho;
+        const int t = (int)(r % T);
+        const long long n = r / T;
+        u16x8 v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int k = k0 + e;
+            const int c = k % C, tap = k / C;
+            const int kh = tap / kW, kw = tap - (tap / kW) * kW;
+            const int h = ho * sH - pH + kh, w = wo * sW - pW + kw;
+            const bool ok = k < kk && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
+            v[e] = ok ? x[(((size_t)n * C + c) * T + t) * (size_t)H * W + (size_t)h * W + w] : (unsigned short)0;
+        }
+        *reinterpret_cast<u16x8*>(y + (size_t)i * 8) = v;
+    }
+}
+
+__global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restrict__ x, __bf16* __restrict__ y, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        y[i] = (__bf16)x[i];      // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
+}
+
 }  // namespace ptx
 
 using namespace ptx;
@@ -330,11 +437,12 @@ extern "C" int ptx_pack_conv_weight(const ptx_pack_desc* d, const float* w, cons
                               d->co_per_super % d->sub_groups || d->Co % d->co_per_super))
         return fail(PTX_ERR_INVALID, "pack: super-group packing needs sub_groups | Ci, sub_groups | co_per_super | Co, no kW fold");
     const int keff = d->fold_kw ? d->kW * d->Ci : d->Ci;
-    if (d->f16 == 1 && (d->Kc % 8 || d->ld_k || d->k_off))
+    if ((d->f16 == 1 || d->f16 == 3) && (d->Kc % 8 || d->ld_k || d->k_off))
         return fail(PTX_ERR_INVALID, "pack: fp16 filters need Kc %% 8 == 0 and no K-concatenation window");
     if (d->f16 == 2 && (d->Kc % 8 || d->ld_k % 8 || d->k_off % 8 || d->sub_groups > 1))
         return fail(PTX_ERR_INVALID, "pack: split (hi8 | lo8) filters need Kc, ld_k and k_off %% 8 == 0, no super-groups");
-    if (d->f16 < 0 || d->f16 > 2) return fail(PTX_ERR_INVALID, "pack: f16 must be 0 (fp32), 1 (halfs) or 2 (split halfs)");
+    if (d->f16 < 0 || d->f16 > 3)
+        return fail(PTX_ERR_INVALID, "pack: f16 must be 0 (fp32), 1 (halfs), 2 (split halfs) or 3 (bf16)");
     if (d->Kc < keff || d->Kc % 4 || d->Co_pad < d->Co || d->Co_pad % 128)
         return fail(PTX_ERR_INVALID, "pack: Kc=%d must cover K=%d (multiple of 4); Co_pad=%d must cover Co=%d (multiple of 128)",
                     d->Kc, keff, d->Co_pad, d->Co);
@@ -541,4 +649,65 @@ extern "C" int ptx_checksum_f32(const int64_t* table, int32_t n, uint64_t* out, 
     hipLaunchKernelGGL(checksum_f32_kernel, dim3(32, (unsigned)n), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const long long*>(table), n, reinterpret_cast<unsigned long long*>(out));
     return hip_check(hipGetLastError(), "checksum launch");
+}
+
+extern "C" int ptx_checksum_b16(const int64_t* table, int32_t n, uint64_t* out, ptx_stream_t stream) {
+    if (!table || !out || n <= 0) return fail(PTX_ERR_INVALID, "checksum_b16: null pointer / empty table");
+    if (n > 65535) return fail(PTX_ERR_UNSUPPORTED, "checksum_b16: more than 65535 tensors");
+    hipLaunchKernelGGL(checksum_b16_kernel, dim3(32, (unsigned)n), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const long long*>(table), n, reinterpret_cast<unsigned long long*>(out));
+    return hip_check(hipGetLastError(), "checksum_b16 launch");
+}
+
+static int check_layout_b16(const void* x, const void* y, int N, int C, int64_t S, int ld, const void* cl) {
+    if (!x || !y) return fail(PTX_ERR_INVALID, "layout_bf16: null pointer");
+    if (N <= 0 || C <= 0 || S <= 0 || ld < C || ld % 8) return fail(PTX_ERR_INVALID, "layout_bf16: bad extents (ld %% 8 == 0, >= C)");
+    if (N > 65535 || cdiv(ld, 32) > 65535 || cdiv64(S, 32) > 0x7fffffffLL) return fail(PTX_ERR_INVALID, "layout_bf16: extents too large for the grid");
+    if ((uintptr_t)cl & 15) return fail(PTX_ERR_INVALID, "layout_bf16: the channels-last tensor must be 16-byte aligned");
+    if (((uintptr_t)x | (uintptr_t)y) & 1) return fail(PTX_ERR_INVALID, "layout_bf16: misaligned pointer");
+    return PTX_OK;
+}
+
+extern "C" int ptx_ncdhw_to_ndhwc_bf16(const void* x, void* y, int32_t N, int32_t C, int64_t S, int32_t ld, ptx_stream_t stream) {
+    int s = check_layout_b16(x, y, N, C, S, ld, y);
+    if (s) return s;
+    dim3 grid((unsigned)cdiv64(S, 32), (unsigned)cdiv(ld, 32), (unsigned)N);
+    hipLaunchKernelGGL(ncs_to_nsc_b16_kernel, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const unsigned short*>(x),
+                       static_cast<unsigned short*>(y), C, (long long)S, ld);
+    return hip_check(hipGetLastError(), "ncdhw_to_ndhwc_bf16 launch");
+}
+
+extern "C" int ptx_ndhwc_to_ncdhw_bf16(const void* x, void* y, int32_t N, int32_t C, int64_t S, int32_t ld, ptx_stream_t stream) {
+    int s = check_layout_b16(x, y, N, C, S, ld, x);
+    if (s) return s;
+    dim3 grid((unsigned)cdiv64(S, 32), (unsigned)cdiv(C, 32), (unsigned)N);
+    hipLaunchKernelGGL(nsc_to_ncs_b16_kernel, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const unsigned short*>(x),
+                       static_cast<unsigned short*>(y), C, (long long)S, ld);
+    return hip_check(hipGetLastError(), "ndhwc_to_ncdhw_bf16 launch");
+}
+
+extern "C" int ptx_im2col_hw_bf16(const void* x, void* y, int32_t N, int32_t C, int32_t T, int32_t H, int32_t W, int32_t kH,
+                                  int32_t kW, int32_t sH, int32_t sW, int32_t pH, int32_t pW, int32_t Ho, int32_t Wo, int32_t ld,
+                                  ptx_stream_t stream) {
+    if (!x || !y) return fail(PTX_ERR_INVALID, "im2col_hw_bf16: null pointer");
+    if (N <= 0 || C <= 0 || T <= 0 || H <= 0 || W <= 0 || kH <= 0 || kW <= 0 || sH <= 0 || sW <= 0 || pH < 0 || pW < 0 ||
+        Ho <= 0 || Wo <= 0)
+        return fail(PTX_ERR_INVALID, "im2col_hw_bf16: non-positive extent");
+    if (ld % 32 || ld < kH * kW * C) return fail(PTX_ERR_INVALID, "im2col_hw_bf16: ld=%d must cover kH*kW*C=%d, multiple of 32", ld, kH * kW * C);
+    if (Ho != (H + 2 * pH - kH) / sH + 1 || Wo != (W + 2 * pW - kW) / sW + 1)
+        return fail(PTX_ERR_INVALID, "im2col_hw_bf16: output extent does not match the geometry");
+    if (((uintptr_t)x & 1) || ((uintptr_t)y & 15)) return fail(PTX_ERR_INVALID, "im2col_hw_bf16: misaligned pointer");
+    const long long total = (long long)N * T * Ho * Wo * (ld / 8);
+    hipLaunchKernelGGL(im2col_hw_bf16_kernel, dim3(grid_for((size_t)total)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const unsigned short*>(x), static_cast<unsigned short*>(y), C, T, H, W, kH, kW, sH, sW, pH, pW,
+                       Ho, Wo, ld, total);
+    return hip_check(hipGetLastError(), "im2col_hw_bf16 launch");
+}
+
+extern "C" int ptx_f32_to_bf16(const float* x, void* y, int64_t n, ptx_stream_t stream) {
+    if (!x || !y || n <= 0) return fail(PTX_ERR_INVALID, "f32_to_bf16: null pointer / empty");
+    if ((uintptr_t)y & 1) return fail(PTX_ERR_INVALID, "f32_to_bf16: misaligned output");
+    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, (hipStream_t)stream, x,
+                       static_cast<__bf16*>(y), (long long)n);
+    return hip_check(hipGetLastError(), "f32_to_bf16 launch");
 }

@@ -329,6 +329,69 @@ __global__ void __launch_bounds__(256) avgpool_cl_kernel(const float* __restrict
     }
 }
 
+// the same pool over a bf16 map (bf16 plans): fp32 sums in the same order as avgpool_cl_kernel, fp32 result
+__global__ void __launch_bounds__(256) avgpool_cl_bf16_kernel(const __bf16* __restrict__ x, float* __restrict__ y, int C,
+                                                              long long S, int ld) {
+    __shared__ float part[4][64];
+    const int n = blockIdx.y;
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int g = threadIdx.x >> 6;
+    float acc = 0.f;
+    if (c < C) {
+        const __bf16* xn = x + (size_t)n * S * ld + c;
+        for (long long s = g; s < S; s += 4) acc += (float)xn[(size_t)s * ld];
+    }
+    part[g][threadIdx.x & 63] = acc;
+    __syncthreads();
+    if (g == 0 && c < C) {
+        const int l = threadIdx.x & 63;
+        y[(size_t)n * C + c] = (part[0][l] + part[1][l] + part[2][l] + part[3][l]) / (float)S;
+    }
+}
+
+// max_pool3d over bf16 maps (PTX_POOL_BF16): 8 channels (16 bytes) per thread; exact (a max of bf16 values is one of them)
+__global__ void __launch_bounds__(256) maxpool3d_bf16_kernel(ptx_pool3d_desc d, const __bf16* __restrict__ x,
+                                                             __bf16* __restrict__ y, size_t total8) {
+    typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+    const int f8r = (d.C + 7) / 8;
+    const int ldy = d.ldy ? d.ldy : d.ld;
+    const bool pad_zero = (d.flags & PTX_POOL_PAD_ZERO) != 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total8; i += (size_t)gridDim.x * 256) {
+        const int q = (int)(i % f8r);
+        size_t pos = i / f8r;
+        const int wo = (int)(pos % d.Wo);
+        size_t t1 = pos / d.Wo;
+        const int ho = (int)(t1 % d.Ho);
+        t1 /= d.Ho;
+        const int to = (int)(t1 % d.To);
+        const int n = (int)(t1 / d.To);
+        const int t_lo = max(0, to * d.sT - d.pT), t_hi = min(d.Ti, to * d.sT - d.pT + d.kT);
+        const int h_lo = max(0, ho * d.sH - d.pH), h_hi = min(d.Hi, ho * d.sH - d.pH + d.kH);
+        const int w_lo = max(0, wo * d.sW - d.pW), w_hi = min(d.Wi, wo * d.sW - d.pW + d.kW);
+        float m[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
+        for (int t = t_lo; t < t_hi; ++t)
+            for (int h = h_lo; h < h_hi; ++h) {
+                const __bf16* row = x + ((((size_t)n * d.Ti + t) * d.Hi + h) * d.Wi) * d.ld + q * 8;
+                for (int w = w_lo; w < w_hi; ++w) {
+                    const bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(row + (size_t)w * d.ld);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], (float)v[e]);
+                }
+            }
+        if (pad_zero && ((t_hi - t_lo) != d.kT || (h_hi - h_lo) != d.kH || (w_hi - w_lo) != d.kW)) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], 0.f);
+        }
+        bf16x8_t o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (__bf16)m[e];          // exact: m[e] is a bf16 value (or 0)
+        // pad channels [C, round_up(C,8)) hold zeros on input, so they stay zero on output
+        *reinterpret_cast<bf16x8_t*>(y + pos * ldy + q * 8) = o;
+    }
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -717,8 +780,36 @@ static unsigned grid_for(size_t work_items) {
 
 using namespace ptx;
 
+static int maxpool3d_bf16(const ptx_pool3d_desc* d, const void* x, void* y, hipStream_t st) {
+    if (d->N <= 0 || d->C <= 0 || d->ld < d->C || d->ld % 8 || d->kT <= 0 || d->kH <= 0 || d->kW <= 0 || d->sT <= 0 ||
+        d->sH <= 0 || d->sW <= 0 || d->pT < 0 || d->pH < 0 || d->pW < 0 || d->To <= 0 || d->Ho <= 0 || d->Wo <= 0)
+        return fail(PTX_ERR_INVALID, "maxpool3d (bf16): bad descriptor (ld %% 8 == 0)");
+    const int c8 = (d->C + 7) / 8 * 8;
+    if (d->ldy < 0 || (d->ldy > 0 && (d->ldy < c8 || d->ldy % 8)) || (d->ldy == 0 && d->ld < c8))
+        return fail(PTX_ERR_INVALID, "maxpool3d (bf16): output stride must cover round_up(C, 8) and be a multiple of 8");
+    if (d->flags & PTX_POOL_SAME) {
+        if (d->pT >= d->kT || d->pH >= d->kH || d->pW >= d->kW || (d->To - 1) * d->sT - d->pT >= d->Ti ||
+            (d->Ho - 1) * d->sH - d->pH >= d->Hi || (d->Wo - 1) * d->sW - d->pW >= d->Wi)
+            return fail(PTX_ERR_INVALID, "maxpool3d: SAME geometry leaves a window without a valid tap");
+    } else {
+        if (2 * d->pT > d->kT || 2 * d->pH > d->kH || 2 * d->pW > d->kW)
+            return fail(PTX_ERR_INVALID, "maxpool3d: padding larger than half the window");
+        const int to = (d->Ti + 2 * d->pT - d->kT) / d->sT + 1;
+        const int ho = (d->Hi + 2 * d->pH - d->kH) / d->sH + 1;
+        const int wo = (d->Wi + 2 * d->pW - d->kW) / d->sW + 1;
+        if (to != d->To || ho != d->Ho || wo != d->Wo) return fail(PTX_ERR_INVALID, "maxpool3d: output extent mismatch");
+    }
+    if (((uintptr_t)x | (uintptr_t)y) & 15) return fail(PTX_ERR_INVALID, "maxpool3d: misaligned pointer");
+    const size_t total8 = (size_t)d->N * d->To * d->Ho * d->Wo * (c8 / 8);
+    hipLaunchKernelGGL(maxpool3d_bf16_kernel, dim3(grid_for(total8)), dim3(256), 0, st, *d, static_cast<const __bf16*>(x),
+                       static_cast<__bf16*>(y), total8);
+    return hip_check(hipGetLastError(), "maxpool3d (bf16) launch");
+}
+
 extern "C" int ptx_maxpool3d_fwd(const ptx_pool3d_desc* d, const float* x, float* y, ptx_stream_t stream) {
     if (!d || !x || !y) return fail(PTX_ERR_INVALID, "maxpool3d: null pointer");
+    if (d->flags & ~(PTX_POOL_SAME | PTX_POOL_PAD_ZERO | PTX_POOL_BF16)) return fail(PTX_ERR_INVALID, "maxpool3d: unknown flags");
+    if (d->flags & PTX_POOL_BF16) return maxpool3d_bf16(d, x, y, (hipStream_t)stream);
     if (d->N <= 0 || d->C <= 0 || d->ld < d->C || d->ld % 4 || d->kT <= 0 || d->kH <= 0 || d->kW <= 0 ||
         d->sT <= 0 || d->sH <= 0 || d->sW <= 0 || d->pT < 0 || d->pH < 0 || d->pW < 0 || d->To <= 0 || d->Ho <= 0 ||
         d->Wo <= 0)
@@ -885,6 +976,15 @@ extern "C" int ptx_global_avgpool(const float* x, float* y, int32_t N, int32_t C
                            (hipStream_t)stream, x, y, C, (long long)S, ld);
     }
     return hip_check(hipGetLastError(), "avgpool launch");
+}
+
+extern "C" int ptx_global_avgpool_bf16(const void* x, float* y, int32_t N, int32_t C, int64_t S, int32_t ld, ptx_stream_t stream) {
+    if (!x || !y) return fail(PTX_ERR_INVALID, "avgpool_bf16: null pointer");
+    if (N <= 0 || C <= 0 || S <= 0) return fail(PTX_ERR_INVALID, "avgpool_bf16: non-positive extent");
+    if (ld < C || ld % 8 || N > 65535) return fail(PTX_ERR_INVALID, "avgpool_bf16: bad ld / N");
+    hipLaunchKernelGGL(avgpool_cl_bf16_kernel, dim3((unsigned)cdiv(C, 64), (unsigned)N), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const __bf16*>(x), y, C, (long long)S, ld);
+    return hip_check(hipGetLastError(), "avgpool_bf16 launch");
 }
 
 static int launch_skinny(SkinnyArgs& a, hipStream_t st) {

@@ -26,7 +26,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import (ConvDesc, ConvStage, ConvProgramInfo, NormDesc, PackDesc, PoolDesc, PTX_EPI_RELU, PTX_EPI_RES_ADD, PTX_EPI_RES_PADA,
-                   PTX_EPI_RES_UP, PTX_F16_OPERANDS, PTX_F16X3_OPERANDS, PTX_SPLITK_FUSED, PTX_PRO_RELU, PTX_EPI_ACCUM, PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PtxError, check)
+                   PTX_EPI_RES_UP, PTX_F16_OPERANDS, PTX_F16X3_OPERANDS, PTX_SPLITK_FUSED, PTX_PRO_RELU, PTX_EPI_ACCUM, PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PtxError, check,
+                   PTX_BF16_OPERANDS, PTX_PACK_BF16, PTX_POOL_BF16)
 
 # PTX_TUNED_TABLE: another table file (tuning sessions: A/B a freshly dumped table against the shipped one on the same box)
 _TUNED_PATH = os.environ.get("PTX_TUNED_TABLE") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_gfx950.json")
@@ -68,7 +69,8 @@ def _config_index(name):
     global _cfg_index
     if _cfg_index is None:
         lib = _lib.lib()
-        _cfg_index = {lib.ptx_conv3d_config_name(i).decode(): i for i in range(lib.ptx_conv3d_num_configs())}
+        n = lib.ptx_conv3d_num_configs() + lib.ptx_conv3d_num_configs_bf16()      # the bf16 tiles close the table
+        _cfg_index = {lib.ptx_conv3d_config_name(i).decode(): i for i in range(n)}
     return _cfg_index.get(name)
 
 
@@ -115,12 +117,29 @@ def _tuned_table():
 
 
 def _tile_kind(name):
-    """Operand flavour of a tile configuration by name: "f16" (halfs), "x3" (split fp32 on f16 MFMA) or "" (fp32)."""
-    return "f16" if name.endswith("/f16") else "x3" if name.endswith("/x3") else ""
+    """Operand flavour of a tile configuration by name: "f16" (halfs), "bf16", "x3" (split fp32 on f16 MFMA) or "" (fp32)."""
+    return "f16" if name.endswith("/f16") else "bf16" if name.endswith("/bf16") else "x3" if name.endswith("/x3") else ""
 
 
 def _flags_kind(flags):
+    if flags & PTX_BF16_OPERANDS:
+        return "bf16"
     return "f16" if flags & PTX_F16_OPERANDS else "x3" if flags & PTX_F16X3_OPERANDS else ""
+
+
+# bf16 inference (a model whose floating-point parameters are torch.bfloat16): the families whose plans run end to end on the
+# bf16 kernels.  Everything else raises at plan build time.
+BF16_FAMILIES = ("resnet3d10", "resnet3d18", "resnet3d34", "resnet3d50", "resnet3d101", "resnet3d152", "resnet3d200",
+                 "r2plus1d10", "r2plus1d18", "r2plus1d34", "r2plus1d50")
+
+
+def model_precision(model):
+    """"bf16" when the model's floating-point parameters are torch.bfloat16, "fp16" for torch.float16, else "fp32" -- read
+    from the first weight (a generator step, not a walk of the tree: this runs on every forward)."""
+    w = next(iter(model.parameters()), None)
+    if w is None:
+        w = next((getattr(m, "weight", None) for m in model.modules() if isinstance(getattr(m, "weight", None), torch.Tensor)), None)
+    return {torch.bfloat16: "bf16", torch.float16: "fp16"}.get(getattr(w, "dtype", None), "fp32")
 
 
 def tuned_lookup(key, kind=""):
@@ -213,13 +232,15 @@ def _geom(conv):
 
 class Act:
     """A channels-last activation: tensor [N,T,H,W,ld], C valid channels."""
-    __slots__ = ("t", "N", "T", "H", "W", "C", "ld", "f16")
+    __slots__ = ("t", "N", "T", "H", "W", "C", "ld", "f16", "bf16")
 
-    def __init__(self, dev, N, T, H, W, C_, ld=None, f16=False):
+    def __init__(self, dev, N, T, H, W, C_, ld=None, f16=False, bf16=False):
         self.N, self.T, self.H, self.W, self.C = N, T, H, W, C_
-        self.f16 = bool(f16)       # halfs: the operand of an fp16-MFMA conv (row stride a multiple of 8 halfs)
-        self.ld = ((C_ + 7) // 8 * 8 if f16 else _r4(C_)) if ld is None else ld
-        self.t = torch.empty((N, T, H, W, self.ld), device=dev, dtype=torch.float16 if f16 else torch.float32)
+        self.f16 = bool(f16 or bf16)   # 16-bit: the operand of an fp16-MFMA conv (row stride a multiple of 8 elements)
+        self.bf16 = bool(bf16)         # ... and its bfloat16 flavour (bf16 plans)
+        self.ld = ((C_ + 7) // 8 * 8 if self.f16 else _r4(C_)) if ld is None else ld
+        dt = torch.bfloat16 if bf16 else torch.float16 if f16 else torch.float32
+        self.t = torch.empty((N, T, H, W, self.ld), device=dev, dtype=dt)
         if self.ld != C_ and self.t.device.type != "meta":
             self.t.zero_()
 
@@ -233,7 +254,7 @@ class Act:
         assert c0 % 4 == 0 and c0 + C_ <= self.ld
         assert not self.f16, "channel slices are fp32 only"
         v = Act.__new__(Act)
-        v.f16 = False
+        v.f16 = v.bf16 = False
         v.N, v.T, v.H, v.W, v.C, v.ld = self.N, self.T, self.H, self.W, C_, self.ld
         v.t = self.t[..., c0:c0 + C_]
         return v
@@ -265,11 +286,15 @@ class _Ref:
 class Packed:
     """BN-folded, K-major filter + bias living on one device; refreshable in place."""
 
-    def __init__(self, plan, convs, bn, fold_kw=False, scale=None, f16=False, x3=None, stem4=False):
+    def __init__(self, plan, convs, bn, fold_kw=False, scale=None, f16=False, x3=None, stem4=False, fold_hw=False):
         dev = plan.dev
         self.stem4 = bool(stem4)     # direct split-operand stem (ptx_conv_stem_x3_fwd): Cin zero-padded to 4, kW folded
         self.plan = plan
-        self.f16 = bool(f16)         # filter stored as halfs for an fp16-operand conv
+        # bf16 plans: every filter is stored as bf16 (ptx_pack_desc.f16 == 3) for a bf16-operand conv
+        self.bf16 = bool(getattr(plan, "bf16", False))
+        self.f16 = bool(f16) or self.bf16   # filter stored as 16-bit values for a 16-bit-operand conv
+        # bf16 stem: the (kh, kw) taps folded into the channel axis (ptx_im2col_hw_bf16), a (kT, 1, 1) conv over kH*kW*Cin
+        self.fold_hw = bool(fold_hw)
         # split operands (Engine.precision == "x3"): every dense fp32 filter is packed as (hi8 | lo8) half blocks
         convs = list(convs)          # >1: concatenated along Co (non-local g/theta/phi)
         self.convs = [plan.ref(c) for c in convs]
@@ -283,6 +308,9 @@ class Packed:
         if self.groups > 1 and (len(convs) > 1 or fold_kw):
             raise PtxError("grouped convolutions are packed one at a time, unfolded")
         self.Ci = c0.in_channels // self.groups      # K extent of one filter row (per group)
+        if self.fold_hw:
+            self.Ci = c0.in_channels * kH * kW
+            kH = kW = 1
         self.real_ci = self.Ci
         if self.stem4:
             self.Ci = 4
@@ -302,8 +330,10 @@ class Packed:
                    and (self.Co > 32 or stem4))
         keff = kW * self.Ci if fold_kw else self.Ci
         self.Kc = (keff + 7) // 8 * 8 if (self.f16 or self.x3) else _r4(keff)
-        if self.f16 and (fold_kw or self.groups > 1 or self.Ci % 2):
+        if self.f16 and (fold_kw or self.groups > 1 or (self.Ci % 2 and not self.bf16)):
             raise PtxError("fp16 filters: dense, unfolded convs with an even channel count only")
+        if self.fold_hw:
+            self.Kc = (self.Ci + 31) // 32 * 32      # whole 32-channel (16-word) chunks of the BK = 16 stem tiles
         if fold_kw:
             self.Kc = max(self.Kc, 32 if self.x3 else _stem_ld()) if keff <= 24 else self.Kc
         if self.stem4:
@@ -311,9 +341,10 @@ class Packed:
         self.Co_pad = _r128(self.Co)
         self.k_eff = (kT, kH, 1) if fold_kw else (kT, kH, kW)
         self.d = PackDesc(self.Co, self.Ci, kT, kH, kW, self.Kc, self.Co_pad, int(fold_kw), 0, 0, 0,
-                          self.sub_groups, self.Ci if self.sub_groups else 0, 2 if self.x3 else int(self.f16))
+                          self.sub_groups, self.Ci if self.sub_groups else 0,
+                          PTX_PACK_BF16 if self.bf16 else 2 if self.x3 else int(self.f16))
         n = _lib.lib().ptx_packed_weight_elems(C.byref(self.d))
-        self.w = torch.empty(n, device=dev, dtype=torch.float16 if self.f16 else torch.float32)
+        self.w = torch.empty(n, device=dev, dtype=torch.bfloat16 if self.bf16 else torch.float16 if self.f16 else torch.float32)
         self.b = torch.empty(self.Co_pad, device=dev, dtype=torch.float32)
 
     def refresh(self):
@@ -329,6 +360,16 @@ class Packed:
             cb = torch.cat([c.bias.detach() for c in convs], 0) if convs[0].bias is not None else None
         if self.stem4 and w.shape[1] < 4:             # zero channel(s) up to the 16-byte position the stem kernel reads
             w = torch.cat([w, w.new_zeros((w.shape[0], 4 - w.shape[1]) + tuple(w.shape[2:]))], 1)
+        if self.bf16:
+            # bf16 plans: the BN fold runs in fp32 on the exactly upcast bf16 parameters and buffers; the folded filter
+            # is rounded to bf16 once, by the pack kernel
+            if w.dtype != torch.bfloat16 or not w.is_cuda:
+                raise PtxError("weights of a bf16 model must be bf16 CUDA tensors on the plan's device (got %s)" % w.dtype)
+            if self.fold_hw:          # [Co][Cin][kT][kH][kW] -> [Co][(kh*kW + kw)*Cin + c][kT][1][1] (ptx_im2col_hw_bf16's order)
+                co, ci, kt, kh, kw = w.shape
+                w = w.permute(0, 3, 4, 1, 2).reshape(co, kh * kw * ci, kt, 1, 1)
+            w = w.float()
+            cb = cb.float() if cb is not None else None
         w = w.contiguous()
         if w.dtype != torch.float32 or not w.is_cuda:
             raise PtxError("weights must be fp32 CUDA tensors on the plan's device")
@@ -338,7 +379,7 @@ class Packed:
         keep = [w, cb]
         if bn is not None:
             ts = [bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var]
-            ts = [t.contiguous() for t in ts]
+            ts = [t.float().contiguous() if self.bf16 else t.contiguous() for t in ts]
             keep += ts
             args = [_ptr(t) for t in ts]
             eps = float(bn.eps)
@@ -454,7 +495,9 @@ class ConvStep:
                 return 2.0 * d.N * frames * rows * (-(-d.Ci // 16) * 16) * (-(-_r4(d.Co) // 64) * 64)
             return 2.0 * d.N * frames * rows * 9 * d.Ci * (-(-_r4(d.Co) // 64) * 64)
         tile = _tile_dims(_lib.lib().ptx_conv3d_config_name(self.cfg).decode())
-        return 2.0 * self.macs if tile is None else issued_conv_flop(self.d, tile)
+        # bf16 descriptors count 32-bit words (two channels) along K
+        words = 2 if self.d.flags & PTX_BF16_OPERANDS else 1
+        return 2.0 * self.macs if tile is None else issued_conv_flop(self.d, tile, words)
 
     def __call__(self, st):
         try:
@@ -729,7 +772,14 @@ class Plan:
         self.tuned = False
         self.graph = None
         self.fuse_shortcut = os.environ.get("PTX_FUSE_SHORTCUT", "1") != "0"
-        self.x3 = getattr(engine, "precision", "fp32") == "x3"     # split fp32 operands on the fp16 matrix cores
+        # arithmetic: the model's parameter dtype decides bf16 (every conv on the bf16 tiles, bf16 activations); for fp32
+        # models Engine.precision picks fp32 / x3
+        prec = model_precision(model)
+        if prec == "fp16":
+            raise PtxError("fp16 models (model.half()) are not supported: use bfloat16 (model.to(torch.bfloat16)) or float32")
+        self.bf16 = prec == "bf16"
+        self.precision = "bf16" if self.bf16 else getattr(engine, "precision", "fp32")
+        self.x3 = self.precision == "x3"     # split fp32 operands on the fp16 matrix cores
         # qualified names of the model's modules: everything the plan keeps from the model is a _Ref
         self._names = {id(m): n for n, m in model.named_modules()}
         self._cur = model                # the model (or DataParallel replica) whose tensors are valid right now
@@ -761,15 +811,15 @@ class Plan:
         self._cur = model
 
     # ---------------------------------------------------------------- building blocks
-    def pack(self, convs, bn, fold_kw=False, scale=None, f16=False, x3=None, stem4=False):
+    def pack(self, convs, bn, fold_kw=False, scale=None, f16=False, x3=None, stem4=False, fold_hw=False):
         """scale: (module, attribute name) of a scalar Parameter multiplying the filter.
         x3: force (True) / forbid (False) split operands for this filter; None = the plan's precision."""
         if not isinstance(convs, (list, tuple)):
             convs = [convs]
         key = (tuple(id(c) for c in convs), id(bn), fold_kw, None if scale is None else (id(scale[0]), scale[1]), bool(f16), x3,
-               bool(stem4))
+               bool(stem4), bool(fold_hw))
         if key not in self._pack_cache:
-            p = Packed(self, convs, bn, fold_kw, scale, f16, x3, stem4)
+            p = Packed(self, convs, bn, fold_kw, scale, f16, x3, stem4, fold_hw)
             self._pack_cache[key] = p
             self.packs.append(p)
         return self._pack_cache[key]
@@ -783,7 +833,7 @@ class Plan:
         return self._pack_cache[key]
 
     def act(self, N, T, H, W, C_, ld=None, f16=False):
-        a = Act(self.dev, N, T, H, W, C_, ld, f16)
+        a = Act(self.dev, N, T, H, W, C_, ld, f16, bf16=bool(f16) and self.bf16)
         self.acts.append(a)      # steps hold raw pointers: the plan owns every buffer
         return a
 
@@ -797,6 +847,8 @@ class Plan:
         tanh     tanh on the output."""
         kT, kH, kW = pk.k_eff
         sT, sH, sW = stride
+        if self.bf16:        # bf16 plans: every conv reads and writes bf16 activations (one rounding per output)
+            out_f16 = True
         xT, xH, xW = x.T, x.H * (2 if up2 else 1), x.W * (2 if up2 else 1)
         if same:        # TF-"SAME": out = ceil(in/stride), `padding` is ignored, front pad = total // 2
             (To, Ho, Wo), padding = _same_geometry((xT, xH, xW), (kT, kH, kW), stride)
@@ -825,11 +877,15 @@ class Plan:
         half = bool(getattr(x, "f16", False))
         if half != bool(getattr(pk, "f16", False)):
             raise PtxError("%s: activation and filter precisions differ" % label)
+        bf16 = bool(getattr(x, "bf16", False))
+        if bf16 != bool(getattr(pk, "bf16", False)):
+            raise PtxError("%s: activation and filter precisions differ" % label)
         if half:        # fp16 operands: the descriptor counts 32-bit words (channel pairs)
-            if x.C % 2 or x.ld % 8 or x2 is not None:
+            # bf16: an odd channel count reads its zero pad channel as the pair's second half (rows are 16-byte padded)
+            if (x.C % 2 and not bf16) or x.ld % 8 or x2 is not None:
                 raise PtxError("%s: fp16 operands need an even channel count and 16-byte rows" % label)
-            flags |= PTX_F16_OPERANDS
-            d.Ci, d.ldx = x.C // 2, x.ld // 2
+            flags |= PTX_F16_OPERANDS | (PTX_BF16_OPERANDS if bf16 else 0)
+            d.Ci, d.ldx = (x.C + 1) // 2, x.ld // 2
         if getattr(pk, "x3", False):
             flags |= PTX_F16X3_OPERANDS
         fused = bool(up2 or affine is not None or out_f16 or raw or tanh or (res is not None and getattr(res, "f16", False)))
@@ -851,7 +907,8 @@ class Plan:
                     raw_act = self.act(x.N, To, Ho, Wo, pk.Co, f16=True)
                     flags |= PTX_EPI_DUAL_RAW
                     ext.y_raw, ext.ld_raw = raw_act.t.data_ptr(), raw_act.ld
-        d.To, d.Ho, d.Wo, d.Co, d.ldy = To, Ho, Wo, pk.Co, y.ld
+        # (a bf16 output of odd width writes its zero pad channel with the pair: bias / filter rows there are zero)
+        d.To, d.Ho, d.Wo, d.Co, d.ldy = To, Ho, Wo, pk.Co + (pk.Co % 2 if bf16 else 0), y.ld
         d.kT, d.kH, d.kW, d.sT, d.sH, d.sW, d.pT, d.pH, d.pW = kT, kH, kW, sT, sH, sW, pT, pH, pW
         d.Kc, d.Co_pad = (pk.Kc // 2 if half else pk.Kc), pk.Co_pad
         d.groups = getattr(pk, "groups", 1)
@@ -899,7 +956,7 @@ class Plan:
             self.steps.append(ps)
             self.patch_steps = getattr(self, "patch_steps", 0) + 1
             return y
-        if fused and not tanh and x2 is None:
+        if fused and not tanh and x2 is None and not bf16:
             # generator stage: a GBlock's 3x3 convs (64 / 128 / 256 channels) and its closing 1x1 conv have their own fp16
             # kernels (gen_stage_f16.hip: no tile table, nothing to tune); PTX_CONV3X3_F16=0 / PTX_CONV1X1_F16=0: A/B runs
             if (res is None and not raw and os.environ.get("PTX_CONV3X3_F16", "1") != "0"
@@ -1110,6 +1167,8 @@ class Plan:
         the kernel does not cover the geometry (the folded implicit-GEMM path then runs)."""
         if os.environ.get("PTX_STEM_DIRECT", "1") == "0":
             return None
+        if self.bf16:
+            return self.stem_bf16(raw, conv, bn, relu, label)
         if raw.norm is not None and os.environ.get("PTX_STEM_DIRECT_U8", "1") == "0":
             return None                  # uint8 frames on the round-1 path: normalise + kW fold in one pass
         if not self.x3:
@@ -1169,6 +1228,32 @@ class Plan:
         st.macs = raw.N * To * Ho * Wo * conv.out_channels * raw.C * kT * kH * kW
         st.hbm_bytes = 0
         self.steps.append(st)
+        self.stem_steps = getattr(self, "stem_steps", 0) + 1
+        return y
+
+    def stem_bf16(self, raw, conv, bn, relu, label):
+        """bf16 RGB stem (conv1 of ResNet3D, resnet3D.py:153-155; the (1,7,7) spatial stem of R2Plus1D, r2plus1d.py:73-88):
+        ptx_im2col_hw_bf16 folds the (kh, kw) taps of the caller's bf16 NCDHW clip into 147 channels (rows padded to 160),
+        and the stem becomes a (kT, 1, 1) conv over them on the bf16 tiles -- 160 / 147 = 1.09x the algorithmic MACs
+        issued (plus tile padding), no torch layout pass."""
+        if raw.norm is not None or raw.t_step != 1 or not isinstance(conv, nn.Conv3d):
+            raise PtxError("%s: the bf16 stem reads a bf16 NCDHW clip (uint8 frames / frame sub-sampling are fp32 only)" % label)
+        (kT, kH, kW), (sT, sH, sW), (pT, pH, pW) = _geom(conv)
+        if getattr(conv, "tf_same", False):
+            raise PtxError("%s: SAME-padded stems are not supported in bf16" % label)
+        Ho, Wo = (raw.H + 2 * pH - kH) // sH + 1, (raw.W + 2 * pW - kW) // sW + 1
+        if min(Ho, Wo) < 1:
+            raise PtxError("%s: input too small for the stem" % label)
+        K = kH * kW * raw.C
+        xf = self.act(raw.N, raw.T, Ho, Wo, K, ld=(K + 31) // 32 * 32, f16=True)
+        lib, yp = self.lib, _ptr(xf.t)
+        N, Cc, T, H, W, ld = raw.N, raw.C, raw.T, raw.H, raw.W, xf.ld
+
+        def im2col(st, self=self):
+            check(lib.ptx_im2col_hw_bf16(self.in_ptr, yp, N, Cc, T, H, W, kH, kW, sH, sW, pH, pW, Ho, Wo, ld, st), "ptx_im2col_hw_bf16")
+        self.steps.append(_tag(im2col, "im2col_hw_bf16", 2 * N * Cc * T * H * W + 2 * xf.t.numel()))
+        y = self.conv(xf, self.pack(conv, bn, fold_hw=True), (sT, 1, 1), (pT, 0, 0), relu=relu, label=label)
+        self.stem_bf16_step = self.conv_steps[-1]
         self.stem_steps = getattr(self, "stem_steps", 0) + 1
         return y
 
@@ -1306,11 +1391,13 @@ class Plan:
             To = (x.T + 2 * p[0] - k[0]) // s[0] + 1
             Ho = (x.H + 2 * p[1] - k[1]) // s[1] + 1
             Wo = (x.W + 2 * p[2] - k[2]) // s[2] + 1
+        bf16 = bool(getattr(x, "bf16", False))
         if y is None:
-            y = self.act(x.N, To, Ho, Wo, x.C, x.ld)
+            y = self.act(x.N, To, Ho, Wo, x.C, x.ld, f16=bf16)
         assert (y.N, y.T, y.H, y.W, y.C) == (x.N, To, Ho, Wo, x.C), "pool output shape"
+        assert bool(getattr(y, "bf16", False)) == bf16, "pool output precision"
         d = PoolDesc(x.N, x.T, x.H, x.W, x.C, x.ld, To, Ho, Wo, k[0], k[1], k[2], s[0], s[1], s[2], p[0], p[1], p[2],
-                     y.ld, (PTX_POOL_SAME | PTX_POOL_PAD_ZERO) if same else 0)
+                     y.ld, ((PTX_POOL_SAME | PTX_POOL_PAD_ZERO) if same else 0) | (PTX_POOL_BF16 if bf16 else 0))
         lib, xp, yp = self.lib, _ptr(x.t), _ptr(y.t)
         self.keepalive.append(d)
 
@@ -1476,6 +1563,13 @@ class Plan:
     # ---------------------------------------------------------------- network
     def _build(self, model):
         kind = getattr(model, "plan_kind", "resnet")
+        if self.bf16:
+            name = str(getattr(model, "arch_name", None) or type(model).__name__)
+            arch = getattr(model, "arch", None)
+            if (kind != "resnet" or name.split("@")[0] not in BF16_FAMILIES or arch is None or arch.nonlocal_layers or arch.dims != 3
+                    or arch.block not in ("basic", "bottleneck")):
+                raise PtxError("bf16 inference covers the ResNet3D (resnet3d10..200) and R(2+1)D (r2plus1d10..50) families; "
+                               "%s (plan kind %r) has bf16 parameters: run it in float32" % (name, kind))
         if kind == "nlblock":                    # a standalone NonLocalBlock3D: [B,C,T,H,W] -> [B,C,T,H,W]
             N, Cc, T, H, W = self.shape
             self.feat = self.nonlocal_block(self.to_channels_last(RawInput(N, Cc, T, H, W)), model, "nl")
@@ -1510,7 +1604,8 @@ class Plan:
         s = blk.stride
         if arch.block.startswith("preact"):
             return self._block_preact(arch, blk, x, name)
-        fuse = (self.fuse_shortcut and blk.has_shortcut and arch.shortcut == "B" and arch.block in ("bottleneck", "resnext", "wide")
+        # (bf16 plans: shortcut B runs as its own conv + a fused residual add -- the dual-source GEMM is fp32 / x3 only)
+        fuse = (self.fuse_shortcut and not self.bf16 and blk.has_shortcut and arch.shortcut == "B" and arch.block in ("bottleneck", "resnext", "wide")
                 and isinstance(blk.conv3, (nn.Conv3d, nn.Conv2d)) and isinstance(blk.downsample[0], (nn.Conv3d, nn.Conv2d)))
         if fuse:
             # conv3 + bn3 and the shortcut conv + bn share the output tile: one GEMM over the
@@ -1694,6 +1789,10 @@ class Plan:
         if getattr(self, "head_error", None):
             raise PtxError(self.head_error)
         f = self.feat
+        if self.bf16:
+            check(self.lib.ptx_global_avgpool_bf16(_ptr(f.t), _ptr(self.pooled), f.N, f.C, f.S, f.ld, _stream()),
+                  "ptx_global_avgpool_bf16")
+            return engine._head_bf16(model, self.pooled, self)
         check(self.lib.ptx_global_avgpool(_ptr(f.t), _ptr(self.pooled), f.N, f.C, f.S, f.ld, 0, _stream()),
               "ptx_global_avgpool")
         out = engine._head(model, _ptr(self.pooled), f.N, f.C, self.dev)
@@ -1719,7 +1818,29 @@ class Plan:
             keep.append(p.refresh())
         for fn in self.refreshers:
             fn()
+        if self.bf16 and getattr(self, "head32", None) is not None:
+            self.head32_refresh(model)
         return keep
+
+    def head32_refresh(self, model):
+        """bf16 plans: the fp32 copy of the classifier (`last_linear` / `fc`) the fp32 ptx_linear_fwd reads, made when the
+        plan is packed and refreshed with it (in place: a captured graph keeps reading the same buffers)."""
+        head = model.head_module
+        if not isinstance(head, nn.Linear):
+            self.head32 = None
+            return None
+        key = (id(head), head.weight.data_ptr(), head.weight._version,
+               None if head.bias is None else (head.bias.data_ptr(), head.bias._version))
+        cur = getattr(self, "head32", None)
+        if cur is not None and cur[1].shape == head.weight.shape and (cur[2] is None) == (head.bias is None):
+            cur[1].copy_(head.weight.detach())
+            if head.bias is not None:
+                cur[2].copy_(head.bias.detach())
+            self.head32 = (key, cur[1], cur[2])
+        else:
+            self.head32 = (key, head.weight.detach().float().contiguous(),
+                           head.bias.detach().float().contiguous() if head.bias is not None else None)
+        return self.head32
 
     @contextlib.contextmanager
     def exclusive(self):
@@ -1840,6 +1961,8 @@ class Engine:
         #           (1e-5 class), 3 / 16 of its matrix-core time.  Activations, epilogues and every other kernel stay
         #           fp32.  Operand magnitudes must stay inside the half range (|v| < 65504).
         # Changing it drops the compiled plans (set it before the first forward, or call invalidate()).
+        # It governs float32 models only: a model whose parameters are bfloat16 runs the bf16 plans (bf16 operands on the
+        # bf16 matrix cores, fp32 accumulate, bf16 activations) whatever it is set to (INTEGRATION.md, bf16 inference).
         self._precision = os.environ.get("PTX_PRECISION", "fp32")
         # Opt-in autograd routing (eager.wanted): with grad mode on and trainable parameters, eval-mode calls run the
         # zoo's torch.nn children and return a differentiable output, as the reference does (frozen-BN fine-tuning).
@@ -1883,7 +2006,7 @@ class Engine:
         if n == "auto":
             n = 1
             if model is not None and shape is not None and not self.use_graph:
-                n = lanes_lookup(lanes_key(model, shape, self._precision)) or 1
+                n = lanes_lookup(lanes_key(model, shape, self.precision_of(model))) or 1
         return n if (n > 1 and not self.use_graph and batch >= n and batch % n == 0) else 1
 
     def tune_lanes(self, model, x, iters=8, verbose=False):
@@ -1891,7 +2014,7 @@ class Engine:
         the tuned table: two lanes must win by 1 % (the lanes double the activation buffers; config 2 gains 1.4-2.2 % across the
         boxes of rounds 5 and 6, which a 1.5 % bar turned into a coin flip).  Returns the lanes kept."""
         x = _dense16(x)
-        key = lanes_key(model, x.shape, self._precision)
+        key = lanes_key(model, x.shape, self.precision_of(model))
         if self.use_graph or x.shape[0] < 2 or x.shape[0] % 2:
             return 1
         keep = self._lanes
@@ -1923,6 +2046,11 @@ class Engine:
     @property
     def precision(self):
         return self._precision
+
+    def precision_of(self, model):
+        """The arithmetic a forward of `model` runs: "bf16" for a model whose parameters are bfloat16 (whatever
+        `precision` says), else `precision` ("fp32" / "x3")."""
+        return "bf16" if model is not None and model_precision(model) == "bf16" else self._precision
 
     @precision.setter
     def precision(self, value):
@@ -1972,12 +2100,15 @@ class Engine:
                            "there is no training-mode / autograd path")
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise PtxError("input must be a CUDA (ROCm) tensor -- there is no CPU fallback in this package")
-        if x.dtype != torch.float32:
+        p = _first_weight(model)
+        if p.dtype == torch.bfloat16:       # bf16 model: bf16 in, bf16 out (dtype mismatches raise, as in torch)
+            if x.dtype != torch.bfloat16:
+                raise PtxError("the model's parameters are bfloat16: the input must be bfloat16 too (got %s)" % x.dtype)
+        elif x.dtype != torch.float32:
             raise PtxError("input must be float32 (got %s)" % x.dtype)
         want = 4 if dims == 2 else 5
         if x.dim() != want:
             raise PtxError("expected a %d-D input, got shape %s" % (want, tuple(x.shape)))
-        p = _first_weight(model)
         if p.device != x.device:
             raise PtxError("input on %s but parameters on %s" % (x.device, p.device))
 
@@ -2006,17 +2137,19 @@ class Engine:
         return sig
 
     def _checksum(self, ts):
-        """Order-independent 64-bit sum of the fp32 bit patterns of every floating-point tensor, computed
-        on the device the tensors live on (ptx_checksum_f32); synchronises on the result."""
+        """Order-independent 64-bit sum of the bit patterns of every floating-point tensor -- fp32 (ptx_checksum_f32) and
+        16-bit (bf16 / fp16: ptx_checksum_b16) -- computed on the device the tensors live on; synchronises on the result."""
         fl = [t for t in ts if t.is_cuda and t.dtype == torch.float32 and t.numel() > 0]
-        if not fl:
+        hl = [t for t in ts if t.is_cuda and t.dtype in (torch.bfloat16, torch.float16) and t.numel() > 0]
+        if not fl and not hl:
             return 0
-        dev = fl[0].device
+        dev = (fl or hl)[0].device
         with torch.cuda.device(dev):
-            tab = torch.tensor([[t.data_ptr(), t.numel()] for t in fl], dtype=torch.int64).to(dev)
             out = torch.zeros(1, dtype=torch.int64, device=dev)
-            check(_lib.lib().ptx_checksum_f32(C.c_void_p(tab.data_ptr()), len(fl), C.c_void_p(out.data_ptr()), _stream()),
-                  "ptx_checksum_f32")
+            for lst, fn in ((fl, "ptx_checksum_f32"), (hl, "ptx_checksum_b16")):
+                if lst:
+                    tab = torch.tensor([[t.data_ptr(), t.numel()] for t in lst], dtype=torch.int64).to(dev)
+                    check(getattr(_lib.lib(), fn)(C.c_void_p(tab.data_ptr()), len(lst), C.c_void_p(out.data_ptr()), _stream()), fn)
             return int(out.item())
 
     def plan_for(self, model, x, shape=None, norm=None, lane=0):
@@ -2025,6 +2158,8 @@ class Engine:
         shape = tuple(x.shape) if shape is None else tuple(shape)
         nkey = None if norm is None else (tuple(norm.mean), tuple(norm.std), norm.swap_rb, norm.to_255)
         key = (shape, x.device.index, nkey) + ((lane,) if lane else ())
+        if model_precision(model) == "bf16":
+            key += ("bf16",)
         with self._lock:
             plan = self._plans.get(key)
             fresh = plan is None
@@ -2061,12 +2196,17 @@ class Engine:
             with plan.exclusive():
                 plan.bind(model)
                 f = plan.run_features(x)
+                dt = torch.bfloat16 if f.bf16 else torch.float32
                 if model.arch.dims == 2:
-                    out = torch.empty((f.N, f.C, f.H, f.W), device=x.device, dtype=torch.float32)
+                    out = torch.empty((f.N, f.C, f.H, f.W), device=x.device, dtype=dt)
                 else:
-                    out = torch.empty((f.N, f.C, f.T, f.H, f.W), device=x.device, dtype=torch.float32)
-                check(_lib.lib().ptx_ndhwc_to_ncdhw(_ptr(f.t), _ptr(out), f.N, f.C, f.S, f.ld, _stream()),
-                      "ptx_ndhwc_to_ncdhw")
+                    out = torch.empty((f.N, f.C, f.T, f.H, f.W), device=x.device, dtype=dt)
+                if f.bf16:
+                    check(_lib.lib().ptx_ndhwc_to_ncdhw_bf16(_ptr(f.t), _ptr(out), f.N, f.C, f.S, f.ld, _stream()),
+                          "ptx_ndhwc_to_ncdhw_bf16")
+                else:
+                    check(_lib.lib().ptx_ndhwc_to_ncdhw(_ptr(f.t), _ptr(out), f.N, f.C, f.S, f.ld, _stream()),
+                          "ptx_ndhwc_to_ncdhw")
         return out
 
     def _head(self, model, pooled_ptr, N, Cf, dev):
@@ -2082,10 +2222,49 @@ class Engine:
             return out
         return None
 
+    def _head_bf16(self, model, pooled, plan=None):
+        """bf16 models: the classifier runs as the fp32 ptx_linear_fwd on the fp32 pooled vector with an fp32 copy of
+        `last_linear` / `fc` (the plan's, refreshed with its filters); the logits are rounded to bf16 once.  A user-supplied
+        head module gets the pooled vector as bf16."""
+        N, Cf = pooled.shape
+        dev = pooled.device
+        head = model.head_module
+        if isinstance(head, nn.Linear) and head.weight.is_cuda and head.weight.dtype == torch.bfloat16:
+            holder = plan if plan is not None else self
+            cur = getattr(holder, "head32", None)
+            key = (id(head), head.weight.data_ptr(), head.weight._version,
+                   None if head.bias is None else (head.bias.data_ptr(), head.bias._version))
+            if cur is None or cur[0] != key:
+                cur = Plan.head32_refresh(holder, model)
+            w32, b32 = cur[1], cur[2]
+            out32 = torch.empty((N, head.out_features), device=dev, dtype=torch.float32)
+            check(_lib.lib().ptx_linear_fwd(_ptr(pooled), _ptr(w32), _ptr(b32) if b32 is not None else C.c_void_p(0),
+                                            _ptr(out32), N, Cf, head.out_features, Cf, head.out_features, 0, _stream()),
+                  "ptx_linear_fwd")
+            out = torch.empty((N, head.out_features), device=dev, dtype=torch.bfloat16)
+            check(_lib.lib().ptx_f32_to_bf16(_ptr(out32), _ptr(out), out32.numel(), _stream()), "ptx_f32_to_bf16")
+            return out
+        p16 = torch.empty((N, Cf), device=dev, dtype=torch.bfloat16)
+        check(_lib.lib().ptx_f32_to_bf16(_ptr(pooled), _ptr(p16), pooled.numel(), _stream()), "ptx_f32_to_bf16")
+        return head(p16)       # user-supplied head module (Identity, custom nn.Module): theirs to run
+
     def logits(self, model, feats):
         """NCDHW feature map -> [N, classes]: global average pool + `last_linear` read at call time
         (users replace it with another Linear or an Identity, reference README "last_linear")."""
         self._validate(model, feats, model.arch.dims)
+        if feats.dtype == torch.bfloat16:
+            # bf16: NCDHW -> channels-last (ptx_ncdhw_to_ndhwc_bf16), then the forward's own pool kernel, so
+            # logits(features(x)) has forward(x)'s bits
+            feats = _dense16(feats)
+            N, Cf = feats.shape[0], feats.shape[1]
+            S = feats.numel() // (N * Cf)
+            with torch.cuda.device(feats.device):
+                ld = (Cf + 7) // 8 * 8
+                cl = torch.empty((N, S, ld), device=feats.device, dtype=torch.bfloat16)
+                check(_lib.lib().ptx_ncdhw_to_ndhwc_bf16(_ptr(feats), _ptr(cl), N, Cf, S, ld, _stream()), "ptx_ncdhw_to_ndhwc_bf16")
+                pooled = torch.empty((N, Cf), device=feats.device, dtype=torch.float32)
+                check(_lib.lib().ptx_global_avgpool_bf16(_ptr(cl), _ptr(pooled), N, Cf, S, ld, _stream()), "ptx_global_avgpool_bf16")
+                return self._head_bf16(model, pooled)
         feats = feats.contiguous()
         N, Cf = feats.shape[0], feats.shape[1]
         S = feats.numel() // (N * Cf)
@@ -2321,6 +2500,8 @@ class Engine:
                            "pretrained models, torchvision_models.py:162-166): pass opts=pretrained_settings[...]")
         if model.training:
             raise PtxError("pretorched-x_amd is a forward-only (inference) engine: call model.eval() first")
+        if model_precision(model) != "fp32":
+            raise PtxError("forward_frames runs float32 models only (this model's parameters are %s)" % model_precision(model))
         dims = model.arch.dims
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
             raise PtxError("forward_frames: frames must be a uint8 CUDA tensor")
@@ -2364,7 +2545,7 @@ class Engine:
         # the engine's own full-batch plan and only when the knob is on "auto"
         if (self._lanes == "auto" and not own_plan and not self.use_graph and x.shape[0] >= 2 and x.shape[0] % 2 == 0
                 and os.environ.get("PTX_TUNE_LANES", "1") != "0"
-                and not (only_untuned and lanes_lookup(lanes_key(model, _dense16(x).shape, self._precision)) is not None)):
+                and not (only_untuned and lanes_lookup(lanes_key(model, _dense16(x).shape, self.precision_of(model))) is not None)):
             with torch.cuda.device(x.device):
                 half = _dense16(_dense16(x)[:x.shape[0] // 2])
                 hp = self.plan_for(model, half)
@@ -2385,7 +2566,7 @@ class Engine:
                 plan = self.plan_for(model, _dense16(x))
             plan.bind(model)
             plan.run_features(_dense16(x))      # make every buffer hold sane data
-            ncfg = lib.ptx_conv3d_num_configs()
+            ncfg = lib.ptx_conv3d_num_configs() + lib.ptx_conv3d_num_configs_bf16()
             seen, seen_body = {}, {}
             log = open(os.environ["PTX_TUNE_LOG"], "w") if os.environ.get("PTX_TUNE_LOG") else None
             for stp in plan.conv_steps:
@@ -2451,6 +2632,8 @@ class Engine:
                         continue
                     if bm >= 128 and M < 8192:
                         continue
+                    if stp is getattr(plan, "stem_bf16_step", None) and issued_conv_flop(stp.d, (bm, bn_, bk), 2) > 3.2 * stp.macs:
+                        continue                         # the bf16 stem issues at most 1.6x its algorithmic MACs
                     blocks = ((M + bm - 1) // bm) * ((ncol + bn_ - 1) // bn_)
                     splits = [1]
                     if blocks < 512:
