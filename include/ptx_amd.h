@@ -372,6 +372,8 @@ int ptx_im2col_hw_bf16(const void* x, void* y, int32_t N, int32_t C, int32_t T, 
                        int32_t sH, int32_t sW, int32_t pH, int32_t pW, int32_t Ho, int32_t Wo, int32_t ld, ptx_stream_t stream);
 /* y[i] = bf16(x[i]) for i < n (round to nearest even; NaN stays NaN): the single rounding of a bf16 plan's logits */
 int ptx_f32_to_bf16(const float* x, void* y, int64_t n, ptx_stream_t stream);
+/* y[i] = float(x[i]) for i < n (exact): the flattened bf16 features of MNISTNonLocalNet entering its fp32 classifier */
+int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t stream);
 /*
  * Small-Cin stem input: x NCDHW [N][C][T][H][W]  ->  y [N][T][H][Wo][ld] with
  *   y[n][t][h][wo][kw*C + c] = x[n][c][t][h][wo*sW - pW + kw]   (0 outside the image / k >= kW*C)
@@ -523,6 +525,9 @@ int ptx_linear_setsum_fwd(const float* x, const float* w, const float* b, float*
                           exact fp32 kernel.                                                                            */
 #define PTX_NL_OUT_F16 16 /* OR into PTX_NL_F16: y is written as halfs (ld_y / bs_y count halfs, ld_y a multiple of 4): the generator's
                              attention output feeds a half conv (ptx_conv1x1_skip_f16_fwd)                                    */
+#define PTX_NL_BF16 32 /* OR into PTX_NL_SOFTMAX / PTX_NL_SCALE (/ PTX_NL_RELU): a descriptor of ptx_nonlocal_bf16_fwd -- theta / phi / g / y
+                          are bf16 rows, ld_* / bs_* count bf16 elements (multiples of 8), pointers 16-byte aligned, d <= 1024.
+                          Exclusive with the other 16-bit bits; ptx_nonlocal_fwd refuses it.                               */
 typedef struct ptx_nonlocal_desc {
     int32_t batch, Nq, Nk, d, dv;
     int32_t ld_theta, ld_phi, ld_g, ld_y;        /* row strides (floats)   */
@@ -532,6 +537,13 @@ typedef struct ptx_nonlocal_desc {
 int ptx_nonlocal_supported(const ptx_nonlocal_desc* desc);
 int ptx_nonlocal_fwd(const ptx_nonlocal_desc* desc, const float* theta, const float* phi, const float* g, float* y,
                      ptx_stream_t stream);
+/* The same attention on bf16 operands (desc->mode carries PTX_NL_BF16): both matmuls on the bf16 matrix cores
+ * (v_mfma_f32_16x16x32_bf16 for theta . phi^T, v_mfma_f32_16x16x16_bf16 for P . g), accumulators, running max and running
+ * sum in fp32.  P is rounded to bf16 once (the A operand of P . g), y once (round to nearest even; NaN stays NaN).  The
+ * kernel contracts over d and dv rounded up to a multiple of 8: the caller guarantees those pad columns of theta / phi / g
+ * are zero.  It writes y's columns [0, round8(dv)), zeros above dv; columns [round8(dv), ld_y) are not touched. */
+int ptx_nonlocal_bf16_fwd(const ptx_nonlocal_desc* desc, const void* theta, const void* phi, const void* g, void* y,
+                          ptx_stream_t stream);
 /* Batched C[b] = op(A[b] x B[b]^T): A [batch][M][lda] (row-major, K contiguous),
  * B [batch][Nn][ldb] (row-major, K contiguous), C [batch][M][ldc]; fp32 MFMA.
  * Used for f = theta^T phi  (nonlocalnet.py:156) and y = softmax(f) g  (:160). */

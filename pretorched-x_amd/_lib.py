@@ -109,7 +109,7 @@ class NonlocalDesc(C.Structure):
                [(n, C.c_int64) for n in ("bs_theta", "bs_phi", "bs_g", "bs_y")] + [("mode", C.c_int32)]
 
 
-PTX_NL_SOFTMAX, PTX_NL_SCALE, PTX_NL_F16, PTX_NL_X3, PTX_NL_RELU, PTX_NL_OUT_F16 = 0, 1, 2, 4, 8, 16
+PTX_NL_SOFTMAX, PTX_NL_SCALE, PTX_NL_F16, PTX_NL_X3, PTX_NL_RELU, PTX_NL_OUT_F16, PTX_NL_BF16 = 0, 1, 2, 4, 8, 16, 32
 
 
 class RgbConvDesc(C.Structure):
@@ -178,6 +178,7 @@ SIGNATURES = {
     "ptx_ndhwc_to_ncdhw_bf16": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
     "ptx_im2col_hw_bf16": (C.c_int, [_P, _P] + [_I] * 14 + [_P]),
     "ptx_f32_to_bf16": (C.c_int, [_P, _P, _L, _P]),
+    "ptx_bf16_to_f32": (C.c_int, [_P, _P, _L, _P]),
     "ptx_global_avgpool_bf16": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
     "ptx_ncdhw_to_ndhwc": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
     "ptx_ndhwc_to_ncdhw": (C.c_int, [_P, _P, _I, _I, _L, _I, _P]),
@@ -198,6 +199,7 @@ SIGNATURES = {
     "ptx_linear_setsum_fwd": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U, _P]),
     "ptx_nonlocal_supported": (C.c_int, [C.POINTER(NonlocalDesc)]),
     "ptx_nonlocal_fwd": (C.c_int, [C.POINTER(NonlocalDesc), _P, _P, _P, _P, _P]),
+    "ptx_nonlocal_bf16_fwd": (C.c_int, [C.POINTER(NonlocalDesc), _P, _P, _P, _P, _P]),
     "ptx_nonlocal_workspace_bytes": (C.c_size_t, [C.POINTER(NonlocalDesc)]),
     "ptx_nonlocal_ws_fwd": (C.c_int, [C.POINTER(NonlocalDesc), _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "ptx_bgemm_nt": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _P]),

@@ -773,18 +773,336 @@ static int nl_sk_chunks(const ptx_nonlocal_desc* d) {
 }
 static size_t nl_sk_slot_floats(const ptx_nonlocal_desc* d) { return (size_t)64 * (d->dv <= 128 ? 128 : 256) + 128; }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// BF16 (PTX_NL_BF16, ptx_nonlocal_bf16_fwd): theta / phi / g / y are bf16 rows, both matmuls on the bf16 matrix cores,
+// accumulators and the online-softmax state in fp32.  The structure of the fp32 kernel: a wave owns 16 queries (theta in
+// registers, O in accumulators), the 4 waves of a workgroup share double-buffered key / value tiles, S is computed
+// TRANSPOSED (one query per lane column) and P stays in registers as the A operand of P . g.
+//   S^T += phi . theta^T   v_mfma_f32_16x16x32_bf16: A = 8 consecutive d of key row n (one ds_read_b128 from the LDS-DMA
+//                          tile), B = 8 consecutive d of this lane's query (registers); 32 d per instruction.
+//   O   += P . g           v_mfma_f32_16x16x16_bf16 (the "_1k" form): A = P[q = n][keys 4*gq .. 4*gq+3] -- exactly the 4
+//                          S^T values the lane holds, rounded to bf16 once -- and B = g[those 4 keys][channel n]: four
+//                          keys of ONE channel, so the value tile sits in LDS transposed ([channel][key], one ds_read_b64
+//                          per instruction).  It is staged through registers: 8-byte global loads of 4 channels x 4 keys
+//                          per item, a 4 x 4 transpose of 16-bit halves, ds_write_b64; the loads of tile t + 1 are in
+//                          flight while tile t computes.
+// Tiles of TK = 16 * KT keys (KT = 2: one barrier and one softmax update per 32 keys).  The epilogue scales by 1 / l,
+// rounds once to bf16 (v_cvt_pk_bf16_f32: NaN stays NaN), writes zeros above dv and stores whole 16-byte row pieces
+// through LDS: columns [0, round8(dv)) of y are written, nothing above.
+struct NlBf16Args {
+    const unsigned short* theta;
+    const unsigned short* phi;
+    const unsigned short* g;
+    unsigned short* y;
+    int batch, Nq, Nk, d, dv;
+    int ld_t, ld_p, ld_g, ld_y;
+    long long bs_t, bs_p, bs_g, bs_y;
+    int q_tiles, relu;
+    unsigned p_bytes, g_bytes, t_bytes;
+};
+
+typedef short short4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ f32x4 mfma_bf16_k32(bf16x8_t a, bf16x8_t b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma_bf16_k16(short4_t a, short4_t b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ short4_t to_bf16x4(float a, float b, float c, float d) {
+    const bf16x4_t v = {(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d};
+    return __builtin_bit_cast(short4_t, v);
+}
+__device__ __forceinline__ void dma16_b16(__amdgpu_buffer_rsrc_t rs, unsigned short* lds_base, unsigned voffset) {
+    typedef __attribute__((address_space(3))) void* lds_ptr_t;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)lds_base, 16, voffset, 0, 0, 0);
+}
+__device__ __forceinline__ unsigned half16(uint2 v, int j) {      // 16-bit element j (0..3) of an 8-byte piece
+    return ((j < 2 ? v.x : v.y) >> (16 * (j & 1))) & 0xffffu;
+}
+
+template <int D, int DV, int KT>
+constexpr size_t nl_bf16_lds_bytes() {
+    constexpr size_t tiles = ((size_t)2 * 16 * KT * D + (size_t)2 * DV * (16 * KT + 4)) * 2;
+    constexpr size_t ys = (size_t)64 * (DV + 8) * 2;
+    return tiles > ys ? tiles : ys;
+}
+
+// TG: theta fragments from global memory inside the d loop (D = 1024: 'gaussian' mode at C = 1024), as in the fp32 kernel
+template <int D, int DV, bool SOFTMAX, bool TG, int KT>
+__global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args p) {
+    constexpr int TK = 16 * KT;              // keys per tile
+    constexpr int QJ = D / 32;               // 32-wide d steps (one ds_read_b128 + one MFMA per 16 keys)
+    constexpr int CB = DV / 16;              // 16-channel output blocks (one ds_read_b64 + one MFMA per 16 keys)
+    constexpr int S8 = D / 8;                // 16-byte slots per key row
+    constexpr int NKP = TK * D / 512;        // 1-KiB DMA pieces of a key tile
+    constexpr int KPW = (NKP + 3) / 4;       // ... per wave
+    constexpr int RS = TK + 4;               // row stride (bf16) of the transposed value tile [DV][RS]
+    constexpr int GI = TK * DV / 16;         // staging items (4 keys x 4 channels) per value tile
+    constexpr int GPT = (GI + 255) / 256;    // ... per thread
+    constexpr int YS = DV + 8;               // row stride (bf16) of the epilogue's output staging [64][YS]
+    static_assert(D % 32 == 0 && DV % 16 == 0 && (TK * D) % 512 == 0 && S8 >= 4, "tile extents");
+    constexpr unsigned kOOB = 0x80000000u;
+    extern __shared__ __attribute__((aligned(16))) unsigned short smem_b16[];
+    unsigned short* Ks = smem_b16;                   // [2][TK][D]  (16-byte slots XOR-swizzled by row)
+    unsigned short* Vt = smem_b16 + 2 * TK * D;      // [2][DV][RS] (transposed: key-contiguous channel rows)
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n_tiles = (p.Nk + TK - 1) / TK;
+    const int tile = xcd_remap(blockIdx.x, p.q_tiles * p.batch);
+    const int b = tile / p.q_tiles, qt = tile - b * p.q_tiles;
+    const int c0 = blockIdx.y * DV;
+    const int n = lane & 15, gq = lane >> 4;
+    const int q = qt * 64 + wave * 16 + n;
+
+    const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned short*>(p.theta + (size_t)b * p.bs_t), 0, p.t_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned short*>(p.phi + (size_t)b * p.bs_p), 0, p.p_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned short*>(p.g + (size_t)b * p.bs_g), 0, p.g_bytes, 0x00020000);
+
+    // ---- theta[q][32 j + 8 gq .. + 7] (the B operand of S^T = phi . theta^T) ----
+    auto load_theta = [&](int j) -> bf16x8_t {
+        const int col = 32 * j + 8 * gq;
+        const unsigned off = ((unsigned)q * (unsigned)p.ld_t + (unsigned)col) * 2u;
+        return __builtin_bit_cast(bf16x8_t, __builtin_amdgcn_raw_buffer_load_b128(
+                                                rs_t, (q < p.Nq && col < p.d) ? off : kOOB, 0, 0));
+    };
+    bf16x8_t qf[TG ? 1 : QJ];
+    if constexpr (!TG) {
+#pragma unroll
+        for (int j = 0; j < QJ; ++j) qf[j] = load_theta(j);
+    }
+
+    auto swz = [&](int row, int slot) -> int {
+        return S8 >= 16 ? (slot ^ (row & 15)) : S8 == 8 ? (slot ^ ((row >> 1) & 7)) : (slot ^ ((row >> 2) & 3));
+    };
+    unsigned koff[KPW];
+#pragma unroll
+    for (int i = 0; i < KPW; ++i) {
+        const int f = (wave + 4 * i) * 512 + lane * 8;            // bf16 index in the linear [TK][D] image
+        const int row = f / D, slot = (f % D) / 8;
+        const int col = swz(row, slot) * 8;                       // logical column this physical slot holds
+        koff[i] = (wave + 4 * i < NKP && col < p.d) ? ((unsigned)row * (unsigned)p.ld_p + (unsigned)col) * 2u : kOOB;
+    }
+    auto issue_keys = [&](int t, int buf) {
+        const unsigned kbase = (unsigned)t * TK * (unsigned)p.ld_p * 2u;
+#pragma unroll
+        for (int i = 0; i < KPW; ++i)
+            if (wave + 4 * i < NKP)
+                dma16_b16(rs_p, Ks + buf * TK * D + (wave + 4 * i) * 512, koff[i] == kOOB ? kOOB : koff[i] + kbase);
+    };
+    // value staging item it: keys 4 * (it % (TK / 4)) + 0..3, channels c0 + 4 * (it / (TK / 4)) + 0..3
+    unsigned goff[GPT];
+#pragma unroll
+    for (int i = 0; i < GPT; ++i) {
+        const int it = tid + 256 * i, kg = it % (TK / 4), cg = it / (TK / 4);
+        const int ch = c0 + 4 * cg;
+        goff[i] = (it < GI && ch < p.dv) ? ((unsigned)(4 * kg) * (unsigned)p.ld_g + (unsigned)ch) * 2u : kOOB;
+    }
+    uint2 gr[GPT][4];
+    auto load_values = [&](int t) {
+        const unsigned vbase = (unsigned)t * TK * (unsigned)p.ld_g * 2u;
+#pragma unroll
+        for (int i = 0; i < GPT; ++i)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                gr[i][k] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(
+                                                         rs_g, goff[i] == kOOB ? kOOB : goff[i] + vbase + (unsigned)k * (unsigned)p.ld_g * 2u, 0, 0));
+    };
+    auto store_values = [&](int buf) {
+        unsigned short* V = Vt + buf * DV * RS;
+#pragma unroll
+        for (int i = 0; i < GPT; ++i) {
+            const int it = tid + 256 * i, kg = it % (TK / 4), cg = it / (TK / 4);
+            if (GI % 256 == 0 || it < GI) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint2 w = {half16(gr[i][0], j) | (half16(gr[i][1], j) << 16), half16(gr[i][2], j) | (half16(gr[i][3], j) << 16)};
+                    *reinterpret_cast<uint2*>(V + (4 * cg + j) * RS + 4 * kg) = w;
+                }
+            }
+        }
+    };
+
+    f32x4 O[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) O[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+    const float inv_nk = 1.0f / (float)p.Nk;
+
+    issue_keys(0, 0);
+    load_values(0);
+    store_values(0);
+    // fragment read offsets (bf16): key row n of each 16-key sub-tile; value row = channel n, keys 4 * gq .. + 3
+    const int k_row_off = n * D;                                  // (16 * kt is a multiple of every swizzle period)
+    const int v_row_off = n * RS + 4 * gq;
+    for (int t = 0; t < n_tiles; ++t) {
+        const int buf = t & 1;
+        int ko = k_row_off, vo = v_row_off;
+        tile_barrier(ko, vo);                 // keys of tile t landed, its values are in LDS; buffers buf ^ 1 are free
+        if (t + 1 < n_tiles) {
+            issue_keys(t + 1, buf ^ 1);
+            load_values(t + 1);
+        }
+        const unsigned short* Kb = Ks + buf * TK * D + ko;
+        const unsigned short* Vb = Vt + buf * DV * RS + vo;
+
+        // ---- S^T sub-tiles (KT independent accumulation chains) ----
+        f32x4 s[KT];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < QJ; ++j) {
+            const bf16x8_t qv = TG ? load_theta(j) : qf[TG ? 0 : j];
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) {
+                const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(Kb + kt * 16 * D + swz(n, 4 * j + gq) * 8);
+                s[kt] = mfma_bf16_k32(kf, qv, s[kt]);
+            }
+        }
+        // s[kt][r] = S[q = n][key = t * TK + 16 kt + 4 gq + r]
+        float pr[KT][4];
+        if constexpr (SOFTMAX) {
+            const int key0 = t * TK + 4 * gq;
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    s[kt][r] = (key0 + 16 * kt + r < p.Nk) ? s[kt][r] : -INFINITY;
+                    mx = fmaxf(mx, s[kt][r]);
+                }
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmaxf(m_run, mx);
+            const bool moved = m_new > m_run;
+            const float m_ref = (m_new == -INFINITY) ? 0.f : m_new;
+            const float alpha = __expf(m_run - m_ref);
+            float ls = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pr[kt][r] = __expf(s[kt][r] - m_ref);
+                ls += (pr[kt][0] + pr[kt][1]) + (pr[kt][2] + pr[kt][3]);
+            }
+            l_run = l_run * alpha + ls;
+            m_run = m_new;
+            if (__any(moved)) {               // O rows are queries 4*gq + r: fetch their alpha from lane (4*gq + r)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float a = __shfl(alpha, 4 * gq + r, 64);
+#pragma unroll
+                    for (int cb = 0; cb < CB; ++cb) O[cb][r] *= a;
+                }
+            }
+        } else {
+            // keys >= Nk read as zero rows: S = 0 there, and their value rows are zero too
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pr[kt][r] = (p.relu ? fmaxf(s[kt][r], 0.f) : s[kt][r]) * inv_nk;
+        }
+
+        // ---- O += P . g_tile: P rounded to bf16 once ----
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+            const short4_t pa = to_bf16x4(pr[kt][0], pr[kt][1], pr[kt][2], pr[kt][3]);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+                const short4_t vb = *reinterpret_cast<const short4_t*>(Vb + cb * 16 * RS + kt * 16);
+                O[cb] = mfma_bf16_k16(pa, vb, O[cb]);
+            }
+        }
+        if (t + 1 < n_tiles) store_values(buf ^ 1);
+    }
+
+    // ---- epilogue: 1 / l per query, one rounding to bf16, zeros above dv; rows leave as 16-byte pieces via LDS ----
+    float inv = 1.f;
+    if constexpr (SOFTMAX) {
+        l_run += __shfl_xor(l_run, 16, 64);
+        l_run += __shfl_xor(l_run, 32, 64);
+        inv = 1.0f / l_run;
+    }
+    __syncthreads();                                  // every wave is done with the tile buffers (Ys aliases them)
+    unsigned short* Ys = smem_b16;                    // [64][YS]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float iv = SOFTMAX ? __shfl(inv, 4 * gq + r, 64) : 1.f;
+        const int row = wave * 16 + 4 * gq + r;
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            const float v = (c0 + cb * 16 + n < p.dv) ? O[cb][r] * iv : 0.f;
+            Ys[row * YS + cb * 16 + n] = __builtin_bit_cast(unsigned short, (__bf16)v);
+        }
+    }
+    __syncthreads();
+    const int lim = min(DV, ((p.dv + 7) & ~7) - c0);  // columns [c0, c0 + lim) of y are this workgroup's
+    unsigned short* yb = p.y + (size_t)b * p.bs_y;
+#pragma unroll
+    for (int e = tid; e < 64 * (DV / 8); e += 256) {
+        const int row = e / (DV / 8), ch = (e % (DV / 8)) * 8;
+        const int qo = qt * 64 + row;
+        if (qo < p.Nq && ch < lim)
+            *reinterpret_cast<uint4*>(yb + (size_t)qo * p.ld_y + c0 + ch) = *reinterpret_cast<const uint4*>(Ys + row * YS + ch);
+    }
+}
+
+template <int D, int DV, bool SOFTMAX, bool TG, int KT>
+static int launch_nl_bf16_mode(const NlBf16Args& a, hipStream_t st) {
+    constexpr size_t lds = nl_bf16_lds_bytes<D, DV, KT>();
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    auto kern = nl_attention_bf16_kernel<D, DV, SOFTMAX, TG, KT>;
+    static bool attr_set[64] = {};   // per device; benign race (idempotent call)
+    int dev = 0;
+    PTX_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        PTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a.q_tiles * a.batch), (unsigned)cdiv(a.dv, DV)), dim3(256), lds, st, a);
+    return hip_check(hipGetLastError(), "nonlocal attention (bf16) launch");
+}
+template <int D, int DV, bool TG = false, int KT = 2>
+static int launch_nl_bf16(const NlBf16Args& a, bool scale_only, hipStream_t st) {
+    return scale_only ? launch_nl_bf16_mode<D, DV, false, TG, KT>(a, st) : launch_nl_bf16_mode<D, DV, true, TG, KT>(a, st);
+}
+template <int D>
+static int launch_nl_bf16_dv(const NlBf16Args& a, bool scale_only, hipStream_t st) {
+    if (a.dv <= 64) return launch_nl_bf16<D, 64>(a, scale_only, st);
+    if (a.dv <= 128) return launch_nl_bf16<D, 128>(a, scale_only, st);
+    return launch_nl_bf16<D, 256>(a, scale_only, st);            // dv > 256: chunks of 256 over blockIdx.y
+}
+
 }  // namespace ptx
 
 using namespace ptx;
 
 extern "C" size_t ptx_nonlocal_workspace_bytes(const ptx_nonlocal_desc* d) {
-    if (!d || !ptx_nonlocal_supported(d)) return 0;
+    if (!d || !ptx_nonlocal_supported(d) || (d->mode & PTX_NL_BF16)) return 0;
     const int chunks = nl_sk_chunks(d);
     return chunks ? (size_t)d->batch * chunks * 2 * nl_sk_slot_floats(d) * sizeof(float) : 0;
 }
 
+// bf16 descriptors: d <= 1024, any dv; row / batch strides multiples of 8 bf16 covering the extents; softmax, scale or
+// scale + relu only
+static int nl_bf16_supported(const ptx_nonlocal_desc* d) {
+    if (d->mode & ~(PTX_NL_BF16 | PTX_NL_SCALE | PTX_NL_RELU) || ((d->mode & PTX_NL_RELU) && !(d->mode & PTX_NL_SCALE))) return 0;
+    if (d->ld_theta % 8 || d->ld_phi % 8 || d->ld_g % 8 || d->ld_y % 8 || d->bs_theta % 8 || d->bs_phi % 8 || d->bs_g % 8 ||
+        d->bs_y % 8)
+        return 0;
+    if (d->ld_theta < d->d || d->ld_phi < d->d || d->ld_g < d->dv || d->ld_y < d->dv) return 0;
+    return d->batch > 0 && d->Nq > 0 && d->Nk > 0 && d->d > 0 && d->dv > 0 && d->d <= 1024 &&
+           d->batch * (int64_t)((d->Nq + 63) / 64) <= 0x7fffffffLL;
+}
+
 extern "C" int ptx_nonlocal_supported(const ptx_nonlocal_desc* d) {
     if (!d) return 0;
+    if (d->mode & PTX_NL_BF16) return nl_bf16_supported(d);
     return d->batch > 0 && d->Nq > 0 && d->Nk > 0 && d->d > 0 && d->dv > 0 && d->d % 4 == 0 && d->dv % 4 == 0 && d->d <= 1024 &&
            d->batch * (int64_t)((d->Nq + 63) / 64) <= 0x7fffffffLL;
 }
@@ -797,6 +1115,8 @@ extern "C" int ptx_nonlocal_fwd(const ptx_nonlocal_desc* d, const float* theta, 
 extern "C" int ptx_nonlocal_ws_fwd(const ptx_nonlocal_desc* d, const float* theta, const float* phi, const float* g, float* y,
                                    void* workspace, size_t workspace_bytes, ptx_stream_t stream) {
     if (!d || !theta || !phi || !g || !y) return fail(PTX_ERR_INVALID, "nonlocal: null pointer");
+    if (d->mode & PTX_NL_BF16)
+        return fail(PTX_ERR_INVALID, "nonlocal: a PTX_NL_BF16 descriptor (bf16 operands) goes to ptx_nonlocal_bf16_fwd");
     if (!ptx_nonlocal_supported(d))
         return fail(PTX_ERR_UNSUPPORTED, "nonlocal: need d, dv multiples of 4 and d <= 1024 (d=%d dv=%d); use the "
                     "ptx_bgemm_nt / ptx_softmax_rows path", d->d, d->dv);
@@ -872,4 +1192,39 @@ extern "C" int ptx_nonlocal_ws_fwd(const ptx_nonlocal_desc* d, const float* thet
     if (d->d <= 64) return d->dv <= 64 ? launch_nl<64, 64>(a, st) : launch_nl<64, 256>(a, st);
     if (d->d <= 256) return d->dv <= 128 ? launch_nl<256, 128>(a, st) : launch_nl<256, 256>(a, st);
     return launch_nl<512, 256>(a, st);
+}
+
+extern "C" int ptx_nonlocal_bf16_fwd(const ptx_nonlocal_desc* d, const void* theta, const void* phi, const void* g, void* y,
+                                     ptx_stream_t stream) {
+    if (!d || !theta || !phi || !g || !y) return fail(PTX_ERR_INVALID, "nonlocal_bf16: null pointer");
+    if (!(d->mode & PTX_NL_BF16))
+        return fail(PTX_ERR_INVALID, "nonlocal_bf16: the descriptor lacks PTX_NL_BF16 (fp32 operands go to ptx_nonlocal_fwd)");
+    if (!ptx_nonlocal_supported(d))
+        return fail(PTX_ERR_UNSUPPORTED, "nonlocal_bf16: need mode PTX_NL_SOFTMAX, PTX_NL_SCALE or PTX_NL_SCALE | PTX_NL_RELU, "
+                    "d <= 1024 (d=%d dv=%d), row / batch strides multiples of 8 bf16 covering d / dv", d->d, d->dv);
+    if (((uintptr_t)theta | (uintptr_t)phi | (uintptr_t)g | (uintptr_t)y) & 15)
+        return fail(PTX_ERR_INVALID, "nonlocal_bf16: pointers must be 16-byte aligned");
+    const uint64_t tb = (uint64_t)d->Nq * d->ld_theta * 2ull, pb = (uint64_t)d->Nk * d->ld_phi * 2ull, gb = (uint64_t)d->Nk * d->ld_g * 2ull;
+    if (tb >= 0x80000000ull || pb >= 0x80000000ull || gb >= 0x80000000ull)
+        return fail(PTX_ERR_UNSUPPORTED, "nonlocal_bf16: one batch item of theta / phi / g must be < 2 GiB");
+    NlBf16Args a{};
+    a.theta = static_cast<const unsigned short*>(theta);
+    a.phi = static_cast<const unsigned short*>(phi);
+    a.g = static_cast<const unsigned short*>(g);
+    a.y = static_cast<unsigned short*>(y);
+    a.batch = d->batch; a.Nq = d->Nq; a.Nk = d->Nk; a.d = d->d; a.dv = d->dv;
+    a.ld_t = d->ld_theta; a.ld_p = d->ld_phi; a.ld_g = d->ld_g; a.ld_y = d->ld_y;
+    a.bs_t = d->bs_theta; a.bs_p = d->bs_phi; a.bs_g = d->bs_g; a.bs_y = d->bs_y;
+    a.q_tiles = cdiv(d->Nq, 64);
+    a.relu = (d->mode & PTX_NL_RELU) != 0;
+    a.t_bytes = (unsigned)tb; a.p_bytes = (unsigned)pb; a.g_bytes = (unsigned)gb;
+    const bool scale_only = (d->mode & PTX_NL_SCALE) != 0;
+    hipStream_t st = (hipStream_t)stream;
+    // the smallest compiled D covering d, from PER-SAMPLE extents only (a clip's bits do not depend on its batch)
+    if (d->d > 512) return launch_nl_bf16<1024, 256, true, 1>(a, scale_only, st);     // theta from global, 16-key tiles
+    if (d->d <= 32) return launch_nl_bf16_dv<32>(a, scale_only, st);
+    if (d->d <= 64) return launch_nl_bf16_dv<64>(a, scale_only, st);
+    if (d->d <= 128) return launch_nl_bf16_dv<128>(a, scale_only, st);
+    if (d->d <= 256) return launch_nl_bf16_dv<256>(a, scale_only, st);
+    return launch_nl_bf16_dv<512>(a, scale_only, st);
 }

@@ -405,6 +405,11 @@ __global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restric
         y[i] = (__bf16)x[i];      // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
 }
 
+__global__ void __launch_bounds__(256) bf16_to_f32_kernel(const __bf16* __restrict__ x, float* __restrict__ y, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        y[i] = (float)x[i];       // exact
+}
+
 }  // namespace ptx
 
 using namespace ptx;
@@ -710,4 +715,12 @@ extern "C" int ptx_f32_to_bf16(const float* x, void* y, int64_t n, ptx_stream_t 
     hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, (hipStream_t)stream, x,
                        static_cast<__bf16*>(y), (long long)n);
     return hip_check(hipGetLastError(), "f32_to_bf16 launch");
+}
+
+extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t stream) {
+    if (!x || !y || n <= 0) return fail(PTX_ERR_INVALID, "bf16_to_f32: null pointer / empty");
+    if (((uintptr_t)x & 1) || ((uintptr_t)y & 3)) return fail(PTX_ERR_INVALID, "bf16_to_f32: misaligned pointer");
+    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const __bf16*>(x), y, (long long)n);
+    return hip_check(hipGetLastError(), "bf16_to_f32 launch");
 }

@@ -131,6 +131,9 @@ def _flags_kind(flags):
 # bf16 kernels.  Everything else raises at plan build time.
 BF16_FAMILIES = ("resnet3d10", "resnet3d18", "resnet3d34", "resnet3d50", "resnet3d101", "resnet3d152", "resnet3d200",
                  "r2plus1d10", "r2plus1d18", "r2plus1d34", "r2plus1d50")
+# ... and the plan kinds built from non-local blocks alone: NonLocalBlock1D / 2D / 3D and MNISTNonLocalNet (the networks that
+# embed blocks in a ResNet, nonlocalresnet3d50 / nonlocal_r2plus1d50, keep raising)
+BF16_NL_KINDS = ("nlblock", "mnist_nl")
 
 
 def model_precision(model):
@@ -252,9 +255,10 @@ class Act:
         """Channels [c0, c0 + C_) of this activation as an output target: same row stride, so a conv /
         pool writing it fills its part of a channel concatenation (torch.cat(dim=1)) in place."""
         assert c0 % 4 == 0 and c0 + C_ <= self.ld
-        assert not self.f16, "channel slices are fp32 only"
+        # bf16 slices start on an 8-channel (16-byte) boundary; fp16 activations are never sliced
+        assert not self.f16 or (self.bf16 and c0 % 8 == 0), "channel slices are fp32 / 16-byte aligned bf16 only"
         v = Act.__new__(Act)
-        v.f16 = v.bf16 = False
+        v.f16 = v.bf16 = self.bf16
         v.N, v.T, v.H, v.W, v.C, v.ld = self.N, self.T, self.H, self.W, C_, self.ld
         v.t = self.t[..., c0:c0 + C_]
         return v
@@ -286,8 +290,11 @@ class _Ref:
 class Packed:
     """BN-folded, K-major filter + bias living on one device; refreshable in place."""
 
-    def __init__(self, plan, convs, bn, fold_kw=False, scale=None, f16=False, x3=None, stem4=False, fold_hw=False):
+    def __init__(self, plan, convs, bn, fold_kw=False, scale=None, f16=False, x3=None, stem4=False, fold_hw=False, pad8=False):
         dev = plan.dev
+        # pad8: each of several Co-concatenated filters starts on an 8-row boundary, zero filter rows / bias in between
+        # (the bf16 non-local theta|phi|g projection: every slice of its output is 16-byte aligned, its pad channels zero)
+        self.pad8 = bool(pad8)
         self.stem4 = bool(stem4)     # direct split-operand stem (ptx_conv_stem_x3_fwd): Cin zero-padded to 4, kW folded
         self.plan = plan
         # bf16 plans: every filter is stored as bf16 (ptx_pack_desc.f16 == 3) for a bf16-operand conv
@@ -303,7 +310,7 @@ class Packed:
         self.scale = (plan.ref(scale[0]), scale[1]) if scale is not None else None
         c0 = convs[0]
         (kT, kH, kW), _, _ = _geom(c0)
-        self.Co = sum(c.out_channels for c in convs)
+        self.Co = sum(_r8(c.out_channels) if self.pad8 else c.out_channels for c in convs)
         self.groups = int(getattr(c0, "groups", 1))
         if self.groups > 1 and (len(convs) > 1 or fold_kw):
             raise PtxError("grouped convolutions are packed one at a time, unfolded")
@@ -355,6 +362,11 @@ class Packed:
         elif len(convs) == 1:
             w = convs[0].weight.detach()
             cb = convs[0].bias.detach() if convs[0].bias is not None else None
+        elif self.pad8:
+            def rows8(t):
+                return torch.cat([t, t.new_zeros((_r8(t.shape[0]) - t.shape[0],) + tuple(t.shape[1:]))], 0)
+            w = torch.cat([rows8(c.weight.detach()) for c in convs], 0)
+            cb = torch.cat([rows8(c.bias.detach()) for c in convs], 0) if convs[0].bias is not None else None
         else:
             w = torch.cat([c.weight.detach() for c in convs], 0)
             cb = torch.cat([c.bias.detach() for c in convs], 0) if convs[0].bias is not None else None
@@ -393,6 +405,39 @@ class Packed:
                                               args[0], args[1], args[2], args[3], C.c_float(eps),
                                               _ptr(self.w), _ptr(self.b), _stream()), "ptx_pack_conv_weight")
         return keep
+
+
+class _ConcatRowsPack(Packed):
+    """bf16 'concatenation' mode: the filter of one 1x1x1 conv producing the affinity rows (a_i, 1, 0, ..) ("a", from
+    theta: row 0 = concat_project's theta half, bias (proj bias, 1, 0, ..)) or (1, b_j, 0, ..) ("b", from phi: row 1 = its
+    phi half, bias (1, 0, ..)), Co = 8 with explicit zero rows; rebuilt from concat_project on every refresh, as the fp32
+    path rebuilds its GEMV weights."""
+
+    def __init__(self, plan, nl, ci, side):
+        shape = nn.Conv3d(ci, 8, 1, bias=True, device="meta")       # geometry only: the rows come from concat_project
+        super().__init__(plan, [shape], None)
+        self.proj, self.side, self.ci = plan.ref(nl.concat_project[0]), side, ci
+
+    def refresh(self):
+        proj = self.plan.get(self.proj)
+        w = proj.weight.detach().reshape(-1)                         # [2 ci]: theta half | phi half
+        if w.dtype != torch.bfloat16 or not w.is_cuda:
+            raise PtxError("weights of a bf16 model must be bf16 CUDA tensors on the plan's device (got %s)" % w.dtype)
+        ci = self.ci
+        wf = torch.zeros((8, ci, 1, 1, 1), device=w.device, dtype=torch.float32)
+        bf = torch.zeros(8, device=w.device, dtype=torch.float32)
+        if self.side == "a":
+            wf[0].view(-1).copy_(w[:ci])
+            bf[1] = 1.0
+            if proj.bias is not None:
+                bf[0:1].copy_(proj.bias.detach().reshape(1))
+        else:
+            wf[1].view(-1).copy_(w[ci:])
+            bf[0] = 1.0
+        null = C.c_void_p(0)
+        check(_lib.lib().ptx_pack_conv_weight(C.byref(self.d), _ptr(wf), _ptr(bf), null, null, null, null, C.c_float(0.0),
+                                              _ptr(self.w), _ptr(self.b), _stream()), "ptx_pack_conv_weight (concat rows)")
+        return [wf, bf]
 
 
 class PackedDual:
@@ -811,15 +856,16 @@ class Plan:
         self._cur = model
 
     # ---------------------------------------------------------------- building blocks
-    def pack(self, convs, bn, fold_kw=False, scale=None, f16=False, x3=None, stem4=False, fold_hw=False):
+    def pack(self, convs, bn, fold_kw=False, scale=None, f16=False, x3=None, stem4=False, fold_hw=False, pad8=False):
         """scale: (module, attribute name) of a scalar Parameter multiplying the filter.
-        x3: force (True) / forbid (False) split operands for this filter; None = the plan's precision."""
+        x3: force (True) / forbid (False) split operands for this filter; None = the plan's precision.
+        pad8: Co-concatenated filters each start on an 8-row boundary (zero rows in between)."""
         if not isinstance(convs, (list, tuple)):
             convs = [convs]
         key = (tuple(id(c) for c in convs), id(bn), fold_kw, None if scale is None else (id(scale[0]), scale[1]), bool(f16), x3,
-               bool(stem4), bool(fold_hw))
+               bool(stem4), bool(fold_hw)) + (("pad8",) if pad8 else ())
         if key not in self._pack_cache:
-            p = Packed(self, convs, bn, fold_kw, scale, f16, x3, stem4, fold_hw)
+            p = Packed(self, convs, bn, fold_kw, scale, f16, x3, stem4, fold_hw, pad8)
             self._pack_cache[key] = p
             self.packs.append(p)
         return self._pack_cache[key]
@@ -1372,6 +1418,15 @@ class Plan:
         return y
 
     def to_channels_last(self, raw):
+        if self.bf16:        # bf16 plans: the caller's bf16 NCDHW input, channels [C, ld) zero-filled
+            y = self.act(raw.N, raw.T, raw.H, raw.W, raw.C, f16=True)
+            lib, yp = self.lib, _ptr(y.t)
+            N, C_, S, ld = raw.N, raw.C, raw.T * raw.H * raw.W, y.ld
+
+            def step(st, self=self):
+                check(lib.ptx_ncdhw_to_ndhwc_bf16(self.in_ptr, yp, N, C_, S, ld, st), "ptx_ncdhw_to_ndhwc_bf16")
+            self.steps.append(_tag(step, "ncdhw_to_ndhwc_bf16", 2 * N * C_ * S + 2 * y.t.numel()))
+            return y
         y = self.act(raw.N, raw.T, raw.H, raw.W, raw.C)
         lib, yp = self.lib, _ptr(y.t)
         N, C_, S, ld = raw.N, raw.C, raw.T * raw.H * raw.W, y.ld
@@ -1413,6 +1468,8 @@ class Plan:
         (possibly channel slices).  Returns False -- nothing emitted -- when the fused kernel does not cover the shape
         (d > 1024) or PTX_NL_FUSED=0 asks for the unfused bgemm / softmax / bgemm chain."""
         from ._lib import NonlocalDesc, PTX_NL_F16, PTX_NL_RELU, PTX_NL_SCALE, PTX_NL_SOFTMAX, PTX_NL_X3
+        if self.bf16:
+            return self.attention_bf16(th, ph, g, y, scale_only, relu)
         d = NonlocalDesc()
         d.batch, d.Nq, d.Nk, d.d, d.dv = th.N, th.S, ph.S, th.C, g.C
         d.ld_theta, d.ld_phi, d.ld_g, d.ld_y = th.ld, ph.ld, g.ld, y.ld
@@ -1446,6 +1503,46 @@ class Plan:
         self.attn_steps = getattr(self, "attn_steps", 0) + 1
         return True
 
+    def attention_bf16(self, th, ph, g, y, scale_only=False, relu=False):
+        """bf16 plans: the same attention as one ptx_nonlocal_bf16_fwd launch (bf16 operands on the bf16 matrix cores, fp32
+        accumulate and softmax state; P and y rounded to bf16 once).  Every operand is a bf16 activation whose pad channels
+        up to round8(C) are zero (the kernel contracts over them); y's columns [0, round8(dv)) are written."""
+        from ._lib import NonlocalDesc, PTX_NL_BF16, PTX_NL_RELU, PTX_NL_SCALE, PTX_NL_SOFTMAX
+        if not all(getattr(a, "bf16", False) for a in (th, ph, g, y)):
+            raise PtxError("attention: a bf16 plan's operands are bf16 activations")
+        if relu and not scale_only:
+            raise PtxError("attention: relu modifies the scale-only affinity")
+        d = NonlocalDesc()
+        d.batch, d.Nq, d.Nk, d.d, d.dv = th.N, th.S, ph.S, th.C, g.C
+        d.ld_theta, d.ld_phi, d.ld_g, d.ld_y = th.ld, ph.ld, g.ld, y.ld
+        d.bs_theta, d.bs_phi, d.bs_g, d.bs_y = th.S * th.ld, ph.S * ph.ld, g.S * g.ld, y.S * y.ld
+        d.mode = PTX_NL_BF16 | (PTX_NL_SCALE if scale_only else PTX_NL_SOFTMAX) | (PTX_NL_RELU if relu else 0)
+        if not self.lib.ptx_nonlocal_supported(C.byref(d)):
+            raise PtxError("attention: the bf16 kernel does not cover d=%d (d <= 1024)" % th.C)
+        lib, tp, pp, gp, yp = self.lib, _ptr(th.t), _ptr(ph.t), _ptr(g.t), _ptr(y.t)
+        self.keepalive.append(d)
+
+        def step(st):
+            check(lib.ptx_nonlocal_bf16_fwd(C.byref(d), tp, pp, gp, yp, st), "ptx_nonlocal_bf16_fwd")
+        self.steps.append(_tag(step, "nonlocal_attention", 2 * th.N * (th.S * th.C + ph.S * ph.C + g.S * g.C + th.S * g.C),
+                               macs=th.N * th.S * ph.S * (th.C + g.C)))
+        self.attn_steps = getattr(self, "attn_steps", 0) + 1
+        self.attn_descs = getattr(self, "attn_descs", []) + [d]
+        self.attn_operands = getattr(self, "attn_operands", []) + [(th, ph, g, y)]
+        return True
+
+    def concat_rows_bf16(self, th, ph, nl, label):
+        """bf16 'concatenation' affinity rows: (a_i, 1, 0, ..) and (1, b_j, 0, ..) as one bf16 1x1x1 conv each (Co = 8,
+        zero rows 2..7), so relu(a_i + b_j) / Nk is the PTX_NL_SCALE | PTX_NL_RELU mode of the bf16 attention at d = 8.
+        a_i and b_j are rounded to bf16 by the conv epilogue (the 1s are exact)."""
+        pa = _ConcatRowsPack(self, nl, th.C, "a")
+        pb = _ConcatRowsPack(self, nl, th.C, "b")
+        self.packs += [pa, pb]
+        one, zero = (1, 1, 1), (0, 0, 0)
+        ta = self.conv(th, pa, one, zero, label=label + ".concat_a")
+        tb = self.conv(ph, pb, one, zero, label=label + ".concat_b")
+        return ta, tb
+
     def concat_attention(self, th, ph, g, y, nl, label):
         """The 'concatenation' affinity (nonlocalnet.py:213-243) on the fused attention kernel.  The 1x1 conv over
         cat([theta_i, phi_j]) is a_i + b_j with a = theta . w[:ci], b = phi . w[ci:] -- the dot product of the 2-vectors
@@ -1453,6 +1550,9 @@ class Plan:
         4-float rows (two live columns), and f . g runs in the same launch: the [N, Sq, Sk] affinity never reaches
         HBM.  Two small GEMMs produce the rows: Linear(ci -> 4) with weight rows (w_theta, 0, 0, 0) / bias (0, 1, 0, 0)
         and weight rows (0, w_phi, 0, 0) / bias (1, 0, 0, 0).  Returns False (nothing emitted) under PTX_NL_FUSED=0."""
+        if self.bf16:
+            ta, pb = self.concat_rows_bf16(th, ph, nl, label)
+            return self.attention_bf16(ta, pb, g, y, scale_only=True, relu=True)
         if os.environ.get("PTX_NL_FUSED", "1") == "0":
             return False
         ci = th.C
@@ -1488,6 +1588,11 @@ class Plan:
             raise PtxError("%s: the fused concatenation attention refused a supported shape" % label)
         return True
 
+    def pool_target(self, x, win):
+        """A compact bf16 output for the non-local block's 2x2x2 sub-sampling pool of x (stride = window, no padding)."""
+        To, Ho, Wo = ((e - w) // w + 1 for e, w in zip((x.T, x.H, x.W), win))
+        return self.act(x.N, To, Ho, Wo, x.C, f16=True)
+
     def nonlocal_block(self, x, nl, label):
         """Non-local block (nonlocalnet.py:139-243): pointwise projections in one launch, f = theta^T phi on
         MFMA, row softmax (or 1/N scaling), y = f g on MFMA, W projection (+BN) + residual in one launch.
@@ -1506,6 +1611,19 @@ class Plan:
         if mode == "gaussian":
             g_act = self.conv(x, self.pack(g_conv, None), one, zero, label=label + ".g")
             th_act = ph_act = x                                   # theta = phi = the input itself
+        elif self.bf16 and mode == "concatenation":
+            # bf16 'concatenation': theta and phi feed the two row convs (concat_rows_bf16), and a conv reads every channel
+            # of its input row (ldx), so they are compact activations of their own here rather than slices of one output
+            th_act = self.conv(x, self.pack(nl.theta, None), one, zero, label=label + ".theta")
+            ph_act = self.conv(x, self.pack(first(nl.phi), None), one, zero, label=label + ".phi")
+            g_act = self.conv(x, self.pack(g_conv, None), one, zero, label=label + ".g")
+        elif self.bf16:
+            # bf16: theta | phi | g each on an 8-channel boundary (zero filter rows / bias between): 16-byte aligned slices
+            # whose pad channels are zero -- what the bf16 attention contracts over
+            c8 = _r8(ci)
+            tpg = self.conv(x, self.pack([nl.theta, first(nl.phi), g_conv], None, pad8=True), one, zero,
+                            label=label + ".theta_phi_g")
+            th_act, ph_act, g_act = tpg.slice(0, ci), tpg.slice(c8, ci), tpg.slice(2 * c8, ci)
         else:
             tpg = self.conv(x, self.pack([nl.theta, first(nl.phi), g_conv], None), one, zero, label=label + ".theta_phi_g")
             th_act, ph_act, g_act = tpg.slice(0, ci), tpg.slice(ci, ci), tpg.slice(2 * ci, ci)
@@ -1516,10 +1634,16 @@ class Plan:
             pool = (win, win, (0, 0, 0))
             if any(e < w for e, w in zip((x.T, x.H, x.W), win)):
                 raise PtxError("%s: sub_sample needs at least 2 positions along every pooled axis" % label)
-            ph_act = self.maxpool(ph_act, *pool)
-            g_act = self.maxpool(g_act, *pool)
+            if self.bf16:
+                # compact outputs; the bf16 pool writes channels [0, round8(C)) as maxima over the input's pad channels,
+                # which are zero (zero filter rows, or the zero-filled pad of x), and the buffers start zeroed
+                ph_act = self.maxpool(ph_act, *pool, y=self.pool_target(ph_act, win))
+                g_act = self.maxpool(g_act, *pool, y=self.pool_target(g_act, win))
+            else:
+                ph_act = self.maxpool(ph_act, *pool)
+                g_act = self.maxpool(g_act, *pool)
         N, Sq, Sk, K = x.N, x.S, ph_act.S, th_act.C
-        yatt = self.act(x.N, x.T, x.H, x.W, ci)
+        yatt = self.act(x.N, x.T, x.H, x.W, ci, f16=self.bf16)
         fused = False
         if mode == "concatenation":
             fused = self.concat_attention(th_act, ph_act, g_act, yatt, nl, label)
@@ -1566,8 +1690,10 @@ class Plan:
         if self.bf16:
             name = str(getattr(model, "arch_name", None) or type(model).__name__)
             arch = getattr(model, "arch", None)
-            if (kind != "resnet" or name.split("@")[0] not in BF16_FAMILIES or arch is None or arch.nonlocal_layers or arch.dims != 3
-                    or arch.block not in ("basic", "bottleneck")):
+            # the standalone non-local blocks and MNISTNonLocalNet run on the bf16 attention kernel
+            if kind not in BF16_NL_KINDS and (
+                    kind != "resnet" or name.split("@")[0] not in BF16_FAMILIES or arch is None or arch.nonlocal_layers
+                    or arch.dims != 3 or arch.block not in ("basic", "bottleneck")):
                 raise PtxError("bf16 inference covers the ResNet3D (resnet3d10..200) and R(2+1)D (r2plus1d10..50) families; "
                                "%s (plan kind %r) has bf16 parameters: run it in float32" % (name, kind))
         if kind == "nlblock":                    # a standalone NonLocalBlock3D: [B,C,T,H,W] -> [B,C,T,H,W]

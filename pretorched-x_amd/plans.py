@@ -189,6 +189,8 @@ def build_mnist_nl(self, model):
         self.head_error = ("MNISTNonLocalNet: fc expects %d features (a 28x28 input), the conv stack produced %dx%dx%d" % (
             model.fc[0].in_features, x.C, x.H, x.W))
         return
+    if self.bf16:
+        return _mnist_head_bf16(self, model, x)
     flat = torch.empty((N, x.C, x.H, x.W), device=self.dev, dtype=torch.float32)      # NCHW: `.view(batch, -1)` order
     self.keepalive.append(flat)
     lib = self.lib
@@ -199,6 +201,49 @@ def build_mnist_nl(self, model):
         check(lib.ptx_ndhwc_to_ncdhw(_ptr(x.t), _ptr(flat), x.N, x.C, x.S, x.ld, _stream()), "ptx_ndhwc_to_ncdhw")
         h = linear(flat.view(x.N, -1), model.fc[0], PTX_EPI_RELU)          # Dropout is the identity in eval mode
         return linear(h, model.fc[3])
+    self.head = head
+
+
+def _mnist_head_bf16(self, model, x):
+    """bf16 MNISTNonLocalNet classifier, fp32 as in the bf16 ResNets: the bf16 features leave in NCHW order
+    (ptx_ndhwc_to_ncdhw_bf16), are widened exactly to fp32 (ptx_bf16_to_f32) and run through fp32 copies of fc[0] / fc[3]
+    (made when the plan is packed, refreshed with it in place); the logits are rounded to bf16 once."""
+    N, dev = x.N, self.dev
+    lins = [model.fc[0], model.fc[3]]
+    f32 = dict(device=dev, dtype=torch.float32)
+    w32 = [torch.zeros(tuple(l.weight.shape), **f32) for l in lins]
+    b32 = [torch.zeros(l.out_features, **f32) for l in lins]
+    flat16 = torch.empty((N, x.C, x.H, x.W), device=dev, dtype=torch.bfloat16)       # NCHW: `.view(batch, -1)` order
+    flat = torch.empty((N, x.C * x.H * x.W), **f32)
+    hid = torch.empty((N, lins[0].out_features), **f32)
+    out32 = torch.empty((N, lins[1].out_features), **f32)
+    self.keepalive += w32 + b32 + [flat16, flat, hid, out32]
+    refs = [self.ref(l) for l in lins]
+
+    def refresh():
+        for r, w, b in zip(refs, w32, b32):
+            lin = self.get(r)
+            w.copy_(lin.weight.detach())
+            if lin.bias is not None:
+                b.copy_(lin.bias.detach())
+            else:
+                b.zero_()
+    if torch.device(dev).type != "meta":
+        self.refreshers.append(refresh)
+    lib = self.lib
+
+    def head(engine, model, x=x):
+        from ._lib import PTX_EPI_RELU
+        st = _stream()
+        K, H1, O = flat.shape[1], hid.shape[1], out32.shape[1]
+        check(lib.ptx_ndhwc_to_ncdhw_bf16(_ptr(x.t), _ptr(flat16), x.N, x.C, x.S, x.ld, st), "ptx_ndhwc_to_ncdhw_bf16")
+        check(lib.ptx_bf16_to_f32(_ptr(flat16), _ptr(flat), flat.numel(), st), "ptx_bf16_to_f32")
+        # Linear -> ReLU (-> Dropout: the identity in eval mode) -> Linear
+        check(lib.ptx_linear_fwd(_ptr(flat), _ptr(w32[0]), _ptr(b32[0]), _ptr(hid), N, K, H1, K, H1, PTX_EPI_RELU, st), "fc.0")
+        check(lib.ptx_linear_fwd(_ptr(hid), _ptr(w32[1]), _ptr(b32[1]), _ptr(out32), N, H1, O, H1, O, 0, st), "fc.3")
+        out = torch.empty((N, O), device=x.t.device, dtype=torch.bfloat16)
+        check(lib.ptx_f32_to_bf16(_ptr(out32), _ptr(out), out32.numel(), st), "ptx_f32_to_bf16")
+        return out
     self.head = head
 
 
