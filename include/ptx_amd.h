@@ -52,6 +52,9 @@ typedef void* ptx_stream_t; /* hipStream_t */
                                 ".../f16" tile configurations (BigGAN generator, BASELINE config 5)            */
 #define PTX_ACT_OUT_F16 0x100 /* ptx_affine_act_upsample: OR into `act` -- y is written as halfs (ldy in halfs,
                                 multiple of 8): the cBN -> ReLU -> upsample pass feeds an fp16-operand conv      */
+#define PTX_ACT_OUT_BF16 0x200 /* ptx_affine_act_upsample: OR into `act` (not with PTX_ACT_OUT_F16) -- y is written as
+                                bfloat16, the fp32 result rounded once (ldy in elements, multiple of 8): the first cBN
+                                pass of a bf16 generator plan feeds a bf16-operand conv                          */
 #define PTX_F16X3_OPERANDS 0x8000u /* ptx_conv3d_fwd / ptx_conv3d_dual_fwd: fp32-ACCURATE products on the fp16 matrix
                                 cores.  x stays fp32 (same layout as the default path); w_packed is packed with
                                 ptx_pack_desc.f16 == 2: every 8-channel block of a filter row is stored as 8 "hi" halfs then 8
@@ -616,6 +619,16 @@ int ptx_conv1x1_pro_f16_fwd(const ptx_conv3d_desc* desc, const void* x, const pt
 int ptx_conv3x3_f16_supported(const ptx_conv3d_desc* desc);
 int ptx_conv3x3_f16_fwd(const ptx_conv3d_desc* desc, const void* x, const void* w_packed, const float* bias, void* y,
                         const ptx_conv_fused_ext* ext, ptx_stream_t stream);
+/* ptx_conv3x3_bf16_fwd / ptx_conv1x1_skip_bf16_fwd -- the same two kernels on bfloat16 operands (bf16 generator plans):
+ * same tiles, descriptor and ext conventions, with PTX_BF16_OPERANDS required in desc->flags (the fp16 entry points refuse
+ * it).  x, w_packed (ptx_pack_desc.f16 == 3), res, y and ext->y_raw hold bf16; products on v_mfma_f32_32x32x16_bf16 with
+ * fp32 accumulate; bias, skip, affine and ReLU in fp32, each output rounded to bf16 once (y_raw too). */
+int ptx_conv3x3_bf16_supported(const ptx_conv3d_desc* desc);
+int ptx_conv3x3_bf16_fwd(const ptx_conv3d_desc* desc, const void* x, const void* w_packed, const float* bias, void* y,
+                         const ptx_conv_fused_ext* ext, ptx_stream_t stream);
+int ptx_conv1x1_skip_bf16_supported(const ptx_conv3d_desc* desc);
+int ptx_conv1x1_skip_bf16_fwd(const ptx_conv3d_desc* desc, const void* x, const void* w_packed, const float* bias, const void* res,
+                              void* y, const ptx_conv_fused_ext* ext, ptx_stream_t stream);
 
 /* ============================================================================================
  * EXPERIMENTAL entry points (PTX_EXPERIMENTAL_API).  Built, tested and exported, but NOT on the default path: each was

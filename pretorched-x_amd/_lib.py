@@ -24,6 +24,7 @@ PTX_SPLITK_FUSED = 0x10000
 PTX_BF16_OPERANDS = 0x20000      # with PTX_F16_OPERANDS: bfloat16 operands / 16-bit outputs and skips (bf16 plans)
 PTX_PACK_BF16 = 3                # ptx_pack_desc.f16: filter written as bf16
 PTX_ACT_OUT_F16 = 0x100
+PTX_ACT_OUT_BF16 = 0x200         # ptx_affine_act_upsample: y written as bf16 (the fp32 result rounded once)
 PTX_EPI_OUT_F16, PTX_EPI_AFFINE, PTX_EPI_DUAL_RAW, PTX_RES_F16, PTX_PRO_UP2, PTX_EPI_TANH = 0x200, 0x400, 0x800, 0x1000, 0x2000, 0x4000
 
 
@@ -211,6 +212,10 @@ SIGNATURES = {
     "ptx_conv1x1_pro_f16_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, C.POINTER(ConvFusedExt), _P, _P, _P, C.POINTER(ConvFusedExt), _P]),
     "ptx_conv3x3_f16_supported": (C.c_int, [C.POINTER(ConvDesc)]),
     "ptx_conv3x3_f16_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, C.POINTER(ConvFusedExt), _P]),
+    "ptx_conv3x3_bf16_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "ptx_conv3x3_bf16_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, C.POINTER(ConvFusedExt), _P]),
+    "ptx_conv1x1_skip_bf16_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "ptx_conv1x1_skip_bf16_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, C.POINTER(ConvFusedExt), _P]),
     "ptx_rgb_conv3x3_f16_supported": (C.c_int, [C.POINTER(RgbConvDesc)]),
     "ptx_rgb_conv_weight_elems": (_Z, [_I]),
     "ptx_pack_rgb_conv_weight": (C.c_int, [_P, _I, _P, _P]),

@@ -67,7 +67,11 @@ _ARCH = {
 
 
 class BigGANDeepGenerator(EngineOwner, nn.Module):
-    """forward(z [B,dim_z], y [B,shared_dim] = self.shared(labels)) -> images [B,3,R,R] in (-1, 1)."""
+    """forward(z [B,dim_z], y [B,shared_dim] = self.shared(labels)) -> images [B,3,R,R] in (-1, 1).
+
+    bf16: a generator whose parameters are torch.bfloat16 (`G.to(torch.bfloat16)`) takes bf16 z / y and returns bf16
+    images; every conv runs on bf16 operands with fp32 accumulation and an fp32 epilogue (DESIGN.md
+    3.20).  The parameter dtype decides: `precision` applies to fp32-parameter generators only."""
     plan_kind = "biggan"
 
     def __init__(self, resolution=256, ch=128, dim_z=128, shared_dim=128, n_classes=1000, depth=2, bottom_width=4,
@@ -76,7 +80,8 @@ class BigGANDeepGenerator(EngineOwner, nn.Module):
         if precision not in ("fp32", "fp16"):
             raise ValueError("precision must be 'fp32' or 'fp16'")
         # 'fp16': the cBN -> ReLU (-> upsample) passes emit halfs and every GBlock / output conv runs on fp16 MFMA
-        # with fp32 accumulation, bias, skip connection and output (BASELINE.json config 5 names fp16 MFMA)
+        # with fp32 accumulation, bias, skip connection and output (BASELINE.json config 5 names fp16 MFMA).  Ignored once the
+        # parameters are bf16: that generator runs the bf16 plan
         self.precision = precision
         if resolution not in _ARCH:
             raise ValueError("resolution must be one of %s" % sorted(_ARCH))

@@ -66,7 +66,10 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ConvArgs p) {
                     half4_t{(_Float16)out[0], (_Float16)out[1], (_Float16)out[2], (_Float16)out[3]};
             else
                 *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.ldy + co) = f32x4{out[0], out[1], out[2], out[3]};
-            if (p.flags & PTX_EPI_DUAL_RAW)
+            if ((p.flags & PTX_EPI_DUAL_RAW) && p.bf16)          // (the raw sum of a bf16 plan: bf16 too)
+                *reinterpret_cast<bf16x4_t*>(reinterpret_cast<__bf16*>(p.y_raw) + (size_t)m * p.ld_raw + co) =
+                    bf16x4_t{(__bf16)raw[0], (__bf16)raw[1], (__bf16)raw[2], (__bf16)raw[3]};
+            else if (p.flags & PTX_EPI_DUAL_RAW)
                 *reinterpret_cast<half4_t*>(reinterpret_cast<_Float16*>(p.y_raw) + (size_t)m * p.ld_raw + co) =
                     half4_t{(_Float16)raw[0], (_Float16)raw[1], (_Float16)raw[2], (_Float16)raw[3]};
             continue;

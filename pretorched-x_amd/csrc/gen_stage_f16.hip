@@ -8,6 +8,11 @@
 //   ptx_conv1x1_skip_f16_fwd  a GBlock's closing 1x1 conv: + skip (upsampled, channel-truncated) and BOTH outputs the next block reads
 //   ptx_conv1x1_pro_f16_fwd   a GBlock's opening 1x1 conv with the block's cBN1 + ReLU applied to its input fragments
 //
+// The 3x3 and closing 1x1 kernels also come in bfloat16 (ptx_conv3x3_bf16_fwd / ptx_conv1x1_skip_bf16_fwd: bf16 plans of the
+// generator).  The loaders only move 16-bit words, so tiles, LDS plan and DMA are shared; the element type E selects the MFMA
+// form (v_mfma_f32_32x32x16_f16 / _bf16) and the rounding of the fp32 epilogue.  The _Float16 instantiations compile to the
+// same instructions as the fp16-only kernels did (llvm-objdump -d).
+//
 // ---- the image conv ----------------------------------------------------------------------------------------------------
 // 3 output channels waste 13/16 of the narrowest MFMA tile, and as an implicit GEMM the layer re-stages its input nine
 // times (0.75 ms at 256 x 256 x 128 x 64 images: 1.4 TB/s, 58 VALU + SALU instructions per MFMA).  Put the TAPS in the N
@@ -25,6 +30,11 @@
 namespace ptx {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
+
+// 32 x 32 x 16 MFMA of the element type (gfx950: the A / B lane maps and the C / D layout of the two forms match)
+__device__ __forceinline__ f32x16 mfma32x16(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16 mfma32x16(bf8 a, bf8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 
 struct RgbArgs {
     const _Float16* x;      // [N][H][W][ldx] halfs, RAW (pre-BN) feature map
@@ -188,8 +198,11 @@ __device__ unsigned long long* g_c3_tl = nullptr;
 
 // NCH: 64-channel input chunks (Ci = 64 NCH); CT: 32-channel output tiles of ONE workgroup (Co_wg = 32 CT: 64 or 128 --
 // wider outputs are cut along blockIdx.y, each part re-staging the patch: C = 256 runs as <4, 4> x 2)
-template <int NCH, int CT, bool UP2>
-__global__ void __launch_bounds__(256, 2) conv3x3_f16_kernel(const C3Args p) {
+// E: _Float16 or __bf16 (the bf16 kernels: same tiles, bf16 MFMAs, bf16 rounding of the fp32 epilogue)
+template <class E, int NCH, int CT, bool UP2>
+__global__ void __launch_bounds__(256, 2) conv3x3_kernel(const C3Args p) {
+    typedef E e8 __attribute__((ext_vector_type(8)));
+    typedef E e4 __attribute__((ext_vector_type(4)));
     constexpr int C = 32 * CT;                     // output channels of this workgroup
     constexpr int KH = CT == 2 ? 64 : 32;          // input channels of one filter tile = one step (16 MFMAs per wave either way)
     constexpr int SPT = 64 / KH;                   // steps per (tap, 64-channel chunk)
@@ -303,24 +316,24 @@ __global__ void __launch_bounds__(256, 2) conv3x3_f16_kernel(const C3Args p) {
     // The fragments of step s + 1 are requested while step s multiplies: group j's registers are refilled right after group
     // j's MFMAs have issued, so inside an input chunk no MFMA waits on an LDS read issued behind the same barrier (measured with
     // the phase clock, scripts/gpu_c3_timeline.py: read-then-multiply per tap took 2.4x the tap's MFMA time).
-    h8 xa[NJ][2], wb[NJ][CT];
+    e8 xa[NJ][2], wb[NJ][CT];
     auto load_group = [&](int j, int r, const char* Bb) {            // fragments of k-group j of step r (inside its chunk)
         const int tap = r / SPT, hf = r - tap * SPT;
         const int kh = tap / 3, kw = tap - kh * 3;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int pos = p_base + (i + kh) * kC3PW + kw;
-            xa[j][i] = *reinterpret_cast<const h8*>(Pa + pos * 128 + (((hf * RS + 2 * j + kg) ^ ((pos >> 1) & 7)) << 4));
+            xa[j][i] = *reinterpret_cast<const e8*>(Pa + pos * 128 + (((hf * RS + 2 * j + kg) ^ ((pos >> 1) & 7)) << 4));
         }
 #pragma unroll
-        for (int a = 0; a < CT; ++a) wb[j][a] = *reinterpret_cast<const h8*>(Bb + b_off[a] + (((2 * j + kg) ^ b_sw[a]) << 4));
+        for (int a = 0; a < CT; ++a) wb[j][a] = *reinterpret_cast<const e8*>(Bb + b_off[a] + (((2 * j + kg) ^ b_sw[a]) << 4));
     };
     auto mma_group = [&](int j) {
 #pragma unroll
         for (int a = 0; a < CT; ++a)
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                acc[a][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[j][a], xa[j][i], acc[a][i], 0, 0, 0);   // C^T[co][position]
+                acc[a][i] = mfma32x16(wb[j][a], xa[j][i], acc[a][i]);   // C^T[co][position]
     };
 
     // prologue: everything but filter tile 2 has landed -> tables to LDS, fragments of step 0
@@ -378,7 +391,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_f16_kernel(const C3Args p) {
     PTX_C3_TL(3);
     __syncthreads();                               // all fragment reads done: the patch area becomes the output tile
     const bool relu = (p.flags & PTX_EPI_RELU) != 0;
-    _Float16* T = reinterpret_cast<_Float16*>(Pa);
+    E* T = reinterpret_cast<E*>(Pa);
 #pragma unroll
     for (int a = 0; a < CT; ++a)
 #pragma unroll
@@ -387,15 +400,14 @@ __global__ void __launch_bounds__(256, 2) conv3x3_f16_kernel(const C3Args p) {
             const f32x4 sc = *reinterpret_cast<const f32x4*>(Sc + co), sf = *reinterpret_cast<const f32x4*>(Sh + co);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-                h4 o;
+                e4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[a][i][4 * g + e] * sc[e] + sf[e];
                     v = relu ? fmaxf(v, 0.f) : v;
-                    o[e] = (_Float16)v;
+                    o[e] = (E)v;
                 }
-                *reinterpret_cast<h4*>(T + ((2 * wave + i) * 32 + l32) * TP + co) = o;
+                *reinterpret_cast<e4*>(T + ((2 * wave + i) * 32 + l32) * TP + co) = o;
             }
         }
     __syncthreads();
@@ -417,6 +429,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_f16_kernel(const C3Args p) {
     PTX_C3_TL(5);
 #endif
 }
+
 
 
 // ---- the closing 1x1 conv of a GBlock (conv4: C/4 -> C' channels, + skip, two outputs) ----------------------------------------
@@ -445,8 +458,9 @@ struct C1Args {
 constexpr int kC1TP = 132;                                      // pitch (floats) of the parked half tile
 constexpr int kC1Lds = 128 * kC1TP * 4 + 3 * 128 * 4;           // parked tile (overlays the operand tiles) + bias / scale / shift
 
-template <int NCH>
-__global__ void __launch_bounds__(256, 2) conv1x1_skip_f16_kernel(const C1Args p) {
+template <class E, int NCH>
+__global__ void __launch_bounds__(256, 2) conv1x1_skip_kernel(const C1Args p) {
+    typedef E e8 __attribute__((ext_vector_type(8)));
     constexpr int CO = 128, CT = 4;
     constexpr int A_BYTES = 256 * 128, BT_BYTES = CO * 128;
     static_assert(A_BYTES + 2 * BT_BYTES <= 128 * kC1TP * 4, "operand tiles under the parked tile");
@@ -551,15 +565,15 @@ __global__ void __launch_bounds__(256, 2) conv1x1_skip_f16_kernel(const C1Args p
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int slot = 2 * j + kg;
-            h8 xa[2], wb[CT];
+            e8 xa[2], wb[CT];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) xa[i] = *reinterpret_cast<const h8*>(Pa + a_off[i] + ((slot ^ a_sw[i]) << 4));
+            for (int i = 0; i < 2; ++i) xa[i] = *reinterpret_cast<const e8*>(Pa + a_off[i] + ((slot ^ a_sw[i]) << 4));
 #pragma unroll
-            for (int a = 0; a < CT; ++a) wb[a] = *reinterpret_cast<const h8*>(Bb + b_off[a] + ((slot ^ b_sw[a]) << 4));
+            for (int a = 0; a < CT; ++a) wb[a] = *reinterpret_cast<const e8*>(Bb + b_off[a] + ((slot ^ b_sw[a]) << 4));
 #pragma unroll
             for (int a = 0; a < CT; ++a)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) acc[a][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[a], xa[i], acc[a][i], 0, 0, 0);
+                for (int i = 0; i < 2; ++i) acc[a][i] = mfma32x16(wb[a], xa[i], acc[a][i]);
         }
         if (s + 1 < NCH) {
             __syncthreads();                       // every wave is done with this input chunk
@@ -593,25 +607,25 @@ __global__ void __launch_bounds__(256, 2) conv1x1_skip_f16_kernel(const C1Args p
             const unsigned px = (unsigned)((n * p.H + h) * p.W + w);
             const f32x4 v0 = *reinterpret_cast<const f32x4*>(T + pl * kC1TP + sl * 8), v1 = *reinterpret_cast<const f32x4*>(T + pl * kC1TP + sl * 8 + 4);
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(Tb + sl * 8), b1 = *reinterpret_cast<const f32x4*>(Tb + sl * 8 + 4);
-            const h8 r = __builtin_bit_cast(h8, rq[it]);           // zeros without a skip operand (empty descriptor)
+            const e8 r = __builtin_bit_cast(e8, rq[it]);           // zeros without a skip operand (empty descriptor)
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = (e < 4 ? v0[e] + b0[e] : v1[e - 4] + b1[e - 4]) + (float)r[e];
             if (dual || !affine) {
-                h8 o;
+                e8 o;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (_Float16)((!affine && relu) ? fmaxf(v[e], 0.f) : v[e]);
+                for (int e = 0; e < 8; ++e) o[e] = (E)((!affine && relu) ? fmaxf(v[e], 0.f) : v[e]);
                 if (dual) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f32x4, o), rs_q, ok ? (px * (unsigned)p.ld_raw + co_base + sl * 8) * 2u : kOOB, 0, 0);
                 else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f32x4, o), rs_y, ok ? (px * (unsigned)p.ldy + co_base + sl * 8) * 2u : kOOB, 0, 0);
             }
             if (affine) {
                 const f32x4 s0 = *reinterpret_cast<const f32x4*>(Tb + CO + sl * 8), s1 = *reinterpret_cast<const f32x4*>(Tb + CO + sl * 8 + 4);
                 const f32x4 t0 = *reinterpret_cast<const f32x4*>(Tb + 2 * CO + sl * 8), t1 = *reinterpret_cast<const f32x4*>(Tb + 2 * CO + sl * 8 + 4);
-                h8 o;
+                e8 o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float u = v[e] * (e < 4 ? s0[e] : s1[e - 4]) + (e < 4 ? t0[e] : t1[e - 4]);
-                    o[e] = (_Float16)(relu ? fmaxf(u, 0.f) : u);
+                    o[e] = (E)(relu ? fmaxf(u, 0.f) : u);
                 }
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f32x4, o), rs_y, ok ? (px * (unsigned)p.ldy + co_base + sl * 8) * 2u : kOOB, 0, 0);
             }
@@ -628,6 +642,7 @@ __global__ void __launch_bounds__(256, 2) conv1x1_skip_f16_kernel(const C1Args p
     __syncthreads();
     copy_out(1, rq1);
 }
+
 
 
 // ---- the opening 1x1 conv of a GBlock (conv1: C -> C/4) with cBN1 + ReLU in its loader ------------------------------------------
@@ -863,9 +878,10 @@ extern "C" int ptx_c3_timeline(void* buf) {        // diagnostic build only: 8 x
 }
 #endif
 
-extern "C" int ptx_conv3x3_f16_supported(const ptx_conv3d_desc* d) {
+// bf: the bf16 entry point (PTX_BF16_OPERANDS required); the fp16 one refuses bf16 descriptors
+static int c3_supported(const ptx_conv3d_desc* d, bool bf) {
     if (!d) return 0;
-    const unsigned need = PTX_F16_OPERANDS | PTX_EPI_OUT_F16;
+    const unsigned need = PTX_F16_OPERANDS | PTX_EPI_OUT_F16 | (bf ? PTX_BF16_OPERANDS : 0u);
     const unsigned may = need | PTX_PRO_UP2 | PTX_EPI_AFFINE | PTX_EPI_RELU;
     if ((d->flags & need) != need || (d->flags & ~may)) return 0;
     const int C = 2 * d->Ci;                                   // fp16 descriptors count 32-bit words (channel pairs)
@@ -882,30 +898,38 @@ extern "C" int ptx_conv3x3_f16_supported(const ptx_conv3d_desc* d) {
     return (int64_t)d->N * cdiv(d->Hi, kC3TH) * cdiv(d->Wi, kC3TW) <= 0x7fffffffLL;
 }
 
-template <int NCH, int CT, bool UP2>
+extern "C" int ptx_conv3x3_f16_supported(const ptx_conv3d_desc* d) { return c3_supported(d, false); }
+extern "C" int ptx_conv3x3_bf16_supported(const ptx_conv3d_desc* d) { return c3_supported(d, true); }
+
+template <bool BF, int NCH, int CT, bool UP2>
 static int launch_c3(const C3Args& a, dim3 grid, hipStream_t st) {
     constexpr size_t lds = kC3PatchBytes + 4 * 8192 + 2 * (32 * CT) * sizeof(float);       // patch + four filter tiles + tables
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
+    const void* fn = BF ? reinterpret_cast<const void*>(&conv3x3_kernel<__bf16, NCH, CT, UP2>)
+                        : reinterpret_cast<const void*>(&conv3x3_kernel<_Float16, NCH, CT, UP2>);
     static bool attr_set[64] = {};
     int dev = 0;
     PTX_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        PTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_f16_kernel<NCH, CT, UP2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        PTX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_f16_kernel<NCH, CT, UP2>), grid, dim3(256), lds, st, a);
-    return hip_check(hipGetLastError(), "conv3x3_f16 launch");
+    if (BF) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_kernel<__bf16, NCH, CT, UP2>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_kernel<_Float16, NCH, CT, UP2>), grid, dim3(256), lds, st, a);
+    return hip_check(hipGetLastError(), BF ? "conv3x3_bf16 launch" : "conv3x3_f16 launch");
 }
 
-extern "C" int ptx_conv3x3_f16_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed, const float* bias, void* y,
-                                   const ptx_conv_fused_ext* ext, ptx_stream_t stream) {
-    if (!d || !x || !w_packed || !y) return fail(PTX_ERR_INVALID, "conv3x3_f16: null pointer");
-    if (!ptx_conv3x3_f16_supported(d))
-        return fail(PTX_ERR_UNSUPPORTED, "conv3x3_f16: a unit-stride 3x3 conv with pad 1 over halfs, Ci == Co in {64, 128, 256}, at least 32 columns, halfs out, "
-                    "flags within F16_OPERANDS | OUT_F16 | PRO_UP2 | EPI_AFFINE | EPI_RELU");
+template <bool BF>
+static int c3_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed, const float* bias, void* y,
+                  const ptx_conv_fused_ext* ext, ptx_stream_t stream) {
+    const char* nm = BF ? "conv3x3_bf16" : "conv3x3_f16";
+    if (!d || !x || !w_packed || !y) return fail(PTX_ERR_INVALID, "%s: null pointer", nm);
+    if (!c3_supported(d, BF))
+        return fail(PTX_ERR_UNSUPPORTED, "%s: a unit-stride 3x3 conv with pad 1 over 16-bit operands, Ci == Co in {64, 128, 256}, at least 32 columns, "
+                    "16-bit out, flags within F16_OPERANDS | OUT_F16 | PRO_UP2 | EPI_AFFINE | EPI_RELU (| BF16_OPERANDS: exactly on the bf16 entry point)", nm);
     if ((d->flags & PTX_EPI_AFFINE) && (!ext || !ext->scale || !ext->shift || ext->ld_affine < d->Co || ext->ld_affine % 4))
-        return fail(PTX_ERR_INVALID, "conv3x3_f16: PTX_EPI_AFFINE needs scale / shift tables with a row stride that is a multiple of 4");
-    if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)bias) & 15) return fail(PTX_ERR_INVALID, "conv3x3_f16: misaligned pointer");
+        return fail(PTX_ERR_INVALID, "%s: PTX_EPI_AFFINE needs scale / shift tables with a row stride that is a multiple of 4", nm);
+    if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)bias) & 15) return fail(PTX_ERR_INVALID, "%s: misaligned pointer", nm);
     const bool up2 = (d->flags & PTX_PRO_UP2) != 0;
     C3Args a{};
     a.x = static_cast<const _Float16*>(x); a.w = static_cast<const _Float16*>(w_packed); a.bias = bias;
@@ -921,14 +945,24 @@ extern "C" int ptx_conv3x3_f16_fwd(const ptx_conv3d_desc* d, const void* x, cons
     a.flags = d->flags;
     const dim3 grid((unsigned)(d->N * a.tiles_h * a.tiles_w), (unsigned)(d->Co <= 128 ? 1 : d->Co / 128));
     const hipStream_t st = (hipStream_t)stream;
-    if (d->Co == 64) return up2 ? launch_c3<1, 2, true>(a, grid, st) : launch_c3<1, 2, false>(a, grid, st);
-    if (d->Co == 128) return up2 ? launch_c3<2, 4, true>(a, grid, st) : launch_c3<2, 4, false>(a, grid, st);
-    return up2 ? launch_c3<4, 4, true>(a, grid, st) : launch_c3<4, 4, false>(a, grid, st);
+    if (d->Co == 64) return up2 ? launch_c3<BF, 1, 2, true>(a, grid, st) : launch_c3<BF, 1, 2, false>(a, grid, st);
+    if (d->Co == 128) return up2 ? launch_c3<BF, 2, 4, true>(a, grid, st) : launch_c3<BF, 2, 4, false>(a, grid, st);
+    return up2 ? launch_c3<BF, 4, 4, true>(a, grid, st) : launch_c3<BF, 4, 4, false>(a, grid, st);
 }
 
-extern "C" int ptx_conv1x1_skip_f16_supported(const ptx_conv3d_desc* d) {
+extern "C" int ptx_conv3x3_f16_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed, const float* bias, void* y,
+                                   const ptx_conv_fused_ext* ext, ptx_stream_t stream) {
+    return c3_fwd<false>(d, x, w_packed, bias, y, ext, stream);
+}
+
+extern "C" int ptx_conv3x3_bf16_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed, const float* bias, void* y,
+                                    const ptx_conv_fused_ext* ext, ptx_stream_t stream) {
+    return c3_fwd<true>(d, x, w_packed, bias, y, ext, stream);
+}
+
+static int c1_supported(const ptx_conv3d_desc* d, bool bf) {
     if (!d) return 0;
-    const unsigned need = PTX_F16_OPERANDS | PTX_EPI_OUT_F16;
+    const unsigned need = PTX_F16_OPERANDS | PTX_EPI_OUT_F16 | (bf ? PTX_BF16_OPERANDS : 0u);
     const unsigned may = need | PTX_EPI_AFFINE | PTX_EPI_RELU | PTX_EPI_DUAL_RAW | PTX_RES_F16 | PTX_EPI_RES_ADD | PTX_EPI_RES_PADA | PTX_EPI_RES_UP;
     if ((d->flags & need) != need || (d->flags & ~may)) return 0;
     const int K = 2 * d->Ci;
@@ -952,36 +986,45 @@ extern "C" int ptx_conv1x1_skip_f16_supported(const ptx_conv3d_desc* d) {
     return (int64_t)d->N * cdiv(d->Hi, kC3TH) * cdiv(d->Wi, kC3TW) <= 0x7fffffffLL;
 }
 
-template <int NCH>
+extern "C" int ptx_conv1x1_skip_f16_supported(const ptx_conv3d_desc* d) { return c1_supported(d, false); }
+extern "C" int ptx_conv1x1_skip_bf16_supported(const ptx_conv3d_desc* d) { return c1_supported(d, true); }
+
+template <bool BF, int NCH>
 static int launch_c1(const C1Args& a, dim3 grid, hipStream_t st) {
     static_assert(kC1Lds <= 80 * 1024, "two workgroups per CU");
+    const void* fn = BF ? reinterpret_cast<const void*>(&conv1x1_skip_kernel<__bf16, NCH>)
+                        : reinterpret_cast<const void*>(&conv1x1_skip_kernel<_Float16, NCH>);
     static bool attr_set[64] = {};
     int dev = 0;
     PTX_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        PTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_skip_f16_kernel<NCH>), hipFuncAttributeMaxDynamicSharedMemorySize, kC1Lds));
+        PTX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kC1Lds));
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv1x1_skip_f16_kernel<NCH>), grid, dim3(256), kC1Lds, st, a);
-    return hip_check(hipGetLastError(), "conv1x1_skip_f16 launch");
+    if (BF) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv1x1_skip_kernel<__bf16, NCH>), grid, dim3(256), kC1Lds, st, a);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv1x1_skip_kernel<_Float16, NCH>), grid, dim3(256), kC1Lds, st, a);
+    return hip_check(hipGetLastError(), BF ? "conv1x1_skip_bf16 launch" : "conv1x1_skip_f16 launch");
 }
 
-extern "C" int ptx_conv1x1_skip_f16_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed, const float* bias, const void* res,
-                                        void* y, const ptx_conv_fused_ext* ext, ptx_stream_t stream) {
-    if (!d || !x || !w_packed || !y) return fail(PTX_ERR_INVALID, "conv1x1_skip_f16: null pointer");
-    if (!ptx_conv1x1_skip_f16_supported(d))
-        return fail(PTX_ERR_UNSUPPORTED, "conv1x1_skip_f16: a 1x1 conv over halfs with 64 / 128 / 256 input channels, a multiple of 128 output "
-                    "channels, at least 32 columns, halfs out, an optional half skip operand (same shape, or nearest-upsampled and channel-truncated)");
+template <bool BF>
+static int c1_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed, const float* bias, const void* res,
+                  void* y, const ptx_conv_fused_ext* ext, ptx_stream_t stream) {
+    const char* nm = BF ? "conv1x1_skip_bf16" : "conv1x1_skip_f16";
+    if (!d || !x || !w_packed || !y) return fail(PTX_ERR_INVALID, "%s: null pointer", nm);
+    if (!c1_supported(d, BF))
+        return fail(PTX_ERR_UNSUPPORTED, "%s: a 1x1 conv over 16-bit operands with 64 / 128 / 256 input channels, a multiple of 128 output "
+                    "channels, at least 32 columns, 16-bit out, an optional 16-bit skip operand (same shape, or nearest-upsampled and "
+                    "channel-truncated); PTX_BF16_OPERANDS exactly on the bf16 entry point", nm);
     const bool has_res = (d->flags & (PTX_EPI_RES_ADD | PTX_EPI_RES_PADA)) != 0;
-    if (has_res && !res) return fail(PTX_ERR_INVALID, "conv1x1_skip_f16: residual flag set but res == NULL");
+    if (has_res && !res) return fail(PTX_ERR_INVALID, "%s: residual flag set but res == NULL", nm);
     if ((d->flags & PTX_EPI_AFFINE) && (!ext || !ext->scale || !ext->shift || ext->ld_affine < d->Co || ext->ld_affine % 4))
-        return fail(PTX_ERR_INVALID, "conv1x1_skip_f16: PTX_EPI_AFFINE needs scale / shift tables with a row stride that is a multiple of 4");
+        return fail(PTX_ERR_INVALID, "%s: PTX_EPI_AFFINE needs scale / shift tables with a row stride that is a multiple of 4", nm);
     if ((d->flags & PTX_EPI_DUAL_RAW) && (!ext || !ext->y_raw || ext->ld_raw < d->Co || ext->ld_raw % 8))
-        return fail(PTX_ERR_INVALID, "conv1x1_skip_f16: PTX_EPI_DUAL_RAW needs ext->y_raw with a row stride that is a multiple of 8 halfs");
+        return fail(PTX_ERR_INVALID, "%s: PTX_EPI_DUAL_RAW needs ext->y_raw with a row stride that is a multiple of 8 elements", nm);
     if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)(ext ? ext->y_raw : nullptr)) & 15)
-        return fail(PTX_ERR_INVALID, "conv1x1_skip_f16: misaligned pointer");
+        return fail(PTX_ERR_INVALID, "%s: misaligned pointer", nm);
     if ((d->flags & PTX_EPI_DUAL_RAW) && (uint64_t)d->N * d->Hi * d->Wi * ext->ld_raw * 2ull >= 0x80000000ull)
-        return fail(PTX_ERR_UNSUPPORTED, "conv1x1_skip_f16: the raw output of one launch must be < 2 GiB");
+        return fail(PTX_ERR_UNSUPPORTED, "%s: the raw output of one launch must be < 2 GiB", nm);
     C1Args a{};
     a.x = static_cast<const _Float16*>(x); a.w = static_cast<const _Float16*>(w_packed); a.bias = bias;
     a.res = has_res ? static_cast<const _Float16*>(res) : nullptr;
@@ -1005,7 +1048,17 @@ extern "C" int ptx_conv1x1_skip_f16_fwd(const ptx_conv3d_desc* d, const void* x,
     const dim3 grid((unsigned)(d->N * a.tiles_h * a.tiles_w), (unsigned)(d->Co / 128));
     const hipStream_t st = (hipStream_t)stream;
     const int K = 2 * d->Ci;
-    return K == 64 ? launch_c1<1>(a, grid, st) : K == 128 ? launch_c1<2>(a, grid, st) : launch_c1<4>(a, grid, st);
+    return K == 64 ? launch_c1<BF, 1>(a, grid, st) : K == 128 ? launch_c1<BF, 2>(a, grid, st) : launch_c1<BF, 4>(a, grid, st);
+}
+
+extern "C" int ptx_conv1x1_skip_f16_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed, const float* bias, const void* res,
+                                        void* y, const ptx_conv_fused_ext* ext, ptx_stream_t stream) {
+    return c1_fwd<false>(d, x, w_packed, bias, res, y, ext, stream);
+}
+
+extern "C" int ptx_conv1x1_skip_bf16_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed, const float* bias, const void* res,
+                                         void* y, const ptx_conv_fused_ext* ext, ptx_stream_t stream) {
+    return c1_fwd<true>(d, x, w_packed, bias, res, y, ext, stream);
 }
 
 // ---- ptx_conv1x1_pro_f16: descriptor = ptx_conv3d_desc of the 1x1 conv; the INPUT affine travels in ext_in (scale / shift /

@@ -134,6 +134,8 @@ BF16_FAMILIES = ("resnet3d10", "resnet3d18", "resnet3d34", "resnet3d50", "resnet
 # ... and the plan kinds built from non-local blocks alone: NonLocalBlock1D / 2D / 3D and MNISTNonLocalNet (the networks that
 # embed blocks in a ResNet, nonlocalresnet3d50 / nonlocal_r2plus1d50, keep raising)
 BF16_NL_KINDS = ("nlblock", "mnist_nl")
+# ... and the BigGAN-deep generator (every resolution and width; plans.build_biggan's bf16 flow)
+BF16_GEN_KINDS = ("biggan",)
 
 
 def model_precision(model):
@@ -749,7 +751,8 @@ class StemStep:
 class PatchConvStep:
     """One launch of a generator-stage kernel designed for the fp16 matrix cores (gen_stage_f16.hip) instead of the
     implicit-GEMM tiles: ptx_conv3x3_f16_fwd (a GBlock's 3x3 convs, one staged input patch per tile) or, with `res` set /
-    kernel == "conv1x1_skip_f16", ptx_conv1x1_skip_f16_fwd (its closing 1x1 conv + skip + both outputs)."""
+    kernel == "conv1x1_skip_f16", ptx_conv1x1_skip_f16_fwd (its closing 1x1 conv + skip + both outputs); the "_bf16"
+    kernels are their bf16 builds (bf16 generator plans)."""
     __slots__ = ("d", "x", "w", "b", "y", "ext", "res", "kernel", "label", "macs", "hbm_bytes", "ext_in")
 
     def __call__(self, st):
@@ -758,6 +761,10 @@ class PatchConvStep:
             check(_lib.lib().ptx_conv1x1_pro_f16_fwd(C.byref(self.d), self.x, C.byref(self.ext_in), self.w, self.b, self.y, ext, st), self.label)
         elif self.kernel == "conv3x3_f16":
             check(_lib.lib().ptx_conv3x3_f16_fwd(C.byref(self.d), self.x, self.w, self.b, self.y, ext, st), self.label)
+        elif self.kernel == "conv3x3_bf16":
+            check(_lib.lib().ptx_conv3x3_bf16_fwd(C.byref(self.d), self.x, self.w, self.b, self.y, ext, st), self.label)
+        elif self.kernel == "conv1x1_skip_bf16":
+            check(_lib.lib().ptx_conv1x1_skip_bf16_fwd(C.byref(self.d), self.x, self.w, self.b, self.res, self.y, ext, st), self.label)
         else:
             check(_lib.lib().ptx_conv1x1_skip_f16_fwd(C.byref(self.d), self.x, self.w, self.b, self.res, self.y, ext, st), self.label)
 
@@ -1010,6 +1017,13 @@ class Plan:
                 patch = "conv3x3_f16"
             elif os.environ.get("PTX_CONV1X1_F16", "1") != "0" and self.lib.ptx_conv1x1_skip_f16_supported(C.byref(d)):
                 patch = "conv1x1_skip_f16"
+        elif fused and not tanh and x2 is None and getattr(self, "gen_patch", False):
+            # bf16 generator plans: the same two kernels on bf16 operands; PTX_CONV3X3_BF16=0 / PTX_CONV1X1_BF16=0: A/B runs
+            if (res is None and not raw and os.environ.get("PTX_CONV3X3_BF16", "1") != "0"
+                    and self.lib.ptx_conv3x3_bf16_supported(C.byref(d))):
+                patch = "conv3x3_bf16"
+            elif os.environ.get("PTX_CONV1X1_BF16", "1") != "0" and self.lib.ptx_conv1x1_skip_bf16_supported(C.byref(d)):
+                patch = "conv1x1_skip_bf16"
         if patch is not None:
             ps = PatchConvStep()
             ps.d, ps.x, ps.w, ps.b, ps.y, ps.ext, ps.label = d, st.x, st.w, st.b, st.y, ext, label
@@ -1691,10 +1705,11 @@ class Plan:
             name = str(getattr(model, "arch_name", None) or type(model).__name__)
             arch = getattr(model, "arch", None)
             # the standalone non-local blocks and MNISTNonLocalNet run on the bf16 attention kernel
-            if kind not in BF16_NL_KINDS and (
+            if kind not in BF16_NL_KINDS + BF16_GEN_KINDS and (
                     kind != "resnet" or name.split("@")[0] not in BF16_FAMILIES or arch is None or arch.nonlocal_layers
                     or arch.dims != 3 or arch.block not in ("basic", "bottleneck")):
-                raise PtxError("bf16 inference covers the ResNet3D (resnet3d10..200) and R(2+1)D (r2plus1d10..50) families; "
+                raise PtxError("bf16 inference covers the ResNet3D (resnet3d10..200) and R(2+1)D (r2plus1d10..50) families, "
+                               "the non-local blocks and the BigGAN-deep generator; "
                                "%s (plan kind %r) has bf16 parameters: run it in float32" % (name, kind))
         if kind == "nlblock":                    # a standalone NonLocalBlock3D: [B,C,T,H,W] -> [B,C,T,H,W]
             N, Cc, T, H, W = self.shape
@@ -2549,19 +2564,24 @@ class Engine:
 
     # ------------------------------------------------------------------------------------
     def generate(self, model, z, y):
-        """BigGAN-deep generator: z [B,dim_z], y [B,shared_dim] (= model.shared(labels)) -> images [B,3,R,R]."""
+        """BigGAN-deep generator: z [B,dim_z], y [B,shared_dim] (= model.shared(labels)) -> images [B,3,R,R].  A generator
+        whose parameters are bfloat16 takes bf16 z / y and returns bf16 images; otherwise everything is float32."""
         if model.training:
             raise PtxError("pretorched-x_amd is a forward-only (inference) engine: call model.eval() first")
+        prec = model_precision(model)
+        want = torch.bfloat16 if prec == "bf16" else torch.float32
         for t, d, nm in ((z, model.dim_z, "z"), (y, model.shared_dim, "y")):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-                raise PtxError("generate: %s must be a float32 CUDA tensor (no CPU fallback)" % nm)
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != want:
+                raise PtxError("generate: %s must be a %s CUDA tensor (no CPU fallback)%s" % (
+                    nm, "bfloat16" if prec == "bf16" else "float32",
+                    "; the generator's parameters are bfloat16" if prec == "bf16" else ""))
             if t.dim() != 2 or t.shape[1] != d:
                 raise PtxError("generate: %s must be [B, %d], got %s" % (nm, d, tuple(t.shape)))
         if z.shape[0] != y.shape[0] or z.device != y.device:
             raise PtxError("generate: z and y must share batch size and device")
         z, y = z.contiguous(), y.contiguous()
         N = z.shape[0]
-        key = ("maxb", ("biggan",))
+        key = ("maxb", ("biggan", prec))
         with self._lock:
             mb = self._sig.get(key)
             if mb is None:
@@ -2607,9 +2627,14 @@ class Engine:
                 plan.bind(model)
                 plan.in_ptr2 = _ptr(y)
                 f = plan.run_features(z)
-                out = torch.empty((N, 3, f.H, f.W), device=z.device, dtype=torch.float32)
-                check(_lib.lib().ptx_ndhwc_to_ncdhw(_ptr(f.t), _ptr(out), N, 3, f.H * f.W, f.ld, _stream()),
-                      "ptx_ndhwc_to_ncdhw")
+                if f.bf16:       # bf16 plans: the tanh conv wrote bf16, the layout pass keeps it
+                    out = torch.empty((N, 3, f.H, f.W), device=z.device, dtype=torch.bfloat16)
+                    check(_lib.lib().ptx_ndhwc_to_ncdhw_bf16(_ptr(f.t), _ptr(out), N, 3, f.H * f.W, f.ld, _stream()),
+                          "ptx_ndhwc_to_ncdhw_bf16")
+                else:
+                    out = torch.empty((N, 3, f.H, f.W), device=z.device, dtype=torch.float32)
+                    check(_lib.lib().ptx_ndhwc_to_ncdhw(_ptr(f.t), _ptr(out), N, 3, f.H * f.W, f.ld, _stream()),
+                          "ptx_ndhwc_to_ncdhw")
         return out
 
     def forward_frames(self, model, frames, opts=None):

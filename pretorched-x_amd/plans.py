@@ -9,8 +9,8 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from ._lib import PTX_ACT_OUT_F16, PtxError, check
-from .engine import RawInput, _geom, _ptr, _r4, _stream
+from ._lib import PTX_ACT_OUT_BF16, PTX_ACT_OUT_F16, PtxError, check
+from .engine import RawInput, _geom, _ptr, _r4, _r8, _stream
 
 
 # --------------------------------------------------------------------------------------------
@@ -278,6 +278,12 @@ def build_biggan(self, model):
 
     bn_refs = [(self.ref(bn), offs[id(bn)], bn.channels) for bn in ccbns]
     lin_ref, obn_ref = self.ref(model.linear), self.ref(obn)
+    bf16 = self.bf16
+    if bf16:
+        # bf16 generator: z / y widened exactly into fp32 scratch rows, the output BN's parameters copied to fp32 (exact)
+        zf, yf = torch.empty((N, cond_dim - sdim), **f32), torch.empty((N, sdim), **f32)
+        obn32 = [torch.empty(obn.channels, **f32) for _ in range(4)]          # gain, bias, stored_mean, stored_var
+        self.keepalive += [zf, yf] + obn32
 
     def refresh_tables():
         # weight relayout only (concatenation / row permutation), rebuilt when a parameter changes
@@ -291,21 +297,31 @@ def build_biggan(self, model):
         # first Linear emits NCHW-ordered features (c, h, w); permute its rows so it writes NHWC directly
         w0.copy_(linear.weight.detach().view(c0, bw, bw, cond_dim).permute(1, 2, 0, 3).reshape(-1, cond_dim))
         b0.copy_(linear.bias.detach().view(c0, bw, bw).permute(1, 2, 0).reshape(-1))
+        if bf16:
+            obn_ = self.get(obn_ref)
+            for dst, src in zip(obn32, (obn_.gain, obn_.bias, obn_.stored_mean, obn_.stored_var)):
+                dst.copy_(src.detach())
     if torch.device(dev).type != "meta":
         self.refreshers.append(refresh_tables)
 
     def prologue(st, self=self):
         obn = self.get(obn_ref)
         # y = cat([shared(labels), z], 1); all cBN gains/biases in two GEMVs; fold with the stored statistics
-        check(lib.ptx_copy2d(self.in_ptr2, _ptr(cond), N, sdim, sdim, cond_dim, st), "cond.y")
-        check(lib.ptx_copy2d(self.in_ptr, _ptr(cond, sdim), N, cond_dim - sdim, cond_dim - sdim, cond_dim, st), "cond.z")
+        if bf16:        # bf16 z / y: widened into fp32 rows first (exact), then the same copies
+            check(lib.ptx_bf16_to_f32(self.in_ptr2, _ptr(yf), N * sdim, st), "cond.y bf16")
+            check(lib.ptx_bf16_to_f32(self.in_ptr, _ptr(zf), N * (cond_dim - sdim), st), "cond.z bf16")
+            src_y, src_z = _ptr(yf), _ptr(zf)
+        else:
+            src_y, src_z = self.in_ptr2, self.in_ptr
+        check(lib.ptx_copy2d(src_y, _ptr(cond), N, sdim, sdim, cond_dim, st), "cond.y")
+        check(lib.ptx_copy2d(src_z, _ptr(cond, sdim), N, cond_dim - sdim, cond_dim - sdim, cond_dim, st), "cond.z")
         check(lib.ptx_linear_fwd(_ptr(cond), _ptr(wg), None, _ptr(gain_all), N, cond_dim, tot, cond_dim, tot, 0, st), "cbn.gain")
         check(lib.ptx_linear_fwd(_ptr(cond), _ptr(wb), None, _ptr(bias_all), N, cond_dim, tot, cond_dim, tot, 0, st), "cbn.bias")
         check(lib.ptx_cbn_fold(_ptr(gain_all), _ptr(bias_all), _ptr(mean_all), _ptr(var_all), C.c_float(eps),
                                _ptr(scale_all), _ptr(shift_all), N, tot, tot, tot, tot, 1, st), "cbn.fold")
-        check(lib.ptx_cbn_fold(_ptr(obn.gain.detach()), _ptr(obn.bias.detach()), _ptr(obn.stored_mean),
-                               _ptr(obn.stored_var), C.c_float(eps), _ptr(oscale), _ptr(oshift), N, obn.channels, 0, 0,
-                               obn.channels, 0, st), "bn.fold")
+        og, ob, om, ov = obn32 if bf16 else (obn.gain.detach(), obn.bias.detach(), obn.stored_mean, obn.stored_var)
+        check(lib.ptx_cbn_fold(_ptr(og), _ptr(ob), _ptr(om), _ptr(ov), C.c_float(eps), _ptr(oscale), _ptr(oshift), N,
+                               obn.channels, 0, 0, obn.channels, 0, st), "bn.fold")
     self.steps.append(prologue)
 
     h = self.act(N, 1, bw, bw, c0)
@@ -315,15 +331,16 @@ def build_biggan(self, model):
                                  0, st), "linear")
     self.steps.append(first_linear)
 
-    half = getattr(model, "precision", "fp32") == "fp16"      # fp16 operands for every conv behind a cBN pass
+    # fp16 operands for every conv behind a cBN pass; `precision` governs fp32-parameter generators only
+    half = not bf16 and getattr(model, "precision", "fp32") == "fp16"
     self.half_plan = half
 
     def affine(x, sc, sh, ld_s, up, act=1, f16_out=None):
-        f16_out = (half and act == 1) if f16_out is None else f16_out
+        f16_out = ((half or bf16) and act == 1) if f16_out is None else f16_out
         y = self.act(N, 1, x.H * up, x.W * up, x.C, f16=f16_out)
         xp, yp, H_, W_, C_, ldx, ldy = _ptr(x.t), C.c_void_p(y.t.data_ptr()), x.H, x.W, x.C, x.ld, y.ld
         if f16_out:
-            act |= PTX_ACT_OUT_F16
+            act |= PTX_ACT_OUT_BF16 if bf16 else PTX_ACT_OUT_F16
 
         def step(st):
             check(lib.ptx_affine_act_upsample(xp, yp, sc, sh, ld_s, N, H_, W_, C_, ldx, ldy, up, act, st),
@@ -337,6 +354,8 @@ def build_biggan(self, model):
         return affine(x, _ptr(scale_all, o), _ptr(shift_all, o), tot, up)
 
     one, zero = (1, 1, 1), (0, 0, 0)
+    if bf16:
+        return _biggan_bf16_stages(self, model, h, cbn, offs, scale_all, shift_all, tot, oscale, oshift)
     if half:
         return _biggan_fp16_stages(self, model, h, cbn, affine, offs, scale_all, shift_all, tot, oscale, oshift)
     for si, stage in enumerate(model.blocks):
@@ -522,6 +541,76 @@ def _biggan_fp16_stages(self, model, h, cbn, affine, offs, scale_all, shift_all,
     self.feat = self.conv(xa, self.pack(model.output_layer[2], None, f16=True), one, (0, 1, 1), tanh=True,
                           label="output_layer.2")
     self.pooled = None
+
+def _biggan_bf16_stages(self, model, h, cbn, offs, scale_all, shift_all, tot, oscale, oshift):
+    """bf16 generator (parameters torch.bfloat16): every conv on bf16 operands with fp32 accumulation, every activation bf16
+    except the first linear's fp32 output.  One flow serves every generator -- bf16 keeps fp32's exponent range, so the
+    folded cBN tables, the attention logits and the skip sums cannot overflow and nothing needs a range guard:
+      * the first cBN1 + ReLU is ptx_affine_act_upsample with PTX_ACT_OUT_BF16 (fp32 in, one rounding);
+      * every conv's epilogue runs bias, skip, the NEXT cBN's affine and ReLU / tanh in fp32 and rounds each output once;
+        a block's last conv writes both what the next block reads (the activated map and the raw sum, PTX_EPI_DUAL_RAW);
+      * the nearest 2x upsample ahead of a block's first 3x3 conv is that conv's loader (PTX_PRO_UP2);
+      * self-attention: theta | phi | g as one conv on 8-channel aligned slices, exact bf16 2 x 2 max pools, one
+        ptx_nonlocal_bf16_fwd (softmax), and `o` * gamma + x + the next cBN1 + ReLU (or the output BN + ReLU) as one conv;
+      * the image conv applies tanh and writes bf16.
+    The 3x3 convs and the skip-adding 1x1 convs run on the patch-resident bf16 kernels where they apply (Plan.conv)."""
+    one, zero = (1, 1, 1), (0, 0, 0)
+    flat = [(si, bi, blk) for si, stage in enumerate(model.blocks) for bi, blk in enumerate(stage)]
+    obn = model.output_layer[0]
+    otab = (_ptr(oscale), _ptr(oshift), obn.channels)
+    self.gen_patch = True                        # Plan.conv: the generator-stage patch kernels apply to this plan
+
+    def tab(bn):
+        o = offs[id(bn)]
+        return (_ptr(scale_all, o), _ptr(shift_all, o), tot)
+
+    xa, xr = cbn(h, flat[0][2].bn1), h           # activated input of the first block (bf16), its skip operand (fp32)
+    for k, (si, bi, blk) in enumerate(flat):
+        name = "blocks.%d.%d" % (si, bi)
+        nxt = flat[k + 1][2] if k + 1 < len(flat) else None
+        if blk.kind != "gblock":
+            if nxt is not None and nxt.kind != "gblock":
+                raise PtxError("%s: two attention blocks in a row are not a BigGAN-deep layout" % name)
+            xa, xr = biggan_attention_bf16(self, xr, blk, name, tab(nxt.bn1) if nxt is not None else otab, nxt is None)
+            continue
+        up = bool(blk.upsample)
+        t = self.conv(xa, self.pack(blk.conv1, None), one, zero, relu=True, affine=tab(blk.bn2), label=name + ".conv1")
+        t = self.conv(t, self.pack(blk.conv2, None), one, (0, 1, 1), relu=True, affine=tab(blk.bn3), up2=up,
+                      label=name + ".conv2")
+        t = self.conv(t, self.pack(blk.conv3, None), one, (0, 1, 1), relu=True, affine=tab(blk.bn4), label=name + ".conv3")
+        skip = dict(res=xr) if (not up and blk.in_channels == blk.out_channels) else \
+            dict(res=xr, res_kind="up", res_stride=(0, int(up), int(up)))
+        if nxt is None:                          # last block: the output layer's BN + ReLU in the epilogue
+            xa, xr = self.conv(t, self.pack(blk.conv4, None), one, zero, relu=True, affine=otab, label=name + ".conv4",
+                               **skip), None
+        elif nxt.kind == "gblock":               # next block's cBN1 + ReLU, plus the raw sum for its skip
+            xa, xr = self.conv(t, self.pack(blk.conv4, None), one, zero, relu=True, affine=tab(nxt.bn1), raw=True,
+                               label=name + ".conv4", **skip)
+        else:                                    # attention next: the raw sum only
+            xa, xr = None, self.conv(t, self.pack(blk.conv4, None), one, zero, label=name + ".conv4", **skip)
+    self.feat = self.conv(xa, self.pack(model.output_layer[2], None), one, (0, 1, 1), tanh=True, label="output_layer.2")
+    self.pooled = None
+
+
+def biggan_attention_bf16(self, x, att, name, next_affine, last):
+    """layers.Attention in a bf16 plan, on the bf16 raw map x: returns (relu(next affine(out)), out) -- the raw sum is not
+    kept when the block is the network's last (`last`: next_affine is the output layer's BN).  theta / phi / g are ONE
+    conv whose slices start on 8-channel boundaries (zero rows between them), so every attention operand is a 16-byte
+    aligned bf16 slice whose pad channels are zero."""
+    c8, c2 = att.ch // 8, att.ch // 2
+    p8 = _r8(c8)
+    one, zero, win = (1, 1, 1), (0, 0, 0), (1, 2, 2)
+    tpg = self.conv(x, self.pack([att.theta, att.phi, att.g], None, pad8=True), one, zero, label=name + ".theta_phi_g")
+    th, ph, g = tpg.slice(0, c8), tpg.slice(p8, c8), tpg.slice(2 * p8, c2)
+    ph = self.maxpool(ph, win, win, zero, y=self.pool_target(ph, win))
+    g = self.maxpool(g, win, win, zero, y=self.pool_target(g, win))
+    yatt = self.act(x.N, 1, x.H, x.W, c2, f16=True)
+    self.attention_bf16(th, ph, g, yatt)
+    pko = self.pack(att.o, None, scale=(att, "gamma"))
+    if last:
+        return self.conv(yatt, pko, one, zero, relu=True, affine=next_affine, res=x, label=name + ".o"), None
+    return self.conv(yatt, pko, one, zero, relu=True, affine=next_affine, raw=True, res=x, label=name + ".o")
+
 
 def _rgb_conv_ok(self, channels, x=None, conv=None, ld_aff=0):
     """The generator's image conv has its own kernel for C in {32, 64, 128} (ptx_rgb_conv3x3_f16_fwd); PTX_RGB_CONV=0 keeps
