@@ -419,6 +419,31 @@ int ptx_fold_kw_frames_u8(const uint8_t* frames, float* y, int32_t N, int32_t C,
                           int32_t W, int32_t frame_step, int32_t T_full, int32_t kW, int32_t sW, int32_t pW,
                           int32_t Wo, int32_t ld, const ptx_norm_desc* norm, ptx_stream_t stream);
 
+/* The other half of TransformImage (transforms/utils.py:53-64: Resize, CenterCrop) on the device: bilinear resize +
+ * crop (+ flip) of uint8 frames, bit-exact with PIL's 8-bit resampling.  PIL works in integers: per axis every output
+ * index has a first input index lo, a tap count n and n coefficients of 2^22 fixed point; the horizontal pass runs
+ * first, its result is rounded to uint8, then the vertical pass:  out = clip8((2^21 + sum_j k[j] * in[lo + j]) >> 22).
+ * The HOST builds the tables (float64, as PIL does) and passes them as DEVICE pointers; crop and flip are folded in
+ * (only the Ho x Wo window has entries).  The builder guarantees 0 <= lo, lo + n <= H (rows) / W (columns) and
+ * n <= taps; the kernel clamps entries to the frame, so a wrong table gives wrong pixels, never a stray access.
+ * frames: [N][T][H][W][C] uint8, C <= 4.  norm is read for the fp32 / bf16 outputs only (may be NULL for uint8).   */
+#define PTX_RESIZE_OUT_U8 0   /* y: uint8 [N][T][Ho][Wo][C], resized + cropped only                          */
+#define PTX_RESIZE_OUT_F32 1  /* y: fp32  [N][C][T][Ho][Wo], normalised with *norm as ptx_frames_u8_to_ncdhw */
+#define PTX_RESIZE_OUT_BF16 2 /* y: bf16  [N][C][T][Ho][Wo], that fp32 value rounded once (nearest even)     */
+#define PTX_RESIZE_MAX_TAPS 64 /* per axis: down-scales up to about 31x                                      */
+typedef struct ptx_resize_desc {
+    int32_t N, T, H, W, C;   /* input frames                                       */
+    int32_t Ho, Wo;          /* output window (rows / columns that have entries)   */
+    int32_t taps_h, taps_w;  /* row pitch of row_k / col_k (>= every n)            */
+    int32_t out_mode;        /* PTX_RESIZE_OUT_*                                   */
+} ptx_resize_desc;
+/* 1 if ptx_resize_frames_u8 runs this problem (extents, taps <= PTX_RESIZE_MAX_TAPS, the on-chip staging fits) */
+int ptx_resize_frames_u8_supported(const ptx_resize_desc* desc);
+int ptx_resize_frames_u8(const ptx_resize_desc* desc, const uint8_t* frames,
+                         const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, /* [Ho], [Ho], [Ho][taps_h] */
+                         const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, /* [Wo], [Wo], [Wo][taps_w] */
+                         void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * Pooling and head.
  * ------------------------------------------------------------------------------------------ */

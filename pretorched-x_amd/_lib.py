@@ -94,6 +94,14 @@ class NormDesc(C.Structure):
         return d
 
 
+class ResizeDesc(C.Structure):
+    """ptx_resize_desc: bilinear resize + crop of uint8 frames through host-built coefficient tables (PIL's arithmetic)."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "H", "W", "C", "Ho", "Wo", "taps_h", "taps_w", "out_mode")]
+
+
+PTX_RESIZE_OUT_U8, PTX_RESIZE_OUT_F32, PTX_RESIZE_OUT_BF16 = 0, 1, 2
+PTX_RESIZE_MAX_TAPS = 64
+
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
 
@@ -188,6 +196,8 @@ SIGNATURES = {
     "ptx_pad_rows": (C.c_int, [_P, _P, _L, _I, _I, _P]),
     "ptx_frames_u8_to_ncdhw": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, C.POINTER(NormDesc), _P]),
     "ptx_fold_kw_frames_u8": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(NormDesc), _P]),
+    "ptx_resize_frames_u8_supported": (C.c_int, [C.POINTER(ResizeDesc)]),
+    "ptx_resize_frames_u8": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
     "ptx_maxpool3d_fwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P]),
     "ptx_cbn_fold": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ptx_affine_act_upsample": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

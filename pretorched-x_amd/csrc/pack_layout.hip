@@ -268,6 +268,274 @@ __global__ void __launch_bounds__(256) fold_kw_frames_u8_kernel(const unsigned c
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// uint8 frames [N][T][H][W][C] -> bilinear resize + crop (+ flip), bit-exact with PIL's 8-bit resampling
+// (TransformImage's PIL half, utils.py:53-64).  The host builds PIL's fixed-point tables (per output index: first
+// input index, tap count, 2^22-scaled coefficients), with crop and flip folded in; this kernel is integer work only:
+//   horizontal pass -> uint8 intermediate -> vertical pass,  out = clip8((2^21 + sum k[j] * in[lo + j]) >> 22).
+// One workgroup per (frame, band of output rows).  It copies the tables it needs to LDS (entries clamped to the frame;
+// the coefficients too when they fit), then each wave stages one referenced input row at a time in LDS (only the
+// column span the column table references; 16-byte loads between a byte head and tail, LDS offset = global address
+// mod 16 so both sides stay aligned; the next row is already on its way in registers), resamples it into the band's
+// uint8 intermediate image in LDS, and after a barrier the vertical pass reads that image and writes either the
+// interleaved uint8 rows or the normalised planes (normalise_u8: FramesToTensor's operations) with 16-byte stores.
+// If a band references more rows than the intermediate holds (the host sizes bands so it does not), the band is done
+// in several chunks.
+// Table entries are clamped to the frame: a wrong table gives wrong pixels, never a stray access.
+// ---------------------------------------------------------------------------------------------
+constexpr int kResizeBand = 16;                 // output rows per workgroup (fewer when the LDS image would not fit)
+constexpr int kResizeLdsCap = 64 * 1024;
+constexpr int kResizeBits = 22;                 // PIL's PRECISION_BITS for 8-bit channels
+
+struct ResizePlan {
+    int band, lds_rows, stage_stride, istride, vec_store;
+    int k_in_lds, k_off, stage_off;          // coefficient tables copied to LDS (when they fit); byte offsets of the carves
+    size_t lds_bytes;
+};
+
+__device__ __forceinline__ void resize_entry(const int* __restrict__ lo_t, const int* __restrict__ n_t, int i, int extent,
+                                             int taps, int& lo, int& n) {
+    lo = min(max(lo_t[i], 0), extent - 1);
+    n = min(max(n_t[i], 0), min(taps, extent - lo));
+}
+
+__device__ __forceinline__ int clip8(int v) { return min(max(v, 0), 255); }
+
+// The bytes [off, end) of input row `row` that the column table references, relative to the 16-byte aligned address g:
+// a byte head [off, vb), 16-byte pieces [vb, ve), a byte tail [ve, end).  g itself may lie before the row: only
+// [off, end) is dereferenced.
+__device__ __forceinline__ const unsigned char* resize_row_span(const unsigned char* fin, int row, int W, int cmin, int C,
+                                                                int span_bytes, int& off, int& vb, int& ve, int& end) {
+    const unsigned char* src = fin + ((size_t)row * W + cmin) * C;
+    off = (int)(reinterpret_cast<uintptr_t>(src) & 15);
+    end = off + span_bytes;
+    vb = min((off + 15) & ~15, end);
+    ve = max(vb, end & ~15);
+    return src - off;
+}
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+struct ResizeRow {               // one lane's share of the first 3 KiB of a row, on its way from HBM to LDS
+    u32x4 v0, v1, v2;
+    unsigned head, tail;
+};
+
+__device__ __forceinline__ void resize_fetch_row(ResizeRow& r, int i, int nrows, const unsigned char* fin, int lo0, int W,
+                                                 int cmin, int C, int span_bytes, int lane) {
+    if (i >= nrows) return;
+    int off, vb, ve, end;
+    const unsigned char* g = resize_row_span(fin, lo0 + i, W, cmin, C, span_bytes, off, vb, ve, end);
+    if (lane < vb - off) r.head = g[off + lane];
+    if (vb + lane * 16 < ve) r.v0 = *reinterpret_cast<const u32x4*>(g + vb + lane * 16);
+    if (vb + (64 + lane) * 16 < ve) r.v1 = *reinterpret_cast<const u32x4*>(g + vb + (64 + lane) * 16);
+    if (vb + (128 + lane) * 16 < ve) r.v2 = *reinterpret_cast<const u32x4*>(g + vb + (128 + lane) * 16);
+    if (lane < end - ve) r.tail = g[ve + lane];
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d, const unsigned char* __restrict__ f,
+                                                               const int* __restrict__ row_lo, const int* __restrict__ row_n,
+                                                               const int* __restrict__ row_k, const int* __restrict__ col_lo,
+                                                               const int* __restrict__ col_n, const int* __restrict__ col_k,
+                                                               void* __restrict__ y, ptx_norm_desc nd, ResizePlan pl) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char resize_smem[];
+    int* hdr = reinterpret_cast<int*>(resize_smem);                 // [0] first, [1] one-past-last referenced column
+    int* t_clo = hdr + 4;                                           // clamped table entries: columns [Wo], [Wo] ...
+    int* t_cn = t_clo + d.Wo;
+    int* t_rlo = t_cn + d.Wo;                                       // ... and this band's rows [kResizeBand], [kResizeBand]
+    int* t_rn = t_rlo + kResizeBand;
+    int* t_k = reinterpret_cast<int*>(resize_smem + pl.k_off);      // col_k [Wo][taps_w], then the band's row_k [band][taps_h]
+    unsigned char* stage = resize_smem + pl.stage_off;              // [4 waves][stage_stride]: one input row segment each
+    unsigned char* inter = stage + 4 * pl.stage_stride;             // [lds_rows][istride]: horizontally resampled rows
+    const int bands = (d.Ho + pl.band - 1) / pl.band;
+    const int wg = xcd_remap((int)blockIdx.x, (int)gridDim.x);      // neighbouring bands share halo rows: same L2
+    const int frame = wg / bands;
+    const int y0 = (wg - frame * bands) * pl.band, y1 = min(y0 + pl.band, d.Ho);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int WoC = d.Wo * C, istride = pl.istride;
+    const int half = 1 << (kResizeBits - 1);
+    const unsigned char* fin = f + (size_t)frame * d.H * d.W * C;
+
+    if (tid == 0) {
+        hdr[0] = d.W;
+        hdr[1] = 0;
+    }
+    __syncthreads();
+    {
+        int cmin = d.W, cmax = 0;
+        for (int x = tid; x < d.Wo; x += 256) {
+            int lo, n;
+            resize_entry(col_lo, col_n, x, d.W, d.taps_w, lo, n);
+            t_clo[x] = lo;
+            t_cn[x] = n;
+            cmin = min(cmin, lo);
+            cmax = max(cmax, lo + n);
+        }
+        atomicMin(&hdr[0], cmin);
+        atomicMax(&hdr[1], cmax);
+        for (int i = tid; i < y1 - y0; i += 256) {
+            int lo, n;
+            resize_entry(row_lo, row_n, y0 + i, d.H, min(d.taps_h, pl.lds_rows), lo, n);
+            t_rlo[i] = lo;
+            t_rn[i] = n;
+        }
+        if (pl.k_in_lds) {
+            const int nck = d.Wo * d.taps_w, nrk = (y1 - y0) * d.taps_h;
+            for (int i = tid; i < nck; i += 256) t_k[i] = col_k[i];
+            for (int i = tid; i < nrk; i += 256) t_k[nck + i] = row_k[(size_t)y0 * d.taps_h + i];
+        }
+    }
+    __syncthreads();
+    const int* ck = pl.k_in_lds ? t_k : col_k;                                            // [Wo][taps_w]
+    const int* rk = pl.k_in_lds ? t_k + d.Wo * d.taps_w : row_k + (size_t)y0 * d.taps_h;  // [y1 - y0][taps_h]
+    const int cmin = hdr[0];
+    const int span_bytes = max(hdr[1] - cmin, 0) * C;               // <= W * C
+
+    int r = y0;
+    while (r < y1) {
+        // the chunk [r, r1) of output rows whose referenced input rows [lo0, hi0) fit the intermediate image
+        int lo0 = t_rlo[r - y0];
+        int hi0 = lo0 + t_rn[r - y0], r1 = r + 1;
+        while (r1 < y1) {
+            const int lo = t_rlo[r1 - y0], n = t_rn[r1 - y0];
+            const int l2 = min(lo0, lo), h2 = max(hi0, lo + n);
+            if (h2 - l2 > pl.lds_rows) break;
+            lo0 = l2;
+            hi0 = h2;
+            ++r1;
+        }
+        const int nrows = hi0 - lo0;
+
+        // horizontal pass: wave w resamples input rows lo0 + w, lo0 + w + 4, ...  The next row's bytes are fetched into
+        // registers (3 x 1 KiB per wave; wider rows copy the rest when the row is staged) before the current
+        // row is resampled, so the HBM latency hides under the LDS work instead of adding to every row.
+        unsigned char* sw = stage + wave * pl.stage_stride;
+        ResizeRow pre = {};
+        resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
+        for (int i0 = 0; i0 < nrows; i0 += 4) {
+            const int i = i0 + wave;
+            int off = 0;
+            if (i < nrows) {
+                int vb, ve, end;
+                const unsigned char* g = resize_row_span(fin, lo0 + i, d.W, cmin, C, span_bytes, off, vb, ve, end);
+                if (lane < vb - off) sw[off + lane] = (unsigned char)pre.head;
+                if (vb + lane * 16 < ve) *reinterpret_cast<u32x4*>(sw + vb + lane * 16) = pre.v0;
+                if (vb + (64 + lane) * 16 < ve) *reinterpret_cast<u32x4*>(sw + vb + (64 + lane) * 16) = pre.v1;
+                if (vb + (128 + lane) * 16 < ve) *reinterpret_cast<u32x4*>(sw + vb + (128 + lane) * 16) = pre.v2;
+                for (int v = vb + (192 + lane) * 16; v < ve; v += 64 * 16)
+                    *reinterpret_cast<uint4*>(sw + v) = *reinterpret_cast<const uint4*>(g + v);
+                if (lane < end - ve) sw[ve + lane] = (unsigned char)pre.tail;
+            }
+            __syncthreads();
+            resize_fetch_row(pre, i + 4, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
+            if (i < nrows) {
+                for (int x = lane; x < d.Wo; x += 64) {
+                    const int lo = t_clo[x], n = t_cn[x];
+                    const unsigned char* p = sw + off + (lo - cmin) * C;
+                    const int* kk = ck + x * d.taps_w;
+                    int acc[C];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) acc[c] = half;
+#pragma unroll 4
+                    for (int j = 0; j < n; ++j) {
+                        const int k = kk[j];
+#pragma unroll
+                        for (int c = 0; c < C; ++c) acc[c] += __mul24(k, (int)p[j * C + c]);
+                    }
+#pragma unroll
+                    for (int c = 0; c < C; ++c) inter[i * istride + x * C + c] = (unsigned char)clip8(acc[c] >> kResizeBits);
+                }
+            }
+        }
+        __syncthreads();
+
+        // vertical pass over output rows [r, r1)
+        const int nout = r1 - r;
+        if (d.out_mode == PTX_RESIZE_OUT_U8) {
+            unsigned char* yo = static_cast<unsigned char*>(y);
+            const int q4 = istride / 4;                              // 4 interleaved bytes per thread
+            for (int it = tid; it < nout * q4; it += 256) {
+                const int yy = it / q4, q = it - yy * q4, row = r + yy;
+                const int lo = t_rlo[row - y0], n = t_rn[row - y0];
+                const unsigned char* p = inter + (lo - lo0) * istride + q * 4;
+                const int* kk = rk + (row - y0) * d.taps_h;
+                int acc[4] = {half, half, half, half};
+                for (int j = 0; j < n; ++j) {
+                    const int k = kk[j];
+                    const unsigned v = *reinterpret_cast<const unsigned*>(p + j * istride);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[e] += __mul24(k, (int)((v >> (8 * e)) & 255u));
+                }
+                // coefficients and pixels are >= 0, so the sums are too: clamp with an unsigned shift + min.  (The signed
+                // clamp of two neighbouring sums is selected as one v_ashr_pk_u8_i32, whose result hipcc then ORs with
+                // the other two bytes as if its upper half were zero; on gfx950 that upper half came back non-zero.)
+                unsigned o = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o |= min((unsigned)acc[e] >> kResizeBits, 255u) << (8 * e);
+                unsigned char* ob = yo + ((size_t)frame * d.Ho + row) * WoC + q * 4;
+                if (pl.vec_store) {
+                    *reinterpret_cast<unsigned*>(ob) = o;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (q * 4 + e < WoC) ob[e] = (unsigned char)(o >> (8 * e));
+                }
+            }
+        } else {
+            const int Wg = (d.Wo + 3) / 4;                           // 4 pixels of one plane row per thread
+            const int n_ = frame / d.T, t = frame - n_ * d.T;
+            for (int it = tid; it < nout * C * Wg; it += 256) {
+                const int xg = it % Wg, t2 = it / Wg;
+                const int c = t2 % C, row = r + t2 / C;
+                const int cin = (nd.swap_rb && (c == 0 || c == 2)) ? 2 - c : c;
+                const int lo = t_rlo[row - y0], n = t_rn[row - y0];
+                const unsigned char* p = inter + (lo - lo0) * istride + cin;
+                const int* kk = rk + (row - y0) * d.taps_h;
+                int xo[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xo[e] = min(xg * 4 + e, d.Wo - 1) * C;
+                int acc[4] = {half, half, half, half};
+                for (int j = 0; j < n; ++j) {
+                    const int k = kk[j];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[e] += __mul24(k, (int)p[j * istride + xo[e]]);
+                }
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    v[e] = normalise_u8((unsigned char)clip8(acc[e] >> kResizeBits), nd.mean[c], nd.std[c], nd.to_255);
+                const size_t o = ((((size_t)n_ * C + c) * d.T + t) * d.Ho + row) * d.Wo + (size_t)xg * 4;
+                if (d.out_mode == PTX_RESIZE_OUT_F32) {
+                    float* yo = static_cast<float*>(y) + o;
+                    if (pl.vec_store) {
+                        f32x4 q = {v[0], v[1], v[2], v[3]};
+                        *reinterpret_cast<f32x4*>(yo) = q;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (xg * 4 + e < d.Wo) yo[e] = v[e];
+                    }
+                } else {
+                    __bf16* yo = static_cast<__bf16*>(y) + o;
+                    unsigned short b[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) b[e] = __builtin_bit_cast(unsigned short, (__bf16)v[e]);   // nearest even
+                    if (pl.vec_store) {
+                        uint2 q = {(unsigned)b[0] | ((unsigned)b[1] << 16), (unsigned)b[2] | ((unsigned)b[3] << 16)};
+                        *reinterpret_cast<uint2*>(yo) = q;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (xg * 4 + e < d.Wo) reinterpret_cast<unsigned short*>(yo)[e] = b[e];
+                    }
+                }
+            }
+        }
+        __syncthreads();                                             // the next chunk overwrites the intermediate image
+        r = r1;
+    }
+}
+
 static unsigned grid_for(size_t work_items) {
     size_t b = (work_items + 255) / 256;
     const size_t cap = (size_t)kNumCU * 8;
@@ -628,6 +896,89 @@ extern "C" int ptx_fold_kw_frames_u8(const uint8_t* frames, float* y, int32_t N,
     hipLaunchKernelGGL(fold_kw_frames_u8_kernel, dim3((unsigned)(N * T * H)), dim3(256), (size_t)C * W * sizeof(float),
                        (hipStream_t)stream, frames, y, C, T, H, W, frame_step, T_full, kW, sW, pW, Wo, ld, *norm);
     return hip_check(hipGetLastError(), "fold_kw_frames_u8 launch");
+}
+
+// Launch shape of resize_frames_u8_kernel, or the reason there is none.  taps_h is the widest row's tap count, and a
+// row of support s has more than 2 s - 1 taps, so output rows advance by at most taps_h / 2 input rows: a band of b
+// output rows references at most b * taps_h / 2 + taps_h + 1 input rows (b when taps_h == 1: the axis is not resampled).
+static int resize_plan(const ptx_resize_desc* d, const void* y, ResizePlan* p, const char* who) {
+    if (!d) return fail(PTX_ERR_INVALID, "%s: null descriptor", who);
+    if (d->N <= 0 || d->T <= 0 || d->H <= 0 || d->W <= 0 || d->Ho <= 0 || d->Wo <= 0)
+        return fail(PTX_ERR_INVALID, "%s: non-positive extent (N=%d T=%d H=%d W=%d Ho=%d Wo=%d)", who, d->N, d->T, d->H, d->W,
+                    d->Ho, d->Wo);
+    if (d->C <= 0 || d->C > 4) return fail(PTX_ERR_INVALID, "%s: C=%d must be 1..4", who, d->C);
+    if (d->taps_h <= 0 || d->taps_w <= 0) return fail(PTX_ERR_INVALID, "%s: taps_h=%d taps_w=%d must be positive", who, d->taps_h, d->taps_w);
+    if (d->out_mode != PTX_RESIZE_OUT_U8 && d->out_mode != PTX_RESIZE_OUT_F32 && d->out_mode != PTX_RESIZE_OUT_BF16)
+        return fail(PTX_ERR_INVALID, "%s: out_mode=%d is not a PTX_RESIZE_OUT_* value", who, d->out_mode);
+    if (d->taps_h > PTX_RESIZE_MAX_TAPS || d->taps_w > PTX_RESIZE_MAX_TAPS)
+        return fail(PTX_ERR_UNSUPPORTED, "%s: taps_h=%d taps_w=%d exceed PTX_RESIZE_MAX_TAPS=%d", who, d->taps_h, d->taps_w,
+                    PTX_RESIZE_MAX_TAPS);
+    const int64_t lim = INT32_MAX;
+    if ((int64_t)d->H * d->W * d->C > lim || (int64_t)d->Ho * d->Wo * d->C > lim || (int64_t)d->Ho * d->taps_h > lim ||
+        (int64_t)d->Wo * d->taps_w > lim || (int64_t)d->N * d->T > lim)
+        return fail(PTX_ERR_UNSUPPORTED, "%s: a frame or a table exceeds 32-bit indexing", who);
+    p->stage_stride = ((d->W * d->C + 15) & ~15) + 16;
+    p->istride = (d->Wo * d->C + 3) & ~3;
+    auto rows_of = [&](int b) { return d->taps_h > 1 ? (b * d->taps_h + 1) / 2 + d->taps_h + 1 : b; };
+    // LDS carves: header + clamped lo / n entries, [the coefficient tables], 4 row stages, the intermediate image.  The
+    // coefficients stay in global memory (L2) when copying them would leave no room for a band of 8 rows.
+    const int64_t entries = 16 + (((2 * (int64_t)d->Wo + 2 * kResizeBand) * 4 + 15) & ~(int64_t)15);
+    const int64_t coeffs = (((int64_t)d->Wo * d->taps_w + (int64_t)kResizeBand * d->taps_h) * 4 + 15) & ~(int64_t)15;
+    const int64_t stages = 4 * (int64_t)p->stage_stride;
+    p->k_in_lds = entries + coeffs + stages + (int64_t)rows_of(std::min(8, d->Ho)) * p->istride <= kResizeLdsCap;
+    const int64_t fixed = entries + (p->k_in_lds ? coeffs : 0) + stages;
+    if (fixed + (int64_t)d->taps_h * p->istride > kResizeLdsCap)
+        return fail(PTX_ERR_UNSUPPORTED, "%s: W=%d, Wo=%d, taps_h=%d need %lld bytes of LDS staging (cap %d)", who, d->W, d->Wo,
+                    d->taps_h, (long long)(fixed + (int64_t)d->taps_h * p->istride), kResizeLdsCap);
+    p->k_off = (int)entries;
+    p->stage_off = (int)(entries + (p->k_in_lds ? coeffs : 0));
+    const int max_rows = (int)((kResizeLdsCap - fixed) / p->istride);
+    int band = std::min(kResizeBand, d->Ho);
+    while (band > 1 && rows_of(band) > max_rows) --band;
+    p->band = band;
+    p->lds_rows = std::max(std::min(max_rows, rows_of(band)), d->taps_h);
+    p->lds_bytes = (size_t)fixed + (size_t)p->lds_rows * p->istride;
+    if ((int64_t)d->N * d->T * cdiv(d->Ho, band) > lim) return fail(PTX_ERR_UNSUPPORTED, "%s: too many workgroups", who);
+    const uintptr_t ya = reinterpret_cast<uintptr_t>(y);
+    p->vec_store = d->out_mode == PTX_RESIZE_OUT_U8 ? ((d->Wo * d->C) % 4 == 0 && ya % 4 == 0)
+                                                    : (d->Wo % 4 == 0 && ya % (d->out_mode == PTX_RESIZE_OUT_F32 ? 16 : 8) == 0);
+    return PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_u8_supported(const ptx_resize_desc* desc) {
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, "ptx_resize_frames_u8_supported") == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_u8(const ptx_resize_desc* desc, const uint8_t* frames, const int32_t* row_lo,
+                                    const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo, const int32_t* col_n,
+                                    const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream) {
+    const char* who = "ptx_resize_frames_u8";
+    ResizePlan p;
+    int s = resize_plan(desc, y, &p, who);
+    if (s) return s;
+    if (!frames || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k) return fail(PTX_ERR_INVALID, "%s: null pointer", who);
+    ptx_norm_desc nd = {};
+    if (desc->out_mode != PTX_RESIZE_OUT_U8) {
+        if (!norm) return fail(PTX_ERR_INVALID, "%s: null norm descriptor", who);
+        for (int c = 0; c < desc->C; ++c)
+            if (!(norm->std[c] != 0.f)) return fail(PTX_ERR_INVALID, "%s: std[%d] must be non-zero", who, c);
+        if (norm->swap_rb && desc->C < 3) return fail(PTX_ERR_INVALID, "%s: BGR swap needs 3 channels", who);
+        nd = *norm;
+    }
+    const dim3 grid((unsigned)((int64_t)desc->N * desc->T * cdiv(desc->Ho, p.band)));
+    hipStream_t st = (hipStream_t)stream;
+#define PTX_RESIZE_LAUNCH(CH)                                                                                               \
+    hipLaunchKernelGGL(resize_frames_u8_kernel<CH>, grid, dim3(256), p.lds_bytes, st, *desc, frames, row_lo, row_n, row_k, \
+                       col_lo, col_n, col_k, y, nd, p)
+    switch (desc->C) {
+        case 1: PTX_RESIZE_LAUNCH(1); break;
+        case 2: PTX_RESIZE_LAUNCH(2); break;
+        case 3: PTX_RESIZE_LAUNCH(3); break;
+        default: PTX_RESIZE_LAUNCH(4); break;
+    }
+#undef PTX_RESIZE_LAUNCH
+    return hip_check(hipGetLastError(), "ptx_resize_frames_u8 launch");
 }
 
 // y[r][0..W) = x[r][0..W), y[r][W..ld) = 0: gives rows whose length is not a multiple of 4 floats a 16-byte pitch

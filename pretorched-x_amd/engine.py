@@ -2637,11 +2637,16 @@ class Engine:
                           "ptx_ndhwc_to_ncdhw")
         return out
 
-    def forward_frames(self, model, frames, opts=None):
+    def forward_frames(self, model, frames, opts=None, transform=None):
         """Decoded uint8 frames [N,T,H,W,C] (NHWC for 2-D models) -> logits.  The tensor half of the
         reference's TransformImage (ToTensor, ToSpaceBGR, ToRange255, Normalize; transforms/utils.py:72-75)
         is fused into the stem's fold kernel: no fp32 NCDHW clip is ever materialised.  `opts`: anything
-        with mean / std / input_space / input_range (default: the model's own pretrained settings)."""
+        with mean / std / input_space / input_range (default: the model's own pretrained settings).
+        `transform`: a `transforms.TransformFrames(.., out="frames")` applied to the frames first (resize + crop of
+        frames of any size on the device, utils.py:53-64); None: the frames already have the input size."""
+        if transform is not None:
+            from .transforms import apply_frames_transform
+            frames = apply_frames_transform(transform, frames)
         opts = model if opts is None else opts
         get = (lambda k: opts[k]) if isinstance(opts, dict) else (lambda k: getattr(opts, k))
         try:

@@ -96,8 +96,8 @@ class InceptionI3d(EngineOwner, nn.Module):
     def forward(self, input):
         return self._engine.forward(self, input)
 
-    def forward_frames(self, frames, opts):
-        return self._engine.forward_frames(self, frames, opts)
+    def forward_frames(self, frames, opts, transform=None):
+        return self._engine.forward_frames(self, frames, opts, transform)
 
 
 def i3d(num_classes=400, pretrained=None):

@@ -152,9 +152,10 @@ class _Runnable(EngineOwner):
         """[B,3,T,H,W] fp32 CUDA clip -> [B,num_classes]  (dropout is the identity in eval mode)."""
         return self._engine.forward(self, input)
 
-    def forward_frames(self, frames, opts):
-        """Decoded uint8 frames [B,T,H,W,3] -> logits, normalisation fused into the stems."""
-        return self._engine.forward_frames(self, frames, opts)
+    def forward_frames(self, frames, opts, transform=None):
+        """Decoded uint8 frames [B,T,H,W,3] -> logits, normalisation fused into the stems.
+        transform: a `transforms.TransformFrames(.., out="frames")` that resizes + crops the frames first."""
+        return self._engine.forward_frames(self, frames, opts, transform)
 
 
 class SlowFast(_Runnable, nn.Module):

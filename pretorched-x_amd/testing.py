@@ -131,3 +131,18 @@ def synth_clips(batch, frames, size, seed=99, channels=3):
     g = torch.Generator()
     g.manual_seed(int(seed))
     return torch.randn(batch, channels, frames, size, size, generator=g)
+
+
+def synth_frames(count, height, width, seed, content="noise"):
+    """Synthetic decoded frames, uint8 numpy [count, height, width, 3]: seeded noise from numpy's legacy generator (its
+    stream is stable across numpy versions, so fixtures store outputs only) or a smooth integer gradient."""
+    import numpy as np
+    if content == "gradient":
+        y = np.arange(height, dtype=np.int64)[:, None]
+        x = np.arange(width, dtype=np.int64)[None, :]
+        one = np.stack([(x * 255) // max(width - 1, 1) + 0 * y, (y * 255) // max(height - 1, 1) + 0 * x,
+                        ((x + y) * 255) // max(width + height - 2, 1)], -1).astype(np.uint8)
+        return np.stack([np.roll(one, 7 * i, axis=1) for i in range(count)])
+    if content != "noise":
+        raise ValueError("synth_frames: content must be 'noise' or 'gradient'")
+    return np.random.RandomState(int(seed)).randint(0, 256, (count, height, width, 3)).astype(np.uint8)
