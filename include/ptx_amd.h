@@ -444,6 +444,44 @@ int ptx_resize_frames_u8(const ptx_resize_desc* desc, const uint8_t* frames,
                          const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, /* [Wo], [Wo], [Wo][taps_w] */
                          void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
 
+/* Multi-view sampling (test-time evaluation of the video families): clips x crops views of a decoded video in one launch
+ * per range of views.  It replaces, per view, an index_select of the clip's frames plus one TransformImage call per crop
+ * (transforms/utils.py:53-75).  video: uint8, frame t of video n at video + n * stride_n + t * stride_t BYTES, each frame
+ * [H][W][C] contiguous -- frames are read in place through frame_idx [clips][T] (device; entries clamped to [0, Tv)),
+ * no gathered copy is made.  The row / column tables are ptx_resize_frames_u8's, over the UNION of the crop windows: the
+ * sorted distinct rows / columns of the resized frame that any window contains (Ur / Uc entries); window k is the run
+ * [row_off[k], row_off[k] + S) x [col_off[k], col_off[k] + S).  View v = clip * crops + crop; views [v0, v0 + nv) of
+ * every video are written, view v at slot v - v0:
+ *   PTX_RESIZE_OUT_U8: y uint8 [N][nv][T][S][S][C];  _F32 / _BF16: y [N][nv][C][T][S][S], normalised as above.
+ * Per output pixel the arithmetic is ptx_resize_frames_u8's: the result is bit-identical to it on the same frame and
+ * window.  Workgroups resample the union once per sampled frame (share) or one window each, see `share`.              */
+#define PTX_VIEWS_MAX_CROPS 4
+#define PTX_VIEWS_SHARE_AUTO 0   /* shared pass where it measured faster and fits on chip         */
+#define PTX_VIEWS_SHARE_ALWAYS 1 /* shared pass or PTX_ERR_UNSUPPORTED                                              */
+#define PTX_VIEWS_SHARE_NEVER 2  /* one window per workgroup                                                        */
+typedef struct ptx_views_desc {
+    int32_t N, Tv, H, W, C;      /* videos                                                  */
+    int32_t clips, T, crops;     /* frame_idx is [clips][T]; crops <= PTX_VIEWS_MAX_CROPS   */
+    int64_t stride_n, stride_t;  /* bytes between videos / between frames (>= H * W * C)    */
+    int32_t S;                   /* output window: S x S                                    */
+    int32_t Ur, Uc;              /* entries of the union row / column tables                */
+    int32_t taps_h, taps_w;      /* row pitch of row_k / col_k (>= every n)                 */
+    int32_t row_off[PTX_VIEWS_MAX_CROPS], col_off[PTX_VIEWS_MAX_CROPS];
+    int32_t v0, nv;              /* view range                                              */
+    int32_t out_mode;            /* PTX_RESIZE_OUT_*                                        */
+    int32_t share;               /* PTX_VIEWS_SHARE_*                                       */
+} ptx_views_desc;
+/* 0: not runnable (extents, taps, the on-chip staging does not fit); 1: runs one window per workgroup; 2: runs the shared pass */
+int ptx_resize_views_u8_supported(const ptx_views_desc* desc);
+int ptx_resize_views_u8(const ptx_views_desc* desc, const uint8_t* video, const int32_t* frame_idx,
+                        const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, /* [Ur], [Ur], [Ur][taps_h] */
+                        const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, /* [Uc], [Uc], [Uc][taps_w] */
+                        void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+/* View reduction: logits [N * V][K] (fp32, or bf16 when bf16 != 0; row pitch ld elements) -> y fp32 [N][K]: the mean over
+ * the V rows of a video of softmax(row) (mode 0; fp32, max-subtracted) or of the rows themselves (mode 1).  K <= 4096. */
+int ptx_views_mean(const void* logits, float* y, int32_t N, int32_t V, int32_t K, int64_t ld, int32_t bf16,
+                   int32_t mode, ptx_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * Pooling and head.
  * ------------------------------------------------------------------------------------------ */

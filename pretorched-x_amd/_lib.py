@@ -101,6 +101,17 @@ class ResizeDesc(C.Structure):
 
 PTX_RESIZE_OUT_U8, PTX_RESIZE_OUT_F32, PTX_RESIZE_OUT_BF16 = 0, 1, 2
 PTX_RESIZE_MAX_TAPS = 64
+PTX_VIEWS_MAX_CROPS = 4
+PTX_VIEWS_SHARE_AUTO, PTX_VIEWS_SHARE_ALWAYS, PTX_VIEWS_SHARE_NEVER = 0, 1, 2
+
+
+class ViewsDesc(C.Structure):
+    """ptx_views_desc: clips x crops views of a decoded video, sampled through a frame index table and union tables."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "Tv", "H", "W", "C", "clips", "T", "crops")] + \
+               [("stride_n", C.c_int64), ("stride_t", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("S", "Ur", "Uc", "taps_h", "taps_w")] + \
+               [("row_off", C.c_int32 * PTX_VIEWS_MAX_CROPS), ("col_off", C.c_int32 * PTX_VIEWS_MAX_CROPS)] + \
+               [(n, C.c_int32) for n in ("v0", "nv", "out_mode", "share")]
 
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
@@ -198,6 +209,9 @@ SIGNATURES = {
     "ptx_fold_kw_frames_u8": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(NormDesc), _P]),
     "ptx_resize_frames_u8_supported": (C.c_int, [C.POINTER(ResizeDesc)]),
     "ptx_resize_frames_u8": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+    "ptx_resize_views_u8_supported": (C.c_int, [C.POINTER(ViewsDesc)]),
+    "ptx_resize_views_u8": (C.c_int, [C.POINTER(ViewsDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+    "ptx_views_mean": (C.c_int, [_P, _P, _I, _I, _I, _L, _I, _I, _P]),
     "ptx_maxpool3d_fwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P]),
     "ptx_cbn_fold": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ptx_affine_act_upsample": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -662,6 +662,45 @@ __global__ void __launch_bounds__(256) softmax_rows_kernel(float* __restrict__ x
 }
 
 // ---------------------------------------------------------------------------------------------
+// multi-view reduction: logits [N * V][K] (fp32 or bf16 rows of pitch ld) -> fp32 [N][K], the mean over a video's V
+// views of softmax(row) (mode 0; max-subtracted, fp32) or of the raw rows (mode 1).  One workgroup per video: wave w
+// takes views w, w + 4, ... (lane l owns columns l, l + 64, ... of the wave's LDS accumulator, so no two lanes touch
+// one word), then the four partial sums are added in wave order: the result does not depend on scheduling.
+// ---------------------------------------------------------------------------------------------
+template <bool BF16>
+__device__ __forceinline__ float views_load(const void* row, int c) {
+    if (BF16) return __uint_as_float((unsigned)static_cast<const unsigned short*>(row)[c] << 16);
+    return static_cast<const float*>(row)[c];
+}
+
+template <bool BF16>
+__global__ void __launch_bounds__(256) views_mean_kernel(const void* __restrict__ x, float* __restrict__ y, int V, int K,
+                                                         long long ld, int mode) {
+    extern __shared__ float views_acc[];                 // [4][K]
+    const int n = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* acc = views_acc + wave * K;
+    for (int c = lane; c < K; c += 64) acc[c] = 0.f;
+    for (int v = wave; v < V; v += 4) {
+        const void* row = static_cast<const char*>(x) + ((size_t)n * V + v) * (size_t)ld * (BF16 ? 2 : 4);
+        if (mode == 1) {
+            for (int c = lane; c < K; c += 64) acc[c] += views_load<BF16>(row, c);
+            continue;
+        }
+        float mx = -INFINITY;
+        for (int c = lane; c < K; c += 64) mx = fmaxf(mx, views_load<BF16>(row, c));
+        mx = wave_max(mx);
+        float sum = 0.f;
+        for (int c = lane; c < K; c += 64) sum += expf(views_load<BF16>(row, c) - mx);
+        const float inv = 1.0f / wave_sum(sum);
+        for (int c = lane; c < K; c += 64) acc[c] += expf(views_load<BF16>(row, c) - mx) * inv;
+    }
+    __syncthreads();
+    const float inv_v = 1.0f / (float)V;
+    for (int c = threadIdx.x; c < K; c += 256)
+        y[(size_t)n * K + c] = (((views_acc[c] + views_acc[K + c]) + views_acc[2 * K + c]) + views_acc[3 * K + c]) * inv_v;
+}
+
+// ---------------------------------------------------------------------------------------------
 // concat plumbing and temporal window means (tiny, bandwidth bound)
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) copy2d_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total4,
@@ -1103,4 +1142,20 @@ extern "C" int ptx_softmax_rows(float* x, int64_t rows, int32_t cols, int32_t ld
     else
         hipLaunchKernelGGL(softmax_rows_kernel<64>, grid, dim3(256), 0, st, x, (long long)rows, cols, ld, scale_only);
     return hip_check(hipGetLastError(), "softmax launch");
+}
+
+extern "C" int ptx_views_mean(const void* logits, float* y, int32_t N, int32_t V, int32_t K, int64_t ld, int32_t bf16,
+                              int32_t mode, ptx_stream_t stream) {
+    if (!logits || !y) return fail(PTX_ERR_INVALID, "views_mean: null pointer");
+    if (N <= 0 || V <= 0 || K <= 0 || ld < K) return fail(PTX_ERR_INVALID, "views_mean: bad extents (N=%d V=%d K=%d ld=%lld)", N, V, K, (long long)ld);
+    if (mode != 0 && mode != 1) return fail(PTX_ERR_INVALID, "views_mean: mode=%d must be 0 (softmax) or 1 (logits)", mode);
+    if (K > 4096) return fail(PTX_ERR_UNSUPPORTED, "views_mean: K=%d classes exceed 4096 (four fp32 rows in LDS)", K);
+    if ((int64_t)N * V > INT32_MAX) return fail(PTX_ERR_UNSUPPORTED, "views_mean: too many rows");
+    const size_t lds = (size_t)4 * K * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    if (bf16)
+        hipLaunchKernelGGL(views_mean_kernel<true>, dim3((unsigned)N), dim3(256), lds, st, logits, y, V, K, (long long)ld, mode);
+    else
+        hipLaunchKernelGGL(views_mean_kernel<false>, dim3((unsigned)N), dim3(256), lds, st, logits, y, V, K, (long long)ld, mode);
+    return hip_check(hipGetLastError(), "views_mean launch");
 }

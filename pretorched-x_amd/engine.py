@@ -2686,6 +2686,33 @@ class Engine:
             self._maybe_tune(model, plan, frames)
             return self._forward_eager(model, plan, frames)
 
+    def forward_views(self, model, video, opts=None, views=None, reduce="softmax", chunk=None):
+        """Decoded uint8 video [N,Tv,H,W,3] (or [Tv,H,W,3]: one video) -> fp32 [N, classes]: the mean over `views`
+        (a `transforms.SampleViews`: clips x crops, sampled on the device) of softmax(logits) (reduce="softmax"), of the
+        logits ("logits"), or the logits of every view [N, V, classes] in the model's dtype (None).
+        float32 models take the views as uint8 frames through forward_frames (views.out == "frames", `opts` as there);
+        bfloat16 models take the normalised bf16 clip through forward() (views: out="tensor", dtype=torch.bfloat16).
+        Views are produced `chunk` at a time (default `views_chunk(N, V, max_batch)`: as many as the per-launch size
+        limit allows), so only one chunk of views exists at any time."""
+        prec = model_precision(model)
+        if prec not in ("fp32", "bf16"):
+            raise PtxError("forward_views runs float32 and bfloat16 models (this model's parameters are %s)" % prec)
+        check_views(views, model, "frames" if prec == "fp32" else "bf16")
+        if getattr(model.arch, "dims", 3) != 3:
+            raise PtxError("forward_views: a 2-D model takes images, not clips (TRN.forward_views runs a 2-D backbone on the "
+                           "frames of a clip)")
+        S = views.size
+        key = ("maxb", (3, views.num_frames, S, S))
+        with self._lock:
+            mb = self._sig.get(key)
+            if mb is None:
+                mb = self._sig[key] = self.max_batch(model, key[1])
+        if prec == "fp32":
+            run = lambda frames: self.forward_frames(model, frames, opts)
+        else:
+            run = lambda clip: self.forward(model, clip)
+        return run_views(video, views, run, mb, reduce, chunk)
+
     def autotune(self, model, x, iters=3, verbose=False, persist=False, only_untuned=False, plan=None):
         """Time every compiled tile configuration (x a few split-K factors) for each distinct conv
         problem of the plan with HIP events and keep the fastest.  Holds the plan's exclusive lock: the
@@ -3107,6 +3134,73 @@ class Engine:
                 kind = "mem" if nb and not macs else "mfma" if macs else "other"
                 rows.append((getattr(stp, "label", getattr(stp, "__name__", "step")), kind, nb, macs, ms, ""))
         return rows
+
+
+# ---------------------------------------------------------------------------------------------
+# multi-view inference: decoded video -> transforms.SampleViews -> model, chunk by chunk -> ptx_views_mean
+# ---------------------------------------------------------------------------------------------
+def views_chunk(N, V, max_batch):
+    """Views per chunk of forward_views for N videos of V views each: every chunk is N * views_chunk clips, the most
+    that `max_batch` clips allow (at least one view, at most all V)."""
+    return max(1, min(int(V), int(max_batch) // max(int(N), 1)))
+
+
+def views_mean(logits, N, V, mode="softmax"):
+    """[N*V, K] (or [N, V, K]) fp32 / bf16 CUDA logits -> fp32 [N, K]: the mean over a video's views of softmax(row)
+    (mode "softmax") or of the rows (mode "logits"), one ptx_views_mean launch."""
+    if mode not in ("softmax", "logits"):
+        raise PtxError("views_mean: mode must be 'softmax' or 'logits', got %r" % (mode,))
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise PtxError("views_mean: logits must be a float32 or bfloat16 CUDA tensor (no CPU fallback)")
+    K = logits.shape[-1]
+    if logits.numel() != N * V * K or logits.stride(-1) != 1:
+        raise PtxError("views_mean: expected %d x %d rows, got shape %s" % (N, V, tuple(logits.shape)))
+    rows = logits.reshape(N * V, K) if logits.dim() != 2 else logits
+    if rows.shape[0] > 1 and rows.stride(0) < K:
+        rows = rows.contiguous()
+    with torch.cuda.device(logits.device):
+        y = torch.empty((N, K), device=logits.device, dtype=torch.float32)
+        check(_lib.lib().ptx_views_mean(C.c_void_p(rows.data_ptr()), _ptr(y), N, V, K, rows.stride(0) if rows.shape[0] > 1 else K,
+                                        int(logits.dtype == torch.bfloat16), 0 if mode == "softmax" else 1, _stream()),
+              "ptx_views_mean")
+    return y
+
+
+def run_views(video, views, run, max_batch, reduce="softmax", chunk=None, who="forward_views"):
+    """The loop behind every forward_views: `views.sample` produces views [v0, v0 + nv) of every video, `run` turns
+    the N * nv clips into logits, the logits of all chunks land in one [N*V, K] buffer, ptx_views_mean reduces it."""
+    if reduce not in ("softmax", "logits", None):
+        raise PtxError("%s: reduce must be 'softmax', 'logits' or None, got %r" % (who, reduce))
+    if not isinstance(video, torch.Tensor) or video.dim() not in (4, 5):
+        raise PtxError("%s: video must be a uint8 CUDA tensor [N,Tv,H,W,3] or [Tv,H,W,3]" % who)
+    N, V = (video.shape[0] if video.dim() == 5 else 1), views.num_views
+    nv = views_chunk(N, V, max_batch) if chunk is None else chunk
+    if not isinstance(nv, int) or isinstance(nv, bool) or nv < 1:
+        raise PtxError("%s: chunk must be a positive number of views, got %r" % (who, chunk))
+    buf = None
+    for v0 in range(0, V, nv):
+        n = min(nv, V - v0)
+        x = views.sample(video, v0, n)                        # rank 4: [n, ...]; rank 5: [N, n, ...]
+        out = run(x.reshape((N * n,) + tuple(x.shape[-4:])))
+        if not isinstance(out, torch.Tensor) or out.numel() % (N * n) or out.dtype not in (torch.float32, torch.bfloat16):
+            raise PtxError("%s: the model's head must return one float32 / bfloat16 row of logits per clip" % who)
+        out = out.reshape(N, n, -1)
+        if buf is None:
+            buf = torch.empty((N, V, out.shape[-1]), device=out.device, dtype=out.dtype)
+        buf[:, v0:v0 + n] = out
+    return buf if reduce is None else views_mean(buf, N, V, reduce)
+
+
+def check_views(views, model, want_out, who="forward_views"):
+    from .transforms import SampleViews
+    if not isinstance(views, SampleViews):
+        raise PtxError("%s: views must be a pretorched.transforms.SampleViews, got %r" % (who, views))
+    if want_out == "frames" and views.out != "frames":
+        raise PtxError("%s: a float32 model takes the views as uint8 frames (forward_frames): build the SampleViews with "
+                       "out='frames'" % who)
+    if want_out == "bf16" and (views.out != "tensor" or views.dtype != torch.bfloat16):
+        raise PtxError("%s: a bfloat16 model takes the views as the normalised bf16 clip: build the SampleViews with "
+                       "out='tensor', dtype=torch.bfloat16" % who)
 
 
 class EngineOwner:

@@ -99,6 +99,12 @@ class InceptionI3d(EngineOwner, nn.Module):
     def forward_frames(self, frames, opts, transform=None):
         return self._engine.forward_frames(self, frames, opts, transform)
 
+    def forward_views(self, video, opts=None, views=None, reduce="softmax", chunk=None):
+        """Decoded uint8 video [N,Tv,H,W,3] -> class probabilities fp32 [N, classes], averaged over the views of
+        `views` (a `transforms.SampleViews`); reduce: "softmax" | "logits" | None ([N, V, classes] logits); chunk: views
+        per launch (default: as many as the per-launch size limit allows).  See Engine.forward_views."""
+        return self._engine.forward_views(self, video, opts, views, reduce, chunk)
+
 
 def i3d(num_classes=400, pretrained=None):
     """BASELINE.json config 4 (InceptionV1-3D, Kinetics-400).  No checkpoint URL is published by the

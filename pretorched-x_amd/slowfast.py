@@ -157,6 +157,12 @@ class _Runnable(EngineOwner):
         transform: a `transforms.TransformFrames(.., out="frames")` that resizes + crops the frames first."""
         return self._engine.forward_frames(self, frames, opts, transform)
 
+    def forward_views(self, video, opts=None, views=None, reduce="softmax", chunk=None):
+        """Decoded uint8 video [N,Tv,H,W,3] -> class probabilities fp32 [N, classes], averaged over the views of
+        `views` (a `transforms.SampleViews`); reduce: "softmax" | "logits" | None ([N, V, classes] logits); chunk: views
+        per launch (default: as many as the per-launch size limit allows).  See Engine.forward_views."""
+        return self._engine.forward_views(self, video, opts, views, reduce, chunk)
+
 
 class SlowFast(_Runnable, nn.Module):
     """slowfast.SlowFast (:366-398)."""

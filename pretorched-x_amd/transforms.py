@@ -15,6 +15,11 @@ uint8 frames:
   built here on the host in float64 exactly as PIL builds them and the kernel does integer work only, so the
   result equals PIL's to the bit.  Crop and flip are folded into the tables.
 
+* `SampleViews` is test-time multi-view sampling of a whole decoded video: `clips` temporal clips x `crops` spatial
+  crops, each resized + cropped as `TransformFrames` does (same tables, same bits), in one HIP launch per range of
+  views.  Frames are read in place through an index table and the crop windows of a sampled frame share one
+  horizontal pass.  `model.forward_views` feeds the views to a model chunk by chunk and averages the predictions.
+
 Image loading and video decoding stay host work and are not on this path.
 """
 import collections
@@ -25,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import NormDesc, PtxError, ResizeDesc, check
+from ._lib import NormDesc, PtxError, ResizeDesc, ViewsDesc, check
 
 PRECISION_BITS = 22       # PIL's fixed-point coefficient precision for 8-bit channels (32 - 8 - 2)
 
@@ -269,3 +274,228 @@ def apply_frames_transform(transform, frames, who="forward_frames"):
         raise PtxError("%s: transform must be a pretorched.transforms.TransformFrames with out='frames', got %r" % (
             who, transform))
     return transform(frames)
+
+
+# ---------------------------------------------------------------------------------------------
+# multi-view sampling: clips x crops of a decoded video (deterministic test-time rules, no RNG)
+# ---------------------------------------------------------------------------------------------
+def clip_frame_indices(Tv, num_frames, frame_stride=1, clips=1, sampling="dense"):
+    """Source frame of every (clip, frame): int64 [clips][num_frames], all in [0, Tv).
+    dense: clips of `num_frames` frames `frame_stride` apart, their starts spread evenly over the video (the centre for
+    one clip); a video shorter than one clip's span starts every clip at 0 and repeats its last frame.
+    segments (TSN / TRN): the video is cut into `num_frames` segments, clip c takes the frame at (c + 0.5) / clips of
+    each segment; `frame_stride` is not used."""
+    Tv, T, clips = int(Tv), int(num_frames), int(clips)
+    if Tv < 1:
+        raise PtxError("SampleViews: the video has no frames")
+    out = np.empty((clips, T), np.int64)
+    if sampling == "dense":
+        span = (T - 1) * int(frame_stride) + 1
+        for c in range(clips):
+            if Tv >= span:
+                start = ((Tv - span) * c) // (clips - 1) if clips > 1 else (Tv - span) // 2
+            else:
+                start = 0
+            for i in range(T):
+                out[c, i] = min(start + i * int(frame_stride), Tv - 1)
+    elif sampling == "segments":
+        for c in range(clips):
+            for i in range(T):
+                out[c, i] = min(int((i + (c + 0.5) / clips) * Tv / T), Tv - 1)
+    else:
+        raise PtxError("SampleViews: sampling must be 'dense' or 'segments', got %r" % (sampling,))
+    return out
+
+
+def crop_windows(h, w, S, crops=1):
+    """(top, left) of the `crops` S x S windows in the resized h x w frame: the centre crop, or three windows along the
+    longer side (the width when w >= h) at offsets 0, round((L - S) / 2), L - S with the other axis centred."""
+    if crops == 1:
+        return [crop_window(h, w, S, "center")]
+    if crops != 3:
+        raise PtxError("SampleViews: crops must be 1 or 3, got %r" % (crops,))
+    ctop, cleft = int(round((h - S) / 2.0)), int(round((w - S) / 2.0))
+    if w >= h:
+        return [crop_window(h, w, S, (ctop, off)) for off in (0, cleft, w - S)]
+    return [crop_window(h, w, S, (off, cleft)) for off in (0, ctop, h - S)]
+
+
+def _union(table, starts, S):
+    """Entries of the sorted distinct indices that the windows [start, start + S) contain, and each window's first entry."""
+    idx = np.unique(np.concatenate([np.arange(st, st + S) for st in starts]))
+    lo, n, k = (a[idx] for a in table)
+    taps = int(n.max())
+    offs = [int(np.searchsorted(idx, st)) for st in starts]
+    return (np.ascontiguousarray(lo), np.ascontiguousarray(n), np.ascontiguousarray(k[:, :taps])), offs
+
+
+class SampleViews:
+    """Multi-view sampling of decoded uint8 video on the device: `clips` temporal clips x `crops` spatial crops, every
+    view resized + cropped exactly as `TransformFrames(opts, crop=window)` does on the clip's frames (bit-identical).
+
+    opts, scale, preserve_aspect_ratio, out, dtype: as for TransformFrames.  num_frames / frame_stride / clips /
+    sampling: see `clip_frame_indices`; crops: 1 or 3, see `crop_windows`.  View v = clip * crops + crop.
+    share: "auto" (the library picks the workgroup shape), "always" / "never" force the shared horizontal pass on or
+    off (measurements; the results are the same bits)."""
+
+    CACHE_SIZE = 8
+    _SHARE = {"auto": _lib.PTX_VIEWS_SHARE_AUTO, "always": _lib.PTX_VIEWS_SHARE_ALWAYS, "never": _lib.PTX_VIEWS_SHARE_NEVER}
+
+    def __init__(self, opts, num_frames=16, frame_stride=4, clips=10, crops=3, sampling="dense", scale=0.875,
+                 preserve_aspect_ratio=True, out="frames", dtype=torch.float32, share="auto"):
+        if out not in ("tensor", "frames"):
+            raise PtxError("SampleViews: out must be 'tensor' or 'frames', got %r" % (out,))
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise PtxError("SampleViews: dtype must be torch.float32 or torch.bfloat16, got %s" % (dtype,))
+        if out == "frames" and dtype != torch.float32:
+            raise PtxError("SampleViews: out='frames' returns uint8 frames; dtype=%s applies to out='tensor' only" % (dtype,))
+        if not (isinstance(scale, (int, float)) and scale > 0):
+            raise PtxError("SampleViews: scale must be a positive number, got %r" % (scale,))
+        for name, v in (("num_frames", num_frames), ("frame_stride", frame_stride), ("clips", clips)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+                raise PtxError("SampleViews: %s must be a positive integer, got %r" % (name, v))
+        if crops not in (1, 3) or isinstance(crops, bool):
+            raise PtxError("SampleViews: crops must be 1 or 3, got %r" % (crops,))
+        if sampling not in ("dense", "segments"):
+            raise PtxError("SampleViews: sampling must be 'dense' or 'segments', got %r" % (sampling,))
+        if share not in self._SHARE:
+            raise PtxError("SampleViews: share must be 'auto', 'always' or 'never', got %r" % (share,))
+        self.input_size = [int(v) for v in _opt(opts, "input_size")]
+        self.input_space, self.input_range = _opt(opts, "input_space"), _opt(opts, "input_range")
+        self.mean, self.std = list(_opt(opts, "mean")), list(_opt(opts, "std"))
+        self.norm = NormDesc.make(self.mean, self.std, self.input_space, self.input_range)
+        self.num_frames, self.frame_stride, self.clips, self.crops = num_frames, frame_stride, clips, crops
+        self.sampling, self.scale, self.preserve_aspect_ratio = sampling, float(scale), bool(preserve_aspect_ratio)
+        self.out, self.dtype, self.share = out, dtype, share
+        self.size = int(max(self.input_size))
+        self.num_views = clips * crops
+        self._cache = collections.OrderedDict()                      # (H, W, device) -> device tables
+        self._idx_cache = collections.OrderedDict()                  # (Tv, device) -> device frame index table
+
+    def frame_indices(self, Tv):
+        """Host: int64 [clips][num_frames], the source frame of every (clip, frame) of a video of Tv frames."""
+        return clip_frame_indices(Tv, self.num_frames, self.frame_stride, self.clips, self.sampling)
+
+    def windows(self, H, W):
+        """Host: [(top, left)] * crops, the crop windows in the resized frame of H x W input frames."""
+        h, w = resized_size(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
+        if h <= 0 or w <= 0:
+            raise PtxError("SampleViews: resized frame %dx%d is empty" % (h, w))
+        return crop_windows(h, w, self.size, self.crops)
+
+    def tables(self, H, W):
+        """Host tables for H x W frames: `rows` / `cols` ((lo, n, k) over the union of the windows' rows / columns),
+        `row_off` / `col_off` (each window's first entry), `S`, `resized`, `windows`."""
+        S = self.size
+        h, w = resized_size(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
+        wins = self.windows(H, W)
+        rows, row_off = _union(resize_axis_table(H, h), [t for t, _ in wins], S)
+        cols, col_off = _union(resize_axis_table(W, w), [l for _, l in wins], S)
+        for name, t in (("rows", rows), ("columns", cols)):
+            if t[2].shape[1] > _lib.PTX_RESIZE_MAX_TAPS:
+                raise PtxError("SampleViews: down-scaling the %s of a %dx%d frame to %dx%d needs %d taps, the kernel's cap is "
+                               "PTX_RESIZE_MAX_TAPS = %d" % (name, H, W, h, w, t[2].shape[1], _lib.PTX_RESIZE_MAX_TAPS))
+        return {"rows": rows, "cols": cols, "row_off": row_off, "col_off": col_off, "S": S, "resized": (h, w), "windows": wins}
+
+    def view_tables(self, H, W, crop):
+        """The tables of ONE crop window cut out of the union tables, in build_tables' form (apply_tables_numpy takes it)."""
+        t = self.tables(H, W)
+        return {"rows": _select(t["rows"], t["row_off"][crop], t["S"]), "cols": _select(t["cols"], t["col_off"][crop], t["S"]),
+                "S": t["S"], "resized": t["resized"], "window": t["windows"][crop]}
+
+    def _cached(self, cache, key, make):
+        hit = cache.get(key)
+        if hit is not None:
+            cache.move_to_end(key)
+            return hit
+        hit = cache[key] = make()
+        while len(cache) > self.CACHE_SIZE:
+            cache.popitem(last=False)
+        return hit
+
+    def _device_tables(self, H, W, device):
+        def make():
+            t = self.tables(H, W)
+            parts = [a.reshape(-1) for a in t["rows"] + t["cols"]]
+            offs = np.cumsum([0] + [p.size for p in parts])
+            buf = torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(device)  # one small upload per input size
+            return buf, [int(o) * 4 for o in offs[:-1]], t
+        return self._cached(self._cache, (H, W, str(device)), make)
+
+    def _device_indices(self, Tv, device):
+        return self._cached(self._idx_cache, (Tv, str(device)),
+                            lambda: torch.from_numpy(self.frame_indices(Tv).astype(np.int32)).to(device))
+
+    def describe(self, H, W):
+        """Which workgroup shape the library runs for H x W frames: "shared" (one horizontal pass over the union of
+        the windows per sampled frame) or "per-window"; raises PtxError when neither fits."""
+        d = self._desc(1, 1, H, W, 3, H * W * 3, H * W * 3, self.tables(H, W), 0, self.num_views)
+        r = _lib.lib().ptx_resize_views_u8_supported(C.byref(d))
+        if r == 0:
+            raise PtxError("SampleViews: %s" % _lib.lib().ptx_last_error().decode(errors="replace"))
+        return "shared" if r == 2 else "per-window"
+
+    def _desc(self, N, Tv, H, W, Cc, stride_n, stride_t, t, v0, nv):
+        d = ViewsDesc()
+        d.N, d.Tv, d.H, d.W, d.C = N, Tv, H, W, Cc
+        d.clips, d.T, d.crops = self.clips, self.num_frames, self.crops
+        d.stride_n, d.stride_t = stride_n, stride_t
+        d.S, d.Ur, d.Uc = self.size, len(t["rows"][0]), len(t["cols"][0])
+        d.taps_h, d.taps_w = t["rows"][2].shape[1], t["cols"][2].shape[1]
+        for k in range(self.crops):
+            d.row_off[k], d.col_off[k] = t["row_off"][k], t["col_off"][k]
+        d.v0, d.nv = v0, nv
+        d.out_mode = _lib.PTX_RESIZE_OUT_U8 if self.out == "frames" else (
+            _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16)
+        d.share = self._SHARE[self.share]
+        return d
+
+    def __call__(self, video):
+        """uint8 CUDA video [N,Tv,H,W,3] | [Tv,H,W,3], any Tv, H, W  ->  every view:
+        out="frames": uint8 [N,V,T,S,S,3] | [V,T,S,S,3];  out="tensor": fp32 | bf16 [N,V,3,T,S,S] | [V,3,T,S,S]."""
+        return self.sample(video)
+
+    def sample(self, video, v0=0, nv=None):
+        """Views v0 .. v0 + nv - 1 only (default: all from v0 on), shaped as __call__'s result with V -> nv.  The
+        video is read in place: any view whose frames are contiguous [H,W,3] blocks (slices and steps over N and Tv
+        included) is taken without a copy."""
+        if not isinstance(video, torch.Tensor):
+            raise PtxError("SampleViews: video must be a uint8 CUDA tensor, got %s" % type(video).__name__)
+        if video.dim() not in (4, 5):
+            raise PtxError("SampleViews: expected [N,Tv,H,W,3] or [Tv,H,W,3], got shape %s" % (tuple(video.shape),))
+        if video.shape[-1] != 3:
+            raise PtxError("SampleViews: frames must have 3 interleaved channels, got %d" % video.shape[-1])
+        if not video.is_cuda or video.dtype != torch.uint8:
+            raise PtxError("SampleViews: video must be a uint8 CUDA tensor (no CPU fallback)")
+        lead = video.dim()
+        v5 = video if lead == 5 else video.unsqueeze(0)
+        N, Tv, H, W, Cc = v5.shape
+        if N * Tv * H * W == 0:
+            raise PtxError("SampleViews: empty video")
+        V = self.num_views
+        nv = V - v0 if nv is None else nv
+        if not (isinstance(v0, int) and isinstance(nv, int) and 0 <= v0 and 1 <= nv and v0 + nv <= V):
+            raise PtxError("SampleViews: view range [%r, %r + %r) is outside the %d views" % (v0, v0, nv, V))
+        frame = H * W * Cc
+        sn, st = v5.stride(0), v5.stride(1)
+        if (tuple(v5.stride()[2:]) != (W * Cc, Cc, 1) or (Tv > 1 and st < frame) or (N > 1 and sn < frame)):
+            v5 = v5.contiguous()                                     # frames that are not [H,W,3] blocks: one copy
+            sn, st = v5.stride(0), v5.stride(1)
+        st = st if Tv > 1 else frame
+        sn = sn if N > 1 else max(frame, st * Tv)
+        S, T = self.size, self.num_frames
+        with torch.cuda.device(video.device):
+            buf, offs, t = self._device_tables(H, W, video.device)
+            idx = self._device_indices(Tv, video.device)
+            if self.out == "frames":
+                y = torch.empty((N, nv, T, S, S, Cc), device=video.device, dtype=torch.uint8)
+            else:
+                y = torch.empty((N, nv, Cc, T, S, S), device=video.device, dtype=self.dtype)
+            desc = self._desc(N, Tv, H, W, Cc, sn, st, t, v0, nv)
+            base = buf.data_ptr()
+            check(_lib.lib().ptx_resize_views_u8(C.byref(desc), C.c_void_p(v5.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                                 *[C.c_void_p(base + o) for o in offs],
+                                                 C.c_void_p(y.data_ptr()), C.byref(self.norm),
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "ptx_resize_views_u8")
+        return y if lead == 5 else y[0]

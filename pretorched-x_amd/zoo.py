@@ -431,6 +431,12 @@ class VideoResNet(EngineOwner, nn.Module):
         transform: a `transforms.TransformFrames(.., out="frames")` that resizes + crops the frames first."""
         return self._engine.forward_frames(self, frames, opts, transform)
 
+    def forward_views(self, video, opts=None, views=None, reduce="softmax", chunk=None):
+        """Decoded uint8 video [N,Tv,H,W,3] -> class probabilities fp32 [N, classes], averaged over the views of
+        `views` (a `transforms.SampleViews`); reduce: "softmax" | "logits" | None ([N, V, classes] logits); chunk: views
+        per launch (default: as many as the per-launch size limit allows).  See Engine.forward_views."""
+        return self._engine.forward_views(self, video, opts, views, reduce, chunk)
+
 
 # ---------------------------------------------------------------------------------------------
 # TRN relation heads (reference trn.py:20-113): standalone modules, HIP-executed MLPs
@@ -613,6 +619,43 @@ class TRN(nn.Module):
 
     def forward(self, input):
         return self.logits(self.features(input))
+
+    def forward_frames(self, frames, opts=None, transform=None):
+        """Decoded uint8 frames [B, T, H, W, 3] with T == num_segments -> logits: the backbone's forward_frames on the
+        [B*T, H, W, 3] view (normalisation fused into its stem), then the relation head; bit-identical to forward() on
+        the FramesToTensor(opts) output rearranged to [B, T, 3, H, W].  opts: default the backbone's settings."""
+        from ._lib import PtxError
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 5:
+            raise PtxError("TRN.forward_frames: expected uint8 CUDA frames [B,T,H,W,3]")
+        if frames.shape[1] != self.num_segments:
+            raise PtxError("TRN.forward_frames: %d frames per clip, the model has num_segments = %d" % (
+                frames.shape[1], self.num_segments))
+        B = frames.shape[0]
+        flat = frames.reshape((B * self.num_segments,) + tuple(frames.shape[2:]))
+        base_rep = self.base_model.forward_frames(flat, self.base_model if opts is None else opts, transform)
+        base_rep = base_rep.view(B, -1, self.num_segments, base_rep.size(-1))
+        return self.logits(self.temporal_relation(base_rep).squeeze())
+
+    def forward_views(self, video, opts=None, views=None, reduce="softmax", chunk=None):
+        """Decoded uint8 video [N,Tv,H,W,3] -> class probabilities fp32 [N, classes] averaged over `views` (a
+        `transforms.SampleViews` with out="frames" and num_frames == num_segments; sampling="segments" is TSN's rule).
+        reduce / chunk as Engine.forward_views; every chunk goes through forward_frames."""
+        from ._lib import PtxError
+        from .engine import check_views, model_precision, run_views
+        if model_precision(self.base_model) != "fp32":
+            raise PtxError("TRN.forward_views runs float32 models only")
+        check_views(views, self, "frames", "TRN.forward_views")
+        if views.num_frames != self.num_segments:
+            raise PtxError("TRN.forward_views: the sampler draws %d frames per clip, the model has num_segments = %d" % (
+                views.num_frames, self.num_segments))
+        eng, S = self.base_model._engine, views.size
+        key = ("maxb", (3, S, S))
+        with eng._lock:
+            mb = eng._sig.get(key)
+            if mb is None:
+                mb = eng._sig[key] = eng.max_batch(self.base_model, key[1])
+        return run_views(video, views, lambda fr: self.forward_frames(fr, opts), max(1, mb // self.num_segments), reduce,
+                         chunk, "TRN.forward_views")
 
     @property
     def crop_size(self):
