@@ -19,7 +19,8 @@ import torch
 
 from . import _lib
 from ._lib import PtxError
-from .engine import Engine, relation_mlp
+from .engine import Engine
+from .heads import relation_mlp
 from . import transforms  # noqa: F401
 from . import models, utils  # noqa: F401  (utils.Identity: README.md:543-546; models.Identity: models/__init__.py:79)
 from .adopt import accelerate  # noqa: F401

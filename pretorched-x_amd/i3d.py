@@ -7,7 +7,7 @@ kinetics-i3d (`InceptionI3d`: Conv3d_1a_7x7 ... Mixed_5c, logits; Unit3D = conv 
 BatchNorm(eps 1e-3) + ReLU with TF-"SAME" padding), so such checkpoints load by key.  **Parity is
 unpinned by the reference**: the checker is the builder-written CPU module in oracle/i3d_standin.py.
 
-Only parameters live here; `engine.Plan._build_i3d` compiles the forward pass: every Unit3D is one
+Only parameters live here; `plans.build_i3d` compiles the forward pass: every Unit3D is one
 implicit-GEMM launch with BN/ReLU folded, "SAME" padding is front-pad geometry (no F.pad copy), the
 four branches of an Inception module write their channel slices of the module output directly
 (no torch.cat), the stem is the kW-folded small-Cin path.

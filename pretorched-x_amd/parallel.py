@@ -96,9 +96,9 @@ def verify_gather(local_logits, gathered, group=None):
 def broadcast_tuned_table(src=0, group=None):
     """Tile choices measured on rank `src` (Engine.autotune) adopted by every rank: N concurrent tuners on one
     node perturb each other's HIP-event timings, and every rank should run the same kernels anyway."""
-    from . import engine as _engine
-    box = [_engine.tuned_snapshot() if dist.get_rank(group) == src else None]
+    from . import tuned as _tuned
+    box = [_tuned.tuned_snapshot() if dist.get_rank(group) == src else None]
     dist.broadcast_object_list(box, src=src, group=group)
     if dist.get_rank(group) != src:
-        _engine.tuned_merge(box[0])
+        _tuned.tuned_merge(box[0])
     return len(box[0])

@@ -1,6 +1,6 @@
 """Plan builders of the model families beyond the ResNet trunk: SlowFast, I3D, BigGAN-deep.
 
-Each `build_*(plan, model)` appends launches to an `engine.Plan` (named `self` below: these were Plan
+Each `build_*(plan, model)` appends launches to a `plan.Plan` (named `self` below: these were Plan
 methods and read like them) using its building blocks -- conv / conv_bn / maxpool / act / slices --
 and sets `plan.feat` (and `plan.head` when the classifier tail is not the default avg-pool + Linear).
 """
@@ -10,7 +10,8 @@ import torch
 import torch.nn as nn
 
 from ._lib import PTX_ACT_OUT_BF16, PTX_ACT_OUT_F16, PtxError, check
-from .engine import RawInput, _geom, _ptr, _r4, _r8, _stream
+from .heads import linear
+from .steps import RawInput, _geom, _ptr, _r4, _r8, _stream, _tag
 
 
 # --------------------------------------------------------------------------------------------
@@ -197,7 +198,6 @@ def build_mnist_nl(self, model):
 
     def head(engine, model, x=x, flat=flat):
         from ._lib import PTX_EPI_RELU
-        from .engine import linear
         check(lib.ptx_ndhwc_to_ncdhw(_ptr(x.t), _ptr(flat), x.N, x.C, x.S, x.ld, _stream()), "ptx_ndhwc_to_ncdhw")
         h = linear(flat.view(x.N, -1), model.fc[0], PTX_EPI_RELU)          # Dropout is the identity in eval mode
         return linear(h, model.fc[3])
@@ -345,7 +345,6 @@ def build_biggan(self, model):
         def step(st):
             check(lib.ptx_affine_act_upsample(xp, yp, sc, sh, ld_s, N, H_, W_, C_, ldx, ldy, up, act, st),
                   "ptx_affine_act_upsample")
-        from .engine import _tag
         self.steps.append(_tag(step, "affine_act_upsample", 4 * N * H_ * W_ * C_ + (2 if f16_out else 4) * N * H_ * W_ * C_ * up * up))
         return y
 
@@ -451,7 +450,6 @@ def _biggan_fp16_stages(self, model, h, cbn, affine, offs, scale_all, shift_all,
         for r, was in guarded:
             ok, vals = half_affine_ok(self.get(r), eps, cond_max)
             if ok != was and guard_on:
-                from .engine import PtxError
                 raise PtxError("BigGAN fp16 plan: a BatchNorm's folded tables %s the range the packed-fp16 affine is safe in "
                                "(max |scale| %.3g, max |shift| %.3g, max |mean| / sigma %.3g) since this plan was compiled: call "
                                "model.refresh() to recompile it" % ("left" if was else "entered", vals[0], vals[1], vals[2]))
@@ -487,7 +485,7 @@ def _biggan_fp16_stages(self, model, h, cbn, affine, offs, scale_all, shift_all,
     for k, (si, bi, blk) in enumerate(flat):
         name = "blocks.%d.%d" % (si, bi)
         nxt = flat[k + 1][2] if k + 1 < len(flat) else None
-        if blk.kind != "gblock" and getattr(xr, "f16", False) and nxt is not None and nxt.kind == "gblock":
+        if blk.kind != "gblock" and xr.f16 and nxt is not None and nxt.kind == "gblock":
             # self-attention inside the half chain (round 4): projections on the fp16 tiles, the output conv + residual + the
             # next block's cBN1 + ReLU as ONE launch that writes both things the next block reads (or the raw sum alone when
             # the next conv1 activates its own input)
@@ -521,7 +519,7 @@ def _biggan_fp16_stages(self, model, h, cbn, affine, offs, scale_all, shift_all,
             xa = self.conv(t, pk(blk.conv4), one, zero, relu=True, affine=(_ptr(oscale), _ptr(oshift), obn.channels),
                            out_f16=True, label=name + ".conv4", **skip)
             xr = None
-        elif pro_ok(nxt, t.H, t.W) and getattr(xr, "f16", False):
+        elif pro_ok(nxt, t.H, t.W) and xr.f16:
             # (only where the skip operand already is halfs: the first block's skip is the fp32 linear output and keeps the
             #  two-output fused stage, so the chain of halfs starts there)
             # the next block activates its own input: ONE output, the raw sum (half of what this conv used to write)
@@ -631,7 +629,6 @@ def _rgb_conv_ok(self, channels, x=None, conv=None, ld_aff=0):
 def _rgb_conv(self, x, conv, scale_ptr, shift_ptr, ld_aff):
     """BN -> ReLU -> conv3x3(C -> 3) -> tanh as ONE launch on the raw half feature map x (gen_stage_f16.hip)."""
     from ._lib import RgbConvDesc, PTX_EPI_TANH
-    from .engine import PtxError, _tag
     lib = self.lib
     d = RgbConvDesc(x.N, x.H, x.W, x.C, x.ld, 4, ld_aff, PTX_EPI_TANH)
     if not x.f16 or conv.out_channels != 3 or tuple(conv.kernel_size) != (3, 3) or tuple(conv.padding) != (1, 1) \
@@ -699,13 +696,13 @@ def biggan_attention(self, x, att, name):
     one, zero = (1, 1, 1), (0, 0, 0)
     # the attention block works on the fp32 raw map (softmax wants fp32 logits); in the fp16 generator plan its two
     # pointwise convs run as split operands on the fp16 matrix cores (fp32-accurate, ~2.5x the fp32-MFMA rate)
-    x3 = True if getattr(self, "half_plan", False) else None
+    x3 = True if self.half_plan else None
     tpg = self.conv(x, self.pack([att.theta, att.phi, att.g], None, x3=x3), one, zero, label=name + ".theta_phi_g")
     phi = self.maxpool(tpg.slice(c8, c8), (1, 2, 2), (1, 2, 2), (0, 0, 0))
     g = self.maxpool(tpg.slice(2 * c8, c2), (1, 2, 2), (1, 2, 2), (0, 0, 0))
     S4 = HW // 4
     yatt = self.act(N, 1, x.H, x.W, c2)
-    if self.attention(tpg.slice(0, c8), phi, g, yatt, f16=bool(getattr(self, "half_plan", False))):
+    if self.attention(tpg.slice(0, c8), phi, g, yatt, f16=bool(self.half_plan)):
         return self.conv(yatt, self.pack(att.o, None, scale=(att, "gamma"), x3=x3), one, zero, res=x, label=name + ".o")
     ldf = _r4(S4)
     f = torch.empty((N, HW, ldf), device=self.dev, dtype=torch.float32)

@@ -4,7 +4,7 @@
 Same constructors and `state_dict` ABI as the reference classes -- `SlowFast` (`slow.*`, `fast.*`,
 `fast.lateral_*`, bias-free `last_linear`), `SlowOnly`, `FastOnly` and the `resnet18/50/101/152/200`
 factories with their `mode='SF'|'S'|'F'` switch -- but the modules only hold parameters: the forward
-pass is compiled by `engine.Plan._build_slowfast` into libptx_amd launches.
+pass is compiled by `plans.build_slowfast` into libptx_amd launches.
 
 What the engine does differently from the reference graph (slowfast.py:140-156, 280-299, 385-398):
   * `input[:, :, ::stride]` is a frame stride of the stem's fold kernel, not a strided copy;

@@ -2,7 +2,7 @@
 (`model.last_linear = pretrained.utils.Identity()`, /root/reference/README.md:543-546; defined at
 /root/reference/pretorched/models/utils.py:81-87 and re-exported as `pretorched.models.Identity`, models/__init__.py:79).
 The engine reads `last_linear` at call time: anything that is not a plain fp32 nn.Linear on the model's device is simply
-CALLED on the pooled features (engine.py `Plan.run_head`), so this class needs no special casing."""
+CALLED on the pooled features (plan.py `Plan.run_head`), so this class needs no special casing."""
 import torch
 
 

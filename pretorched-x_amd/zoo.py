@@ -453,7 +453,7 @@ class Relation(nn.Module):
         self.eval()
 
     def forward(self, input):
-        from .engine import relation_mlp
+        from .heads import relation_mlp
         if eager.wanted(self, input):
             return eager.relation(self, input)
         flat = input.contiguous().view(-1, self.num_inputs * self.in_features)
@@ -481,7 +481,7 @@ class MultiScaleRelation(nn.Module):
     def forward(self, input):
         import numpy as np
         from ._lib import PTX_REL_MAX_FRAMES, PTX_REL_MAX_SETS
-        from .engine import relation_mlp, relation_scale
+        from .heads import relation_mlp, relation_scale
         x = input.contiguous().view(-1, self.num_input, self.in_features)        # [B, T, F]
         if eager.wanted(self, input):          # trn.py:95-113 on the torch.nn path: same RNG consumption
             outs = []
@@ -614,7 +614,7 @@ class TRN(nn.Module):
         return self.temporal_relation(base_rep).squeeze()
 
     def logits(self, features):
-        from .engine import linear
+        from .heads import linear
         return linear(features, self.last_linear)
 
     def forward(self, input):
@@ -641,7 +641,8 @@ class TRN(nn.Module):
         `transforms.SampleViews` with out="frames" and num_frames == num_segments; sampling="segments" is TSN's rule).
         reduce / chunk as Engine.forward_views; every chunk goes through forward_frames."""
         from ._lib import PtxError
-        from .engine import check_views, model_precision, run_views
+        from .heads import check_views, run_views
+        from .plan import model_precision
         if model_precision(self.base_model) != "fp32":
             raise PtxError("TRN.forward_views runs float32 models only")
         check_views(views, self, "frames", "TRN.forward_views")
@@ -649,11 +650,7 @@ class TRN(nn.Module):
             raise PtxError("TRN.forward_views: the sampler draws %d frames per clip, the model has num_segments = %d" % (
                 views.num_frames, self.num_segments))
         eng, S = self.base_model._engine, views.size
-        key = ("maxb", (3, S, S))
-        with eng._lock:
-            mb = eng._sig.get(key)
-            if mb is None:
-                mb = eng._sig[key] = eng.max_batch(self.base_model, key[1])
+        mb = eng._max_batch(self.base_model, (3, S, S))
         return run_views(video, views, lambda fr: self.forward_frames(fr, opts), max(1, mb // self.num_segments), reduce,
                          chunk, "TRN.forward_views")
 

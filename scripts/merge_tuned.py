@@ -10,13 +10,13 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from pretorched_x_amd import engine, _lib        # noqa: E402
+from pretorched_x_amd import tuned, _lib         # noqa: E402
 
 lib = _lib.lib()
 names = {lib.ptx_conv3d_config_name(i).decode() for i in range(lib.ptx_conv3d_num_configs())}
 names |= {lib.ptx_conv3d_chain_config_name(i).decode() for i in range(lib.ptx_conv3d_chain_num_configs())}     # "chain:" keys
 names |= {"chain", "pair"}                                                                                       # "alt:" keys
-names |= {"igemm", "lanes", "program", "launches"} | set(engine.BODY_SHAPES)                                     # "body:" / "lanes:" / "prog:" keys
+names |= {"igemm", "lanes", "program", "launches"} | set(tuned.BODY_SHAPES)                                      # "body:" / "lanes:" / "prog:" keys
 path = os.path.join(ROOT, "pretorched-x_amd", "tuned_gfx950.json")
 table = json.load(open(path))
 n0 = len(table)
@@ -29,6 +29,6 @@ for f in [a for a in sys.argv[1:] if a != "--new-only"]:
         if base.get(k) != v and not (new_only and k in base):
             table[k] = v
 table = {k: v for k, v in table.items() if v[0] in names}
-engine._tuned = {k: (str(v[0]), int(v[1])) for k, v in table.items()}
-engine.save_tuned_table(path)
+tuned.tuned_replace(table)
+tuned.save_tuned_table(path)
 print("%d -> %d entries" % (n0, len(table)))
