@@ -477,6 +477,39 @@ int ptx_resize_views_u8(const ptx_views_desc* desc, const uint8_t* video, const 
                         const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, /* [Ur], [Ur], [Ur][taps_h] */
                         const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, /* [Uc], [Uc], [Uc][taps_w] */
                         void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+/* YUV 4:2:0 decoder output as the source of the two resize entry points above: NV12 (interleaved chroma, what the
+ * hardware decoders return, usually with a row pitch) and I420 (planar).  The kernels convert to RGB while they stage an
+ * input row on chip, so the RGB frame never exists in memory; everything after the staged row, and therefore every
+ * output bit, is that of the _u8 entry point on the converted frames.  Integer contract, 16 fractional bits, with
+ * y' = Y - y_off, cb = Cb - 128, cr = Cr - 128 and >> an arithmetic shift:
+ *   R = clip8((ky*y' + krv*cr + 32768) >> 16)   G = clip8((ky*y' - kgu*cb - kgv*cr + 32768) >> 16)
+ *   B = clip8((ky*y' + kbu*cb + 32768) >> 16)
+ * The chroma sample of pixel (r, c) is (r >> 1, c >> 1) (nearest replication); a chroma plane has ceil(H/2) x ceil(W/2)
+ * samples.  Planes are read in place: frame (n, t) of the luma plane starts at y + n * stride_n_y + t * stride_t_y, its
+ * row r at + r * pitch_y (bytes); the chroma pointers use stride_n_c / stride_t_c / pitch_c and sample c of a row lies at
+ * + c * step_c.  No alignment is required of any pointer or pitch.  desc->C must be 3; H, W may be odd.
+ * The host-side checks (null planes, pitches <= 0 or shorter than a row, step_c, 32-bit overflow of a plane) need no device. */
+typedef struct ptx_yuv420_src {
+    const uint8_t *y, *u, *v;          /* first sample of each plane of frame (0,0); interleaved UV: v == u + 1   */
+    int64_t stride_n_y, stride_t_y;    /* bytes between videos / frames of the luma plane                         */
+    int64_t stride_n_c, stride_t_c;    /* same for both chroma pointers                                           */
+    int32_t pitch_y, pitch_c;          /* bytes between rows                                                      */
+    int32_t step_c;                    /* bytes between chroma samples of a row: 1 planar, 2 interleaved          */
+    int32_t y_off, ky, krv, kgu, kgv, kbu;
+} ptx_yuv420_src;
+/* ptx_resize_frames_u8 on frames [N][T] of a YUV source (stride_n_* / stride_t_* address frame (n, t)) */
+int ptx_resize_frames_yuv420_supported(const ptx_resize_desc* desc, const ptx_yuv420_src* src);
+int ptx_resize_frames_yuv420(const ptx_resize_desc* desc, const ptx_yuv420_src* src,
+                             const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
+                             const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k,
+                             void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+/* ptx_resize_views_u8 on a YUV video: the source's strides address the frames, desc->stride_n / desc->stride_t are
+ * IGNORED.  _supported returns 0 / 1 / 2 as ptx_resize_views_u8_supported does. */
+int ptx_resize_views_yuv420_supported(const ptx_views_desc* desc, const ptx_yuv420_src* src);
+int ptx_resize_views_yuv420(const ptx_views_desc* desc, const ptx_yuv420_src* src, const int32_t* frame_idx,
+                            const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
+                            const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k,
+                            void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
 /* View reduction: logits [N * V][K] (fp32, or bf16 when bf16 != 0; row pitch ld elements) -> y fp32 [N][K]: the mean over
  * the V rows of a video of softmax(row) (mode 0; fp32, max-subtracted) or of the rows themselves (mode 1).  K <= 4096. */
 int ptx_views_mean(const void* logits, float* y, int32_t N, int32_t V, int32_t K, int64_t ld, int32_t bf16,

@@ -113,6 +113,14 @@ class ViewsDesc(C.Structure):
                [("row_off", C.c_int32 * PTX_VIEWS_MAX_CROPS), ("col_off", C.c_int32 * PTX_VIEWS_MAX_CROPS)] + \
                [(n, C.c_int32) for n in ("v0", "nv", "out_mode", "share")]
 
+
+class Yuv420Src(C.Structure):
+    """ptx_yuv420_src: the planes of a YUV 4:2:0 source (NV12 / I420, any row pitch) and the colour coefficients."""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p)] + \
+               [(n, C.c_int64) for n in ("stride_n_y", "stride_t_y", "stride_n_c", "stride_t_c")] + \
+               [(n, C.c_int32) for n in ("pitch_y", "pitch_c", "step_c", "y_off", "ky", "krv", "kgu", "kgv", "kbu")]
+
+
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
 
@@ -211,6 +219,12 @@ SIGNATURES = {
     "ptx_resize_frames_u8": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
     "ptx_resize_views_u8_supported": (C.c_int, [C.POINTER(ViewsDesc)]),
     "ptx_resize_views_u8": (C.c_int, [C.POINTER(ViewsDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+    "ptx_resize_frames_yuv420_supported": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src)]),
+    "ptx_resize_frames_yuv420": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _P,
+                                           C.POINTER(NormDesc), _P]),
+    "ptx_resize_views_yuv420_supported": (C.c_int, [C.POINTER(ViewsDesc), C.POINTER(Yuv420Src)]),
+    "ptx_resize_views_yuv420": (C.c_int, [C.POINTER(ViewsDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _P, _P,
+                                          C.POINTER(NormDesc), _P]),
     "ptx_views_mean": (C.c_int, [_P, _P, _I, _I, _I, _L, _I, _I, _P]),
     "ptx_maxpool3d_fwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P]),
     "ptx_cbn_fold": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

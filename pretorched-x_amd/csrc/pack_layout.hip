@@ -280,12 +280,15 @@ __global__ void __launch_bounds__(256) fold_kw_frames_u8_kernel(const unsigned c
 // Table entries are clamped to the frame: a wrong table gives wrong pixels, never a stray access.
 // ---------------------------------------------------------------------------------------------
 
-template <int C>
+// YUV: the frames are the planes of `ys` (f is unused) and a row is converted to RGB while it is staged (resize_common.h);
+// everything from the staged row on is the same code.
+template <int C, bool YUV = false>
 __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d, const unsigned char* __restrict__ f,
                                                                const int* __restrict__ row_lo, const int* __restrict__ row_n,
                                                                const int* __restrict__ row_k, const int* __restrict__ col_lo,
                                                                const int* __restrict__ col_n, const int* __restrict__ col_k,
-                                                               void* __restrict__ y, ptx_norm_desc nd, ResizePlan pl) {
+                                                               void* __restrict__ y, ptx_norm_desc nd, ResizePlan pl,
+                                                               ptx_yuv420_src ys) {
     extern __shared__ __attribute__((aligned(16))) unsigned char resize_smem[];
     int* hdr = reinterpret_cast<int*>(resize_smem);                 // [0] first, [1] one-past-last referenced column
     int* t_clo = hdr + 4;                                           // clamped table entries: columns [Wo], [Wo] ...
@@ -302,7 +305,8 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int WoC = d.Wo * C, istride = pl.istride;
     const int half = 1 << (kResizeBits - 1);
-    const unsigned char* fin = f + (size_t)frame * d.H * d.W * C;
+    const unsigned char* fin = YUV ? nullptr : f + (size_t)frame * d.H * d.W * C;
+    const YuvFrame yf = YUV ? yuv_frame(ys, frame / d.T, frame % d.T) : YuvFrame{};
 
     if (tid == 0) {
         hdr[0] = d.W;
@@ -338,6 +342,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
     const int* rk = pl.k_in_lds ? t_k + d.Wo * d.taps_w : row_k + (size_t)y0 * d.taps_h;  // [y1 - y0][taps_h]
     const int cmin = hdr[0];
     const int span_bytes = max(hdr[1] - cmin, 0) * C;               // <= W * C
+    const int px_end = max(hdr[1], cmin);                           // one past the last referenced column
 
     int r = y0;
     while (r < y1) {
@@ -359,11 +364,15 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
         // row is resampled, so the HBM latency hides under the LDS work instead of adding to every row.
         unsigned char* sw = stage + wave * pl.stage_stride;
         ResizeRow pre = {};
-        resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
+        YuvRow ypre = {};
+        if constexpr (YUV) yuv_fetch_row(ypre, 0 + wave, nrows, ys, yf, lo0, cmin, px_end, lane);
+        else resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
         for (int i0 = 0; i0 < nrows; i0 += 4) {
             const int i = i0 + wave;
             int off = 0;
-            if (i < nrows) {
+            if constexpr (YUV) {
+                if (i < nrows) off = yuv_stage_row(sw, ypre, ys, yf, lo0 + i, cmin, px_end, lane);
+            } else if (i < nrows) {
                 int vb, ve, end;
                 const unsigned char* g = resize_row_span(fin, lo0 + i, d.W, cmin, C, span_bytes, off, vb, ve, end);
                 if (lane < vb - off) sw[off + lane] = (unsigned char)pre.head;
@@ -375,7 +384,8 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
                 if (lane < end - ve) sw[ve + lane] = (unsigned char)pre.tail;
             }
             __syncthreads();
-            resize_fetch_row(pre, i + 4, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
+            if constexpr (YUV) yuv_fetch_row(ypre, i + 4, nrows, ys, yf, lo0, cmin, px_end, lane);
+            else resize_fetch_row(pre, i + 4, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
             if (i < nrows) {
                 for (int x = lane; x < d.Wo; x += 64) {
                     const int lo = t_clo[x], n = t_cn[x];
@@ -852,14 +862,15 @@ extern "C" int ptx_resize_frames_u8_supported(const ptx_resize_desc* desc) {
     return resize_plan(desc, nullptr, &p, "ptx_resize_frames_u8_supported") == PTX_OK;
 }
 
-extern "C" int ptx_resize_frames_u8(const ptx_resize_desc* desc, const uint8_t* frames, const int32_t* row_lo,
-                                    const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo, const int32_t* col_n,
-                                    const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream) {
-    const char* who = "ptx_resize_frames_u8";
+// Both sources: `frames` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.
+static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames, const ptx_yuv420_src* src, const int32_t* row_lo,
+                             const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo, const int32_t* col_n,
+                             const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream, const char* who) {
     ResizePlan p;
     int s = resize_plan(desc, y, &p, who);
     if (s) return s;
-    if (!frames || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k) return fail(PTX_ERR_INVALID, "%s: null pointer", who);
+    if (src && (s = yuv_check(src, desc->C, desc->H, desc->W, who))) return s;
+    if ((!frames && !src) || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k) return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     ptx_norm_desc nd = {};
     if (desc->out_mode != PTX_RESIZE_OUT_U8) {
         if (!norm) return fail(PTX_ERR_INVALID, "%s: null norm descriptor", who);
@@ -872,7 +883,12 @@ extern "C" int ptx_resize_frames_u8(const ptx_resize_desc* desc, const uint8_t* 
     hipStream_t st = (hipStream_t)stream;
 #define PTX_RESIZE_LAUNCH(CH)                                                                                               \
     hipLaunchKernelGGL(resize_frames_u8_kernel<CH>, grid, dim3(256), p.lds_bytes, st, *desc, frames, row_lo, row_n, row_k, \
-                       col_lo, col_n, col_k, y, nd, p)
+                       col_lo, col_n, col_k, y, nd, p, ptx_yuv420_src{})
+    if (src) {
+        hipLaunchKernelGGL((resize_frames_u8_kernel<3, true>), grid, dim3(256), p.lds_bytes, st, *desc, (const unsigned char*)nullptr, row_lo, row_n,
+                           row_k, col_lo, col_n, col_k, y, nd, p, *src);
+        return hip_check(hipGetLastError(), who);
+    }
     switch (desc->C) {
         case 1: PTX_RESIZE_LAUNCH(1); break;
         case 2: PTX_RESIZE_LAUNCH(2); break;
@@ -881,6 +897,26 @@ extern "C" int ptx_resize_frames_u8(const ptx_resize_desc* desc, const uint8_t* 
     }
 #undef PTX_RESIZE_LAUNCH
     return hip_check(hipGetLastError(), "ptx_resize_frames_u8 launch");
+}
+
+extern "C" int ptx_resize_frames_u8(const ptx_resize_desc* desc, const uint8_t* frames, const int32_t* row_lo,
+                                    const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo, const int32_t* col_n,
+                                    const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream) {
+    return resize_frames_run(desc, frames, nullptr, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, "ptx_resize_frames_u8");
+}
+
+extern "C" int ptx_resize_frames_yuv420_supported(const ptx_resize_desc* desc, const ptx_yuv420_src* src) {
+    const char* who = "ptx_resize_frames_yuv420_supported";
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, who) == PTX_OK && yuv_check(src, desc->C, desc->H, desc->W, who) == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_yuv420(const ptx_resize_desc* desc, const ptx_yuv420_src* src, const int32_t* row_lo,
+                                        const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo, const int32_t* col_n,
+                                        const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream) {
+    const char* who = "ptx_resize_frames_yuv420";
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    return resize_frames_run(desc, nullptr, src, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who);
 }
 
 // y[r][0..W) = x[r][0..W), y[r][W..ld) = 0: gives rows whose length is not a multiple of 4 floats a 16-byte pitch

@@ -63,6 +63,156 @@ __device__ __forceinline__ void resize_fetch_row(ResizeRow& r, int i, int nrows,
     if (lane < end - ve) r.tail = g[ve + lane];
 }
 
+// ---------------------------------------------------------------------------------------------
+// YUV 4:2:0 sources (ptx_yuv420_src: NV12 / I420 planes, any row pitch).  The row staging converts to RGB on the way
+// from the registers to the row stage, so the stage holds the interleaved RGB bytes the horizontal pass reads and no
+// RGB frame exists in HBM.  A lane owns GROUPS of 16 pixels that start at an even pixel (e0 = cmin & ~1, group g is
+// [e0 + 16 g, e0 + 16 g + 16)): its 16 luma bytes and its 8 chroma pairs are exactly the bytes it needs, whatever the
+// planes' alignments, so nothing crosses lanes.  A whole group is three loads (16 luma bytes; 16 interleaved or 8 + 8
+// planar chroma bytes) through align-1 vector types -- gfx950 global loads take any address -- and the last, partial
+// group of a row is fetched byte by byte, so no byte past the referenced span [cmin, cmax) is touched.
+//   R = clip8((ky y' + krv cr + 2^15) >> 16)   G = clip8((ky y' - kgu cb - kgv cr + 2^15) >> 16)   B = clip8((ky y' + kbu cb + 2^15) >> 16)
+// with y' = Y - y_off, cb = Cb - 128, cr = Cr - 128; chroma of pixel (r, c) is the sample (r >> 1, c >> 1).
+// ---------------------------------------------------------------------------------------------
+typedef u32x4 u32x4_any __attribute__((aligned(1)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef u32x2 u32x2_any __attribute__((aligned(1)));
+
+struct YuvFrame {                // one frame of a ptx_yuv420_src
+    const unsigned char *y, *u, *v;
+};
+struct YuvGroup {                // 16 pixels: luma bytes, then chroma as 8 U bytes (c.x, c.y) and 8 V bytes (c.z, c.w)
+    u32x4 y, c;
+};
+struct YuvRow {                  // one lane's share of the first 2048 pixels of a row, on its way from HBM to LDS
+    YuvGroup g0, g1;
+};
+
+__device__ __forceinline__ YuvFrame yuv_frame(const ptx_yuv420_src& s, int n, int t) {
+    YuvFrame f;
+    f.y = s.y + (int64_t)n * s.stride_n_y + (int64_t)t * s.stride_t_y;
+    f.u = s.u + (int64_t)n * s.stride_n_c + (int64_t)t * s.stride_t_c;
+    f.v = s.v + (int64_t)n * s.stride_n_c + (int64_t)t * s.stride_t_c;
+    return f;
+}
+
+// Pixels [p0, min(p0 + 16, px_end)) of input row `row`; p0 is even and below px_end.
+__device__ __forceinline__ void yuv_load_group(YuvGroup& g, const ptx_yuv420_src& s, const YuvFrame& f, int row, int p0,
+                                               int px_end) {
+    const unsigned char* yp = f.y + (size_t)row * s.pitch_y + p0;
+    const size_t co = (size_t)(row >> 1) * s.pitch_c + (size_t)(p0 >> 1) * s.step_c;
+    const int rem = px_end - p0;
+    if (rem >= 16) {
+        g.y = *reinterpret_cast<const u32x4_any*>(yp);
+        if (s.step_c == 2) {
+            const bool vu = f.v < f.u;                               // V first (NV21 order)
+            const u32x4 q = *reinterpret_cast<const u32x4_any*>((vu ? f.v : f.u) + co);
+            const unsigned e0 = __builtin_amdgcn_perm(q.y, q.x, 0x06040200u), e1 = __builtin_amdgcn_perm(q.w, q.z, 0x06040200u);
+            const unsigned o0 = __builtin_amdgcn_perm(q.y, q.x, 0x07050301u), o1 = __builtin_amdgcn_perm(q.w, q.z, 0x07050301u);
+            g.c = vu ? u32x4{o0, o1, e0, e1} : u32x4{e0, e1, o0, o1};
+        } else {
+            const u32x2 a = *reinterpret_cast<const u32x2_any*>(f.u + co), b = *reinterpret_cast<const u32x2_any*>(f.v + co);
+            g.c = u32x4{a.x, a.y, b.x, b.y};
+        }
+    } else {
+        unsigned yy[4] = {0, 0, 0, 0}, cc[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < rem) yy[k >> 2] |= (unsigned)yp[k] << (8 * (k & 3));
+        const int nc = (rem + 1) >> 1;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k < nc) {
+                cc[k >> 2] |= (unsigned)f.u[co + (size_t)k * s.step_c] << (8 * (k & 3));
+                cc[2 + (k >> 2)] |= (unsigned)f.v[co + (size_t)k * s.step_c] << (8 * (k & 3));
+            }
+        g.y = u32x4{yy[0], yy[1], yy[2], yy[3]};
+        g.c = u32x4{cc[0], cc[1], cc[2], cc[3]};
+    }
+}
+
+// A negative sum gives 0: clamp below before the UNSIGNED shift, then min (not the signed clamp of the shifted value,
+// see resize_frames_u8_kernel on v_ashr_pk_u8_i32).
+__device__ __forceinline__ unsigned yuv_clip8(int sum) { return min((unsigned)max(sum, 0) >> 16, 255u); }
+
+// Converts the group and writes its RGB bytes to dst (16-byte aligned): 48 bytes, or only the 4-byte words that hold
+// one of the first `rem` pixels when the group is the partial last one of its row.
+__device__ __forceinline__ void yuv_stage_group(unsigned char* dst, const YuvGroup& g, const ptx_yuv420_src& s, int rem) {
+    const unsigned yw[4] = {g.y.x, g.y.y, g.y.z, g.y.w}, cw[4] = {g.c.x, g.c.y, g.c.z, g.c.w};
+    unsigned o[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};          // 16 x RGB, byte 3 p + c of the group in word (3 p + c) / 4
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int cb = (int)((cw[k >> 2] >> (8 * (k & 3))) & 255u) - 128;
+        const int cr = (int)((cw[2 + (k >> 2)] >> (8 * (k & 3))) & 255u) - 128;
+        const int rv = __mul24(s.krv, cr) + 32768;
+        const int gv = 32768 - __mul24(s.kgu, cb) - __mul24(s.kgv, cr);
+        const int bv = __mul24(s.kbu, cb) + 32768;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int p = 2 * k + h;
+            const int yy = __mul24(s.ky, (int)((yw[p >> 2] >> (8 * (p & 3))) & 255u) - s.y_off);
+            o[(3 * p) >> 2] |= yuv_clip8(yy + rv) << (8 * ((3 * p) & 3));
+            o[(3 * p + 1) >> 2] |= yuv_clip8(yy + gv) << (8 * ((3 * p + 1) & 3));
+            o[(3 * p + 2) >> 2] |= yuv_clip8(yy + bv) << (8 * ((3 * p + 2) & 3));
+        }
+    }
+    if (rem >= 16) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) *reinterpret_cast<u32x4*>(dst + 16 * q) = u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j)
+            if (4 * j < 3 * rem) *reinterpret_cast<unsigned*>(dst + 4 * j) = o[j];
+    }
+}
+
+// The YUV counterparts of resize_fetch_row and of the kernels' "registers -> row stage" step.  Lane l owns groups l,
+// 64 + l (prefetched in registers) and 128 + l, 192 + l, ... (rows of more than 2048 referenced pixels load those when
+// the row is staged).  The stage holds pixel e0 at byte 0, so the horizontal pass reads pixel c at (cmin - e0) * 3 +
+// (c - cmin) * 3: yuv_stage_row returns that first offset (0 or 3) as the RGB path returns its address mod 16.  The
+// last word written ends below (cmax - e0) * 3 + 3 <= W * 3 + 6, inside the stage's W * 3 + 16 bytes.
+__device__ __forceinline__ void yuv_fetch_row(YuvRow& r, int i, int nrows, const ptx_yuv420_src& s, const YuvFrame& f, int lo0,
+                                              int cmin, int px_end, int lane) {
+    if (i >= nrows) return;
+    const int e0 = cmin & ~1;
+    if (e0 + lane * 16 < px_end) yuv_load_group(r.g0, s, f, lo0 + i, e0 + lane * 16, px_end);
+    if (e0 + (64 + lane) * 16 < px_end) yuv_load_group(r.g1, s, f, lo0 + i, e0 + (64 + lane) * 16, px_end);
+}
+
+__device__ __forceinline__ int yuv_stage_row(unsigned char* sw, const YuvRow& r, const ptx_yuv420_src& s, const YuvFrame& f,
+                                             int row, int cmin, int px_end, int lane) {
+    const int e0 = cmin & ~1;
+    int p0 = e0 + lane * 16;
+    if (p0 < px_end) yuv_stage_group(sw + (p0 - e0) * 3, r.g0, s, px_end - p0);
+    p0 += 64 * 16;
+    if (p0 < px_end) yuv_stage_group(sw + (p0 - e0) * 3, r.g1, s, px_end - p0);
+    for (p0 += 64 * 16; p0 < px_end; p0 += 64 * 16) {
+        YuvGroup g;
+        yuv_load_group(g, s, f, row, p0, px_end);
+        yuv_stage_group(sw + (p0 - e0) * 3, g, s, px_end - p0);
+    }
+    return (cmin - e0) * 3;
+}
+
+// Host-side checks of a ptx_yuv420_src for N x T frames of H x W pixels (no device needed).
+inline int yuv_check(const ptx_yuv420_src* s, int C, int H, int W, const char* who) {
+    if (!s) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    if (C != 3) return fail(PTX_ERR_INVALID, "%s: C=%d, a YUV source converts to 3 channels", who, C);
+    if (!s->y || !s->u || !s->v) return fail(PTX_ERR_INVALID, "%s: null plane pointer", who);
+    if (s->pitch_y <= 0 || s->pitch_c <= 0)
+        return fail(PTX_ERR_INVALID, "%s: pitch_y=%d / pitch_c=%d must be positive", who, s->pitch_y, s->pitch_c);
+    if (s->step_c != 1 && s->step_c != 2) return fail(PTX_ERR_INVALID, "%s: step_c=%d must be 1 (planar) or 2 (interleaved)", who, s->step_c);
+    if (s->step_c == 2 && s->v != s->u + 1 && s->u != s->v + 1)
+        return fail(PTX_ERR_INVALID, "%s: interleaved chroma (step_c=2) needs v == u + 1 (or u == v + 1)", who);
+    const int64_t Hc = ((int64_t)H + 1) / 2, Wc = ((int64_t)W + 1) / 2;
+    if (s->pitch_y < W || s->pitch_c < Wc * s->step_c)
+        return fail(PTX_ERR_INVALID, "%s: pitch_y=%d / pitch_c=%d are shorter than a row (%d luma, %lld chroma bytes)", who,
+                    s->pitch_y, s->pitch_c, W, (long long)(Wc * s->step_c));
+    if ((int64_t)H * s->pitch_y > INT32_MAX || Hc * s->pitch_c > INT32_MAX)
+        return fail(PTX_ERR_UNSUPPORTED, "%s: a plane of a frame exceeds 32-bit indexing", who);
+    return PTX_OK;
+}
+
 // Launch shape of resize_frames_u8_kernel, or the reason there is none.  taps_h is the widest row's tap count, and a
 // row of support s has more than 2 s - 1 taps, so output rows advance by at most taps_h / 2 input rows: a band of b
 // output rows references at most b * taps_h / 2 + taps_h + 1 input rows (b when taps_h == 1: the axis is not resampled).

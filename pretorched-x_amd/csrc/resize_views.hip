@@ -21,14 +21,14 @@ namespace ptx {
 
 constexpr int kViewsMinSharedBand = 4;      // below this the shared pass re-reads too many halo rows: one window per workgroup
 
-template <int C>
+template <int C, bool YUV = false>
 __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, const unsigned char* __restrict__ f,
                                                               const int* __restrict__ frame_idx,
                                                               const int* __restrict__ row_lo, const int* __restrict__ row_n,
                                                               const int* __restrict__ row_k, const int* __restrict__ col_lo,
                                                               const int* __restrict__ col_n, const int* __restrict__ col_k,
                                                               void* __restrict__ y, ptx_norm_desc nd, ResizePlan pl, int shared,
-                                                              int clip0, int nclips) {
+                                                              int clip0, int nclips, ptx_yuv420_src ys) {
     extern __shared__ __attribute__((aligned(16))) unsigned char views_smem[];
     int* hdr = reinterpret_cast<int*>(views_smem);                  // [0] first, [1] one-past-last referenced column
     const int Rn = shared ? d.Ur : d.S, Cn = shared ? d.Uc : d.S;   // rows / columns this launch shape resamples per frame
@@ -69,7 +69,8 @@ __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, 
     const int SC = d.S * C, istride = pl.istride;
     const int half = 1 << (kResizeBits - 1);
     const int src_t = min(max(frame_idx[clip * d.T + ti], 0), d.Tv - 1);
-    const unsigned char* fin = f + (size_t)n * (size_t)d.stride_n + (size_t)src_t * (size_t)d.stride_t;
+    const unsigned char* fin = YUV ? nullptr : f + (size_t)n * (size_t)d.stride_n + (size_t)src_t * (size_t)d.stride_t;
+    const YuvFrame yf = YUV ? yuv_frame(ys, n, src_t) : YuvFrame{};      // a YUV source: the planes of ys, converted in the row staging
     row_lo += rbase + y0;
     row_n += rbase + y0;
     row_k += (size_t)(rbase + y0) * d.taps_h;
@@ -111,6 +112,7 @@ __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, 
     const int* rk = pl.k_in_lds ? t_k + Cn * d.taps_w : row_k;      // [y1 - y0][taps_h]
     const int cmin = hdr[0];
     const int span_bytes = max(hdr[1] - cmin, 0) * C;               // <= W * C
+    const int px_end = max(hdr[1], cmin);                           // one past the last referenced column
 
     int r = y0;
     while (r < y1) {
@@ -131,11 +133,15 @@ __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, 
         // row's bytes already on their way in registers
         unsigned char* sw = stage + wave * pl.stage_stride;
         ResizeRow pre = {};
-        resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
+        YuvRow ypre = {};
+        if constexpr (YUV) yuv_fetch_row(ypre, 0 + wave, nrows, ys, yf, lo0, cmin, px_end, lane);
+        else resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
         for (int i0 = 0; i0 < nrows; i0 += 4) {
             const int i = i0 + wave;
             int off = 0;
-            if (i < nrows) {
+            if constexpr (YUV) {
+                if (i < nrows) off = yuv_stage_row(sw, ypre, ys, yf, lo0 + i, cmin, px_end, lane);
+            } else if (i < nrows) {
                 int vb, ve, end;
                 const unsigned char* g = resize_row_span(fin, lo0 + i, d.W, cmin, C, span_bytes, off, vb, ve, end);
                 if (lane < vb - off) sw[off + lane] = (unsigned char)pre.head;
@@ -147,7 +153,8 @@ __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, 
                 if (lane < end - ve) sw[ve + lane] = (unsigned char)pre.tail;
             }
             __syncthreads();
-            resize_fetch_row(pre, i + 4, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
+            if constexpr (YUV) yuv_fetch_row(ypre, i + 4, nrows, ys, yf, lo0, cmin, px_end, lane);
+            else resize_fetch_row(pre, i + 4, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
             if (i < nrows) {
                 for (int x = lane; x < Cn; x += 64) {
                     const int lo = t_clo[x], nn = t_cn[x];
@@ -263,7 +270,8 @@ __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, 
 }
 
 // Launch shape, or the reason there is none.  *shared: 1 = one workgroup per (frame, band of union rows), 0 = per window.
-static int views_plan(const ptx_views_desc* d, const void* y, ResizePlan* p, int* shared, const char* who) {
+static int views_plan(const ptx_views_desc* d, const void* y, ResizePlan* p, int* shared, const char* who,
+                      const ptx_yuv420_src* src = nullptr) {
     if (!d) return fail(PTX_ERR_INVALID, "%s: null descriptor", who);
     if (d->N <= 0 || d->Tv <= 0 || d->H <= 0 || d->W <= 0 || d->S <= 0 || d->clips <= 0 || d->T <= 0)
         return fail(PTX_ERR_INVALID, "%s: non-positive extent (N=%d Tv=%d H=%d W=%d S=%d clips=%d T=%d)", who, d->N, d->Tv, d->H,
@@ -274,7 +282,9 @@ static int views_plan(const ptx_views_desc* d, const void* y, ResizePlan* p, int
     if (d->share < PTX_VIEWS_SHARE_AUTO || d->share > PTX_VIEWS_SHARE_NEVER)
         return fail(PTX_ERR_INVALID, "%s: share=%d is not a PTX_VIEWS_SHARE_* value", who, d->share);
     const int64_t frame_bytes = (int64_t)d->H * d->W * d->C;
-    if (d->stride_t < frame_bytes || d->stride_n < frame_bytes)
+    if (src) {                                                       // the source addresses its frames itself: d's strides are not read
+        if (int s = yuv_check(src, d->C, d->H, d->W, who)) return s;
+    } else if (d->stride_t < frame_bytes || d->stride_n < frame_bytes)
         return fail(PTX_ERR_INVALID, "%s: stride_t=%lld / stride_n=%lld are smaller than a frame (%lld bytes)", who,
                     (long long)d->stride_t, (long long)d->stride_n, (long long)frame_bytes);
     const int64_t V = (int64_t)d->clips * d->crops;
@@ -329,16 +339,16 @@ extern "C" int ptx_resize_views_u8_supported(const ptx_views_desc* desc) {
     return shared ? 2 : 1;
 }
 
-extern "C" int ptx_resize_views_u8(const ptx_views_desc* desc, const uint8_t* video, const int32_t* frame_idx,
-                                   const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
-                                   const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm,
-                                   ptx_stream_t stream) {
-    const char* who = "ptx_resize_views_u8";
+// Both sources: `video` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.
+static int resize_views_run(const ptx_views_desc* desc, const uint8_t* video, const ptx_yuv420_src* src, const int32_t* frame_idx,
+                            const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                            const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream,
+                            const char* who) {
     ResizePlan p;
     int shared;
-    int s = views_plan(desc, y, &p, &shared, who);
+    int s = views_plan(desc, y, &p, &shared, who, src);
     if (s) return s;
-    if (!video || !frame_idx || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k)
+    if ((!video && !src) || !frame_idx || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k)
         return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     ptx_norm_desc nd = {};
     if (desc->out_mode != PTX_RESIZE_OUT_U8) {
@@ -354,7 +364,12 @@ extern "C" int ptx_resize_views_u8(const ptx_views_desc* desc, const uint8_t* vi
     hipStream_t st = (hipStream_t)stream;
 #define PTX_VIEWS_LAUNCH(CH)                                                                                                \
     hipLaunchKernelGGL(resize_views_u8_kernel<CH>, grid, dim3(256), p.lds_bytes, st, *desc, video, frame_idx, row_lo, row_n, \
-                       row_k, col_lo, col_n, col_k, y, nd, p, shared, clip0, nclips)
+                       row_k, col_lo, col_n, col_k, y, nd, p, shared, clip0, nclips, ptx_yuv420_src{})
+    if (src) {
+        hipLaunchKernelGGL((resize_views_u8_kernel<3, true>), grid, dim3(256), p.lds_bytes, st, *desc, (const unsigned char*)nullptr, frame_idx, row_lo,
+                           row_n, row_k, col_lo, col_n, col_k, y, nd, p, shared, clip0, nclips, *src);
+        return hip_check(hipGetLastError(), who);
+    }
     switch (desc->C) {
         case 1: PTX_VIEWS_LAUNCH(1); break;
         case 2: PTX_VIEWS_LAUNCH(2); break;
@@ -363,4 +378,30 @@ extern "C" int ptx_resize_views_u8(const ptx_views_desc* desc, const uint8_t* vi
     }
 #undef PTX_VIEWS_LAUNCH
     return hip_check(hipGetLastError(), "ptx_resize_views_u8 launch");
+}
+
+extern "C" int ptx_resize_views_u8(const ptx_views_desc* desc, const uint8_t* video, const int32_t* frame_idx,
+                                   const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                                   const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm,
+                                   ptx_stream_t stream) {
+    return resize_views_run(desc, video, nullptr, frame_idx, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream,
+                            "ptx_resize_views_u8");
+}
+
+extern "C" int ptx_resize_views_yuv420_supported(const ptx_views_desc* desc, const ptx_yuv420_src* src) {
+    const char* who = "ptx_resize_views_yuv420_supported";
+    ResizePlan p;
+    int shared;
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who), 0;
+    if (views_plan(desc, nullptr, &p, &shared, who, src) != PTX_OK) return 0;
+    return shared ? 2 : 1;
+}
+
+extern "C" int ptx_resize_views_yuv420(const ptx_views_desc* desc, const ptx_yuv420_src* src, const int32_t* frame_idx,
+                                       const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                                       const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm,
+                                       ptx_stream_t stream) {
+    const char* who = "ptx_resize_views_yuv420";
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    return resize_views_run(desc, nullptr, src, frame_idx, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who);
 }

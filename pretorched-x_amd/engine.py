@@ -632,9 +632,11 @@ class Engine:
         is fused into the stem's fold kernel: no fp32 NCDHW clip is ever materialised.  `opts`: anything
         with mean / std / input_space / input_range (default: the model's own pretrained settings).
         `transform`: a `transforms.TransformFrames(.., out="frames")` applied to the frames first (resize + crop of
-        frames of any size on the device, utils.py:53-64); None: the frames already have the input size."""
-        if transform is not None:
-            from .transforms import apply_frames_transform
+        frames of any size on the device, utils.py:53-64); None: the frames already have the input size.
+        `frames` may be a `transforms.YUV420` source (NV12 / I420 planes); it needs a transform, whose kernel converts
+        the colours while it stages the rows."""
+        from .transforms import YUV420, apply_frames_transform
+        if transform is not None or isinstance(frames, YUV420):
             frames = apply_frames_transform(transform, frames)
         opts = model if opts is None else opts
         get = (lambda k: opts[k]) if isinstance(opts, dict) else (lambda k: getattr(opts, k))
@@ -672,7 +674,8 @@ class Engine:
             return self._forward_eager(model, plan, frames)
 
     def forward_views(self, model, video, opts=None, views=None, reduce="softmax", chunk=None):
-        """Decoded uint8 video [N,Tv,H,W,3] (or [Tv,H,W,3]: one video) -> fp32 [N, classes]: the mean over `views`
+        """Decoded uint8 video [N,Tv,H,W,3] (or [Tv,H,W,3]: one video; or a `transforms.YUV420` source with planes
+        [N,Tv,H,W] / [Tv,H,W]) -> fp32 [N, classes]: the mean over `views`
         (a `transforms.SampleViews`: clips x crops, sampled on the device) of softmax(logits) (reduce="softmax"), of the
         logits ("logits"), or the logits of every view [N, V, classes] in the model's dtype (None).
         float32 models take the views as uint8 frames through forward_frames (views.out == "frames", `opts` as there);

@@ -44,9 +44,16 @@ def run_views(video, views, run, max_batch, reduce="softmax", chunk=None, who="f
     the N * nv clips into logits, the logits of all chunks land in one [N*V, K] buffer, ptx_views_mean reduces it."""
     if reduce not in ("softmax", "logits", None):
         raise PtxError("%s: reduce must be 'softmax', 'logits' or None, got %r" % (who, reduce))
-    if not isinstance(video, torch.Tensor) or video.dim() not in (4, 5):
-        raise PtxError("%s: video must be a uint8 CUDA tensor [N,Tv,H,W,3] or [Tv,H,W,3]" % who)
-    N, V = (video.shape[0] if video.dim() == 5 else 1), views.num_views
+    from .transforms import YUV420
+    if isinstance(video, YUV420):                                  # planes [N,Tv,H,W] or [Tv,H,W]: the source knows N
+        if video.lead not in (2, 3):
+            raise PtxError("%s: a YUV420 video has planes [N,Tv,H,W] or [Tv,H,W]" % who)
+        N = video.N if video.lead == 3 else 1
+    elif not isinstance(video, torch.Tensor) or video.dim() not in (4, 5):
+        raise PtxError("%s: video must be a uint8 CUDA tensor [N,Tv,H,W,3] or [Tv,H,W,3] (or a transforms.YUV420)" % who)
+    else:
+        N = video.shape[0] if video.dim() == 5 else 1
+    V = views.num_views
     nv = views_chunk(N, V, max_batch) if chunk is None else chunk
     if not isinstance(nv, int) or isinstance(nv, bool) or nv < 1:
         raise PtxError("%s: chunk must be a positive number of views, got %r" % (who, chunk))

@@ -133,6 +133,63 @@ def synth_clips(batch, frames, size, seed=99, channels=3):
     return torch.randn(batch, channels, frames, size, size, generator=g)
 
 
+def synth_yuv420(count, height, width, seed, content="noise"):
+    """Synthetic decoder output: uint8 numpy planes (y [count,H,W], u, v [count,ceil(H/2),ceil(W/2)]).  "noise": seeded
+    bytes from numpy's legacy generator in all three planes (independent chroma noise drives many pixels out of gamut,
+    so both ends of the conversion's clamp are exercised); "extremes": constant frames cycling through (Y, Cb, Cr) =
+    (255, 255, 255), (0, 0, 0), (16, 240, 16)."""
+    import numpy as np
+    hc, wc = (height + 1) // 2, (width + 1) // 2
+    if content == "extremes":
+        triples = [(255, 255, 255), (0, 0, 0), (16, 240, 16)]
+        pick = [triples[i % 3] for i in range(count)]
+        return tuple(np.stack([np.full(shape, t[k], np.uint8) for t in pick])
+                     for k, shape in enumerate(((height, width), (hc, wc), (hc, wc))))
+    if content != "noise":
+        raise ValueError("synth_yuv420: content must be 'noise' or 'extremes'")
+    rs = np.random.RandomState(int(seed))
+    y = rs.randint(0, 256, (count, height, width)).astype(np.uint8)
+    u = rs.randint(0, 256, (count, hc, wc)).astype(np.uint8)
+    v = rs.randint(0, 256, (count, hc, wc)).astype(np.uint8)
+    return y, u, v
+
+
+def yuv420_source(planes, layout, device, matrix="bt709", color_range="limited", lead_shape=None):
+    """A `transforms.YUV420` over numpy planes (y, u, v as `synth_yuv420` returns them) in one of the memory layouts a
+    decoder produces: "nv12" / "i420" (packed frames, even sizes), "planes" (y, u, v tensors), "planes_uv" (y and an
+    interleaved uv plane), "nv12_pitched" (y and uv are views into wider buffers: row pitch W + 14 / 2 * ceil(W/2) + 6
+    bytes, base pointers 1 and 3 bytes past the allocation).  lead_shape: reshape the leading [count] to it."""
+    import numpy as np
+    import torch
+    from .transforms import YUV420
+    y, u, v = (np.ascontiguousarray(a) for a in planes)
+    count, H, W = y.shape
+    hc, wc = u.shape[1:]
+    lead = (count,) if lead_shape is None else tuple(lead_shape)
+    kw = dict(matrix=matrix, color_range=color_range)
+    uv = np.stack([u, v], -1)                                       # [count, hc, wc, 2]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    if layout == "nv12":
+        return YUV420.from_nv12(dev(np.concatenate([y, uv.reshape(count, hc, W)], 1)).view(lead + (H * 3 // 2, W)), **kw)
+    if layout == "i420":
+        packed = np.concatenate([y.reshape(count, -1), u.reshape(count, -1), v.reshape(count, -1)], 1)
+        return YUV420.from_i420(dev(packed).view(lead + (H * 3 // 2, W)), **kw)
+    if layout == "planes":
+        return YUV420(dev(y).view(lead + (H, W)), dev(u).view(lead + (hc, wc)), dev(v).view(lead + (hc, wc)), **kw)
+    if layout == "planes_uv":
+        return YUV420(dev(y).view(lead + (H, W)), dev(uv).view(lead + (hc, wc, 2)), **kw)
+    if layout == "nv12_pitched":
+        py, pc = W + 14, 2 * wc + 6
+        by = torch.zeros(count * H * py + 1, dtype=torch.uint8, device=device)
+        bc = torch.zeros(count * hc * pc + 3, dtype=torch.uint8, device=device)
+        ty = by[1:].view(lead + (H, py))[..., :W]
+        tc = bc[3:].view(lead + (hc, pc))[..., :2 * wc].unflatten(-1, (wc, 2))
+        ty.copy_(dev(y).view(lead + (H, W)))
+        tc.copy_(dev(uv).view(lead + (hc, wc, 2)))
+        return YUV420(ty, tc, **kw)
+    raise ValueError("yuv420_source: unknown layout %r" % (layout,))
+
+
 def synth_frames(count, height, width, seed, content="noise"):
     """Synthetic decoded frames, uint8 numpy [count, height, width, 3]: seeded noise from numpy's legacy generator (its
     stream is stable across numpy versions, so fixtures store outputs only) or a smooth integer gradient."""

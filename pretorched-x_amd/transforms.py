@@ -20,6 +20,11 @@ uint8 frames:
   views.  Frames are read in place through an index table and the crop windows of a sampled frame share one
   horizontal pass.  `model.forward_views` feeds the views to a model chunk by chunk and averages the predictions.
 
+* `YUV420` describes decoder output (NV12 / I420 planes, any row pitch) and is accepted wherever RGB frames are:
+  the two resize kernels convert to RGB while they stage an input row on chip (`yuv_coefficients` is the integer
+  contract, `yuv420_to_rgb_numpy` its numpy statement), so the RGB frame never exists in HBM and every output bit
+  is that of the RGB path on the converted frames.
+
 Image loading and video decoding stay host work and are not on this path.
 """
 import collections
@@ -30,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import NormDesc, PtxError, ResizeDesc, ViewsDesc, check
+from ._lib import NormDesc, PtxError, ResizeDesc, ViewsDesc, Yuv420Src, check
 
 PRECISION_BITS = 22       # PIL's fixed-point coefficient precision for 8-bit channels (32 - 8 - 2)
 
@@ -66,6 +71,170 @@ class FramesToTensor:
         if lead == 5:
             return out
         return out[0] if lead == 4 else out[0, :, 0]
+
+
+# ---------------------------------------------------------------------------------------------
+# YUV 4:2:0 sources: the colour contract (integers, 16 fractional bits) and the container of a decoder's planes
+# ---------------------------------------------------------------------------------------------
+YUV_BITS = 16
+_YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}              # Kr, Kb
+_YUV_RANGES = {"limited": (255.0 / 219.0, 255.0 / 224.0, 16), "full": (1.0, 1.0, 0)}   # luma scale, chroma scale, y_off
+
+
+def yuv_coefficients(matrix="bt709", color_range="limited"):
+    """(y_off, ky, krv, kgu, kgv, kbu): the integer coefficients (2**16 fixed point, rounded from float64) of
+        R = clip8((ky*y' + krv*cr + 32768) >> 16)     G = clip8((ky*y' - kgu*cb - kgv*cr + 32768) >> 16)
+        B = clip8((ky*y' + kbu*cb + 32768) >> 16)     with y' = Y - y_off, cb = Cb - 128, cr = Cr - 128."""
+    if matrix not in _YUV_MATRICES:
+        raise PtxError("YUV420: matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+    if color_range not in _YUV_RANGES:
+        raise PtxError("YUV420: color_range must be 'limited' or 'full', got %r" % (color_range,))
+    kr, kb = _YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    sy, sc, y_off = _YUV_RANGES[color_range]
+    q = lambda v: int(round(v * float(1 << YUV_BITS)))
+    return (y_off, q(sy), q(2.0 * (1.0 - kr) * sc), q(2.0 * kb * (1.0 - kb) / kg * sc), q(2.0 * kr * (1.0 - kr) / kg * sc),
+            q(2.0 * (1.0 - kb) * sc))
+
+
+def yuv420_to_rgb_numpy(y, u, v, matrix="bt709", color_range="limited"):
+    """The kernels' colour conversion in numpy: uint8 planes y [..,H,W], u, v [..,ceil(H/2),ceil(W/2)] -> uint8
+    [..,H,W,3].  The chroma sample of pixel (r, c) is (r >> 1, c >> 1).  The host-side model the tests compare with;
+    not a fallback."""
+    y_off, ky, krv, kgu, kgv, kbu = yuv_coefficients(matrix, color_range)
+    y, u, v = (np.asarray(a) for a in (y, u, v))
+    H, W = y.shape[-2:]
+    if u.shape != v.shape or u.shape[-2:] != ((H + 1) // 2, (W + 1) // 2) or u.shape[:-2] != y.shape[:-2]:
+        raise PtxError("yuv420_to_rgb_numpy: chroma planes %s / %s do not match the %dx%d luma plane" % (u.shape, v.shape, H, W))
+    rows, cols = np.arange(H) >> 1, np.arange(W) >> 1
+    yy = ky * (y.astype(np.int64) - y_off)
+    cb = u.astype(np.int64)[..., rows, :][..., cols] - 128
+    cr = v.astype(np.int64)[..., rows, :][..., cols] - 128
+    half = 1 << (YUV_BITS - 1)
+    rgb = np.stack([(yy + krv * cr + half) >> YUV_BITS, (yy - kgu * cb - kgv * cr + half) >> YUV_BITS,
+                    (yy + kbu * cb + half) >> YUV_BITS], -1)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+class YUV420:
+    """Decoded YUV 4:2:0 frames (8 bit) as a decoder hands them back, accepted wherever RGB frames are:
+
+        YUV420(y, uv, ...)     y [..,H,W], uv [..,ceil(H/2),ceil(W/2),2]         (NV12 surfaces, any row pitch)
+        YUV420(y, u, v, ...)   u, v [..,ceil(H/2),ceil(W/2)]                      (planar)
+        YUV420.from_nv12(packed, ...) / YUV420.from_i420(packed, ...)            packed [..,H*3/2,W], even H and W
+
+    with 0, 1 or 2 leading dimensions ([H,W], [T,H,W], [N,T,H,W]: `lead` = 1, 2, 3 as an RGB tensor of rank lead + 2).
+    matrix: "bt709" | "bt601"; color_range: "limited" | "full" (see `yuv_coefficients`).  Planes are read in place when
+    their rows are contiguous runs (a uv plane: last strides (2, 1)) -- row pitch, frame and video strides and base
+    alignment are arbitrary --, anything else costs one `.contiguous()` copy of that plane at the call."""
+
+    def __init__(self, y, u, v=None, matrix="bt709", color_range="limited"):
+        self.coefficients = yuv_coefficients(matrix, color_range)
+        self.matrix, self.color_range = matrix, color_range
+        planes = (y, u) if v is None else (y, u, v)
+        for p in planes:
+            if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8:
+                raise PtxError("YUV420: planes must be uint8 tensors, got %s" % (
+                    p.dtype if isinstance(p, torch.Tensor) else type(p).__name__,))
+        if len({p.device for p in planes}) != 1:
+            raise PtxError("YUV420: planes are on different devices (%s)" % ", ".join(str(p.device) for p in planes))
+        if y.dim() not in (2, 3, 4):
+            raise PtxError("YUV420: expected a luma plane [N,T,H,W], [T,H,W] or [H,W], got shape %s" % (tuple(y.shape),))
+        H, W = int(y.shape[-2]), int(y.shape[-1])
+        want = tuple(y.shape[:-2]) + ((H + 1) // 2, (W + 1) // 2)
+        for name, p in (("uv", u),) if v is None else (("u", u), ("v", v)):
+            if tuple(p.shape) != want + ((2,) if v is None else ()):
+                raise PtxError("YUV420: the %s plane has shape %s, a %dx%d luma plane of shape %s needs %s (ceil(H/2) x "
+                               "ceil(W/2) samples)" % (name, tuple(p.shape), H, W, tuple(y.shape),
+                                                       want + ((2,) if v is None else ())))
+        self.y, self.u, self.v = y, u, v                            # v is None: u holds the interleaved pairs
+        self.H, self.W, self.lead, self.device = H, W, y.dim() - 1, y.device
+        self.N = int(y.shape[0]) if y.dim() == 4 else 1
+        self.T = int(y.shape[-3]) if y.dim() >= 3 else 1
+        self.lead_shape = tuple(y.shape[:-2])
+
+    @staticmethod
+    def _packed(packed, who):
+        if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
+            raise PtxError("YUV420.%s: packed frames must be a uint8 tensor" % who)
+        if packed.dim() not in (2, 3, 4):
+            raise PtxError("YUV420.%s: expected [N,T,H*3/2,W], [T,H*3/2,W] or [H*3/2,W], got shape %s" % (who, tuple(packed.shape)))
+        rows, W = int(packed.shape[-2]), int(packed.shape[-1])
+        H = rows * 2 // 3
+        if rows % 3 or H % 2 or W % 2 or H == 0 or W == 0:
+            raise PtxError("YUV420.%s: a packed frame is H*3/2 rows of W bytes with even H and W, got %d rows of %d (pass "
+                           "planes for odd sizes)" % (who, rows, W))
+        return H, W
+
+    @classmethod
+    def from_nv12(cls, packed, matrix="bt709", color_range="limited"):
+        """Packed NV12 [..,H*3/2,W]: H rows of luma, then H/2 rows of interleaved Cb Cr pairs.  Views, no copy."""
+        H, W = cls._packed(packed, "from_nv12")
+        return cls(packed[..., :H, :], packed[..., H:, :].unflatten(-1, (W // 2, 2)), None, matrix, color_range)
+
+    @classmethod
+    def from_i420(cls, packed, matrix="bt709", color_range="limited"):
+        """Packed I420 [..,H*3/2,W]: the luma plane, then the Cb plane, then the Cr plane (H/2 x W/2 each, as flat
+        runs).  Views when each packed frame is contiguous, otherwise `reshape` copies the frames once."""
+        H, W = cls._packed(packed, "from_i420")
+        flat = packed.reshape(tuple(packed.shape[:-2]) + (H * 3 // 2 * W,))
+        q = (H // 2) * (W // 2)
+        return cls(flat[..., :H * W].unflatten(-1, (H, W)), flat[..., H * W:H * W + q].unflatten(-1, (H // 2, W // 2)),
+                   flat[..., H * W + q:].unflatten(-1, (H // 2, W // 2)), matrix, color_range)
+
+    @staticmethod
+    def _rows_in_place(p, inner):
+        """p's trailing dimensions `inner` (a row, or a row of pairs) are a contiguous run and rows do not overlap."""
+        k = len(inner)
+        want, run = [], 1
+        for n in reversed(inner):
+            want.append(run)
+            run *= n
+        if any(p.shape[-1 - i] > 1 and p.stride(-1 - i) != want[i] for i in range(k)):
+            return False
+        return p.shape[-1 - k] == 1 or p.stride(-1 - k) >= run
+
+    def source(self, who="YUV420"):
+        """(Yuv420Src, tensors to keep alive): the kernels' descriptor of the planes, checked and copied where needed."""
+        if self.device.type != "cuda":
+            raise PtxError("%s: the planes of a YUV420 source must be uint8 CUDA tensors (no CPU fallback)" % who)
+        if self.N * self.T == 0 or self.H * self.W == 0:
+            raise PtxError("%s: empty batch" % who)
+        Hc, Wc = (self.H + 1) // 2, (self.W + 1) // 2
+        y = self.y if self._rows_in_place(self.y, (self.W,)) else self.y.contiguous()
+        if self.v is None:
+            u = self.u if self._rows_in_place(self.u, (Wc, 2)) else self.u.contiguous()
+            c, keep = u.select(-1, 0), (y, u)
+            pu, pv, step, pitch_c = u.data_ptr(), u.data_ptr() + 1, 2, (u.stride(-3) if Hc > 1 else 2 * Wc)
+        else:
+            u, v = self.u, self.v
+            if not (self._rows_in_place(u, (Wc,)) and self._rows_in_place(v, (Wc,)) and
+                    all(u.stride(i) == v.stride(i) or u.shape[i] == 1 for i in range(u.dim() - 1))):
+                u, v = u.contiguous(), v.contiguous()              # one pitch and one set of strides serve both pointers
+            c, keep = u, (y, u, v)
+            pu, pv, step, pitch_c = u.data_ptr(), v.data_ptr(), 1, (u.stride(-2) if Hc > 1 else Wc)
+
+        def strides(p, nd):                                         # (video, frame) strides of a plane with nd trailing dims
+            lead = p.dim() - nd
+            st = p.stride(lead - 1) if lead >= 1 and p.shape[lead - 1] > 1 else 0
+            sn = p.stride(lead - 2) if lead >= 2 and p.shape[lead - 2] > 1 else 0
+            return sn, st
+
+        s = Yuv420Src()
+        s.y, s.u, s.v = y.data_ptr(), pu, pv
+        s.stride_n_y, s.stride_t_y = strides(y, 2)
+        s.stride_n_c, s.stride_t_c = strides(c, 2)
+        s.pitch_y, s.pitch_c, s.step_c = (y.stride(-2) if self.H > 1 else self.W), pitch_c, step
+        s.y_off, s.ky, s.krv, s.kgu, s.kgv, s.kbu = self.coefficients
+        return s, keep
+
+    def to_rgb_numpy(self):
+        """uint8 [..,H,W,3] through `yuv420_to_rgb_numpy` (host; tests and examples)."""
+        if self.v is None:
+            u, v = self.u[..., 0], self.u[..., 1]
+        else:
+            u, v = self.u, self.v
+        return yuv420_to_rgb_numpy(self.y.cpu().numpy(), u.cpu().numpy(), v.cpu().numpy(), self.matrix, self.color_range)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -230,7 +399,11 @@ class TransformFrames:
 
     def __call__(self, frames):
         """uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3], any H, W  ->
-        out="tensor": [N,3,T,S,S] | [3,T,S,S] | [3,S,S] (fp32 or bf16);  out="frames": uint8, same rank, H, W -> S, S."""
+        out="tensor": [N,3,T,S,S] | [3,T,S,S] | [3,S,S] (fp32 or bf16);  out="frames": uint8, same rank, H, W -> S, S.
+        A `YUV420` source is taken in place of the frames (converted while the kernel stages its rows: the same bits as
+        the call on the converted frames); the result's rank follows `src.lead` as it follows the tensor's rank."""
+        if isinstance(frames, YUV420):
+            return self._call_yuv(frames)
         if not isinstance(frames, torch.Tensor):
             raise PtxError("TransformFrames: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
         if frames.dim() not in (3, 4, 5):
@@ -266,9 +439,37 @@ class TransformFrames:
         return y[0] if lead == 4 else y[0, :, 0]
 
 
+    def _call_yuv(self, src):
+        ysrc, keep = src.source("TransformFrames")
+        N, T, H, W, S = src.N, src.T, src.H, src.W, self.size
+        with torch.cuda.device(src.device):
+            buf, offs, taps_h, taps_w = self._device_tables(H, W, src.device)
+            if self.out == "frames":
+                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((N, T, S, S, 3), device=src.device, dtype=torch.uint8)
+            else:
+                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+                y = torch.empty((N, 3, T, S, S), device=src.device, dtype=self.dtype)
+            desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
+            base = buf.data_ptr()
+            check(_lib.lib().ptx_resize_frames_yuv420(C.byref(desc), C.byref(ysrc), *[C.c_void_p(base + o) for o in offs],
+                                                      C.c_void_p(y.data_ptr()), C.byref(self.norm),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "ptx_resize_frames_yuv420")
+            del keep                                                 # planes (copies included) stayed alive up to the launch
+        if self.out == "frames":
+            return y.view(src.lead_shape + (S, S, 3))
+        if src.lead == 3:
+            return y
+        return y[0] if src.lead == 2 else y[0, :, 0]
+
+
 def apply_frames_transform(transform, frames, who="forward_frames"):
-    """The `transform=` hook of forward_frames: a TransformFrames with out="frames", applied to the raw frames."""
+    """The `transform=` hook of forward_frames: a TransformFrames with out="frames", applied to the raw frames.  A
+    `YUV420` source has no RGB frames to pass on, so it needs one (a crop-only transform serves frames of the input size)."""
     if transform is None:
+        if isinstance(frames, YUV420):
+            raise PtxError("%s: a YUV420 source needs transform=TransformFrames(.., out='frames') (the colour conversion "
+                           "runs in its row staging; a crop-only transform serves frames that have the input size)" % who)
         return frames
     if not isinstance(transform, TransformFrames) or transform.out != "frames":
         raise PtxError("%s: transform must be a pretorched.transforms.TransformFrames with out='frames', got %r" % (
@@ -458,7 +659,9 @@ class SampleViews:
     def sample(self, video, v0=0, nv=None):
         """Views v0 .. v0 + nv - 1 only (default: all from v0 on), shaped as __call__'s result with V -> nv.  The
         video is read in place: any view whose frames are contiguous [H,W,3] blocks (slices and steps over N and Tv
-        included) is taken without a copy."""
+        included) is taken without a copy.  A `YUV420` source ([N,Tv,..] or [Tv,..] planes) is read in place of the video."""
+        if isinstance(video, YUV420):
+            return self._sample_yuv(video, v0, nv)
         if not isinstance(video, torch.Tensor):
             raise PtxError("SampleViews: video must be a uint8 CUDA tensor, got %s" % type(video).__name__)
         if video.dim() not in (4, 5):
@@ -499,3 +702,30 @@ class SampleViews:
                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                   "ptx_resize_views_u8")
         return y if lead == 5 else y[0]
+
+    def _sample_yuv(self, src, v0, nv):
+        if src.lead not in (2, 3):
+            raise PtxError("SampleViews: expected a YUV420 video with planes [N,Tv,H,W] or [Tv,H,W], got one frame")
+        ysrc, keep = src.source("SampleViews")
+        N, Tv, H, W = src.N, src.T, src.H, src.W
+        V = self.num_views
+        nv = V - v0 if nv is None else nv
+        if not (isinstance(v0, int) and isinstance(nv, int) and 0 <= v0 and 1 <= nv and v0 + nv <= V):
+            raise PtxError("SampleViews: view range [%r, %r + %r) is outside the %d views" % (v0, v0, nv, V))
+        S, T = self.size, self.num_frames
+        with torch.cuda.device(src.device):
+            buf, offs, t = self._device_tables(H, W, src.device)
+            idx = self._device_indices(Tv, src.device)
+            if self.out == "frames":
+                y = torch.empty((N, nv, T, S, S, 3), device=src.device, dtype=torch.uint8)
+            else:
+                y = torch.empty((N, nv, 3, T, S, S), device=src.device, dtype=self.dtype)
+            desc = self._desc(N, Tv, H, W, 3, 0, 0, t, v0, nv)         # the source carries the frame strides
+            base = buf.data_ptr()
+            check(_lib.lib().ptx_resize_views_yuv420(C.byref(desc), C.byref(ysrc), C.c_void_p(idx.data_ptr()),
+                                                     *[C.c_void_p(base + o) for o in offs],
+                                                     C.c_void_p(y.data_ptr()), C.byref(self.norm),
+                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "ptx_resize_views_yuv420")
+            del keep
+        return y if src.lead == 3 else y[0]

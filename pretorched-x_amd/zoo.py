@@ -625,6 +625,11 @@ class TRN(nn.Module):
         [B*T, H, W, 3] view (normalisation fused into its stem), then the relation head; bit-identical to forward() on
         the FramesToTensor(opts) output rearranged to [B, T, 3, H, W].  opts: default the backbone's settings."""
         from ._lib import PtxError
+        from .transforms import YUV420, apply_frames_transform
+        if isinstance(frames, YUV420):                              # NV12 / I420 planes [B,T,H,W]: converted by the transform
+            if frames.lead != 3:
+                raise PtxError("TRN.forward_frames: expected a YUV420 source with planes [B,T,H,W]")
+            frames, transform = apply_frames_transform(transform, frames, "TRN.forward_frames"), None
         if not isinstance(frames, torch.Tensor) or frames.dim() != 5:
             raise PtxError("TRN.forward_frames: expected uint8 CUDA frames [B,T,H,W,3]")
         if frames.shape[1] != self.num_segments:
