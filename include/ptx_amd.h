@@ -503,6 +503,34 @@ int ptx_resize_frames_yuv420(const ptx_resize_desc* desc, const ptx_yuv420_src* 
                              const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
                              const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k,
                              void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+/* One window and flips PER CLIP in one launch (TransformImage's random_crop / random_hflip / random_vflip,
+ * transforms/utils.py:36-70: RandomCrop(max(input_size)), RandomHorizontalFlip(), RandomVerticalFlip() after the resize,
+ * drawn by the caller).  The tables are ptx_resize_frames_u8's, but they cover the WHOLE resized frame: h rows and w
+ * columns (row_k [h][taps_h], col_k [w][taps_w]); desc->Ho x desc->Wo stays the output window.  Output pixel (r, c) of
+ * every frame of clip n is resized-frame pixel
+ *   (top_n + (vflip_n ? Ho-1-r : r),  left_n + (hflip_n ? Wo-1-c : c)),     windows: DEVICE pointer, [N].
+ * The arithmetic per output pixel is unchanged: clip n's result is bit-identical to ptx_resize_frames_u8 on that clip with
+ * rows [top_n, top_n + Ho) and columns [left_n, left_n + Wo) of the same tables, reversed where a flip asks for it; the
+ * yuv420 form is bit-identical to the u8 form on the converted frames.  The kernel clamps top / left into [0, h - Ho] /
+ * [0, w - Wo] and treats any non-zero flip as 1, so a wrong window gives wrong pixels, never a stray access.  The host
+ * checks what needs no device: everything ptx_resize_frames_u8 checks, a null windows pointer, h < Ho, w < Wo.
+ * _supported: 1 if the call runs (ptx_resize_frames_u8_supported's conditions and tables that hold a window).         */
+typedef struct ptx_resize_window {
+    int32_t top, left;       /* first row / column of the window in the resized frame */
+    int32_t hflip, vflip;    /* 0 / 1: mirror the window's columns / rows             */
+} ptx_resize_window;
+int ptx_resize_frames_u8_windows_supported(const ptx_resize_desc* desc, int32_t h, int32_t w);
+int ptx_resize_frames_u8_windows(const ptx_resize_desc* desc, const uint8_t* frames,
+                                 const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, /* [h], [h], [h][taps_h] */
+                                 const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, /* [w], [w], [w][taps_w] */
+                                 int32_t h, int32_t w, const ptx_resize_window* windows,
+                                 void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+int ptx_resize_frames_yuv420_windows_supported(const ptx_resize_desc* desc, const ptx_yuv420_src* src, int32_t h, int32_t w);
+int ptx_resize_frames_yuv420_windows(const ptx_resize_desc* desc, const ptx_yuv420_src* src,
+                                     const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
+                                     const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k,
+                                     int32_t h, int32_t w, const ptx_resize_window* windows,
+                                     void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
 /* ptx_resize_views_u8 on a YUV video: the source's strides address the frames, desc->stride_n / desc->stride_t are
  * IGNORED.  _supported returns 0 / 1 / 2 as ptx_resize_views_u8_supported does. */
 int ptx_resize_views_yuv420_supported(const ptx_views_desc* desc, const ptx_yuv420_src* src);

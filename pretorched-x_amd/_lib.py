@@ -99,6 +99,11 @@ class ResizeDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "T", "H", "W", "C", "Ho", "Wo", "taps_h", "taps_w", "out_mode")]
 
 
+class ResizeWindow(C.Structure):
+    """ptx_resize_window: one clip's crop window in the resized frame and its flips (ptx_resize_frames_*_windows)."""
+    _fields_ = [(n, C.c_int32) for n in ("top", "left", "hflip", "vflip")]
+
+
 PTX_RESIZE_OUT_U8, PTX_RESIZE_OUT_F32, PTX_RESIZE_OUT_BF16 = 0, 1, 2
 PTX_RESIZE_MAX_TAPS = 64
 PTX_VIEWS_MAX_CROPS = 4
@@ -222,6 +227,12 @@ SIGNATURES = {
     "ptx_resize_frames_yuv420_supported": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src)]),
     "ptx_resize_frames_yuv420": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _P,
                                            C.POINTER(NormDesc), _P]),
+    "ptx_resize_frames_u8_windows_supported": (C.c_int, [C.POINTER(ResizeDesc), _I, _I]),
+    "ptx_resize_frames_u8_windows": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P,
+                                               C.POINTER(NormDesc), _P]),
+    "ptx_resize_frames_yuv420_windows_supported": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src), _I, _I]),
+    "ptx_resize_frames_yuv420_windows": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _I, _I,
+                                                   _P, _P, C.POINTER(NormDesc), _P]),
     "ptx_resize_views_yuv420_supported": (C.c_int, [C.POINTER(ViewsDesc), C.POINTER(Yuv420Src)]),
     "ptx_resize_views_yuv420": (C.c_int, [C.POINTER(ViewsDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _P, _P,
                                           C.POINTER(NormDesc), _P]),

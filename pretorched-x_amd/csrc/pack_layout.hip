@@ -282,13 +282,24 @@ __global__ void __launch_bounds__(256) fold_kw_frames_u8_kernel(const unsigned c
 
 // YUV: the frames are the planes of `ys` (f is unused) and a row is converted to RGB while it is staged (resize_common.h);
 // everything from the staged row on is the same code.
-template <int C, bool YUV = false>
+// WIN (ptx_resize_frames_*_windows): the tables cover the whole resized frame (win.h rows, win.w columns) and every clip
+// has a window of its own: output pixel (r, c) of clip n takes table row top_n + (vflip_n ? Ho-1-r : r) and table column
+// left_n + (hflip_n ? Wo-1-c : c).  Only the table INDEX changes: the workgroup copies those entries to LDS where the
+// fixed-window kernel copies entries y0 + i and x, and everything derived from the copied entries (the referenced column
+// span, the head / tail split of the row staging, the YUV group origin, the chunks of a band, whose rows now may descend)
+// follows per clip.  top / left are clamped so the window lies inside the tables.
+struct ResizeWindows {
+    const ptx_resize_window* wins;   // device, [N]
+    int h, w;                        // entries of the row / column tables
+};
+
+template <int C, bool YUV = false, bool WIN = false>
 __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d, const unsigned char* __restrict__ f,
                                                                const int* __restrict__ row_lo, const int* __restrict__ row_n,
                                                                const int* __restrict__ row_k, const int* __restrict__ col_lo,
                                                                const int* __restrict__ col_n, const int* __restrict__ col_k,
                                                                void* __restrict__ y, ptx_norm_desc nd, ResizePlan pl,
-                                                               ptx_yuv420_src ys) {
+                                                               ptx_yuv420_src ys, ResizeWindows win) {
     extern __shared__ __attribute__((aligned(16))) unsigned char resize_smem[];
     int* hdr = reinterpret_cast<int*>(resize_smem);                 // [0] first, [1] one-past-last referenced column
     int* t_clo = hdr + 4;                                           // clamped table entries: columns [Wo], [Wo] ...
@@ -307,6 +318,16 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
     const int half = 1 << (kResizeBits - 1);
     const unsigned char* fin = YUV ? nullptr : f + (size_t)frame * d.H * d.W * C;
     const YuvFrame yf = YUV ? yuv_frame(ys, frame / d.T, frame % d.T) : YuvFrame{};
+    int top = 0, left = 0, hflip = 0, vflip = 0;
+    if constexpr (WIN) {
+        const ptx_resize_window wn = win.wins[frame / d.T];
+        top = min(max(wn.top, 0), max(win.h - d.Ho, 0));
+        left = min(max(wn.left, 0), max(win.w - d.Wo, 0));
+        hflip = wn.hflip != 0;
+        vflip = wn.vflip != 0;
+    }
+    auto col_of = [&](int x) { return WIN ? left + (hflip ? d.Wo - 1 - x : x) : x; };      // table column of output column x
+    auto row_of = [&](int r) { return WIN ? top + (vflip ? d.Ho - 1 - r : r) : r; };        // table row of output row r
 
     if (tid == 0) {
         hdr[0] = d.W;
@@ -317,7 +338,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
         int cmin = d.W, cmax = 0;
         for (int x = tid; x < d.Wo; x += 256) {
             int lo, n;
-            resize_entry(col_lo, col_n, x, d.W, d.taps_w, lo, n);
+            resize_entry(col_lo, col_n, col_of(x), d.W, d.taps_w, lo, n);
             t_clo[x] = lo;
             t_cn[x] = n;
             cmin = min(cmin, lo);
@@ -327,19 +348,40 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
         atomicMax(&hdr[1], cmax);
         for (int i = tid; i < y1 - y0; i += 256) {
             int lo, n;
-            resize_entry(row_lo, row_n, y0 + i, d.H, min(d.taps_h, pl.lds_rows), lo, n);
+            resize_entry(row_lo, row_n, row_of(y0 + i), d.H, min(d.taps_h, pl.lds_rows), lo, n);
             t_rlo[i] = lo;
             t_rn[i] = n;
         }
         if (pl.k_in_lds) {
             const int nck = d.Wo * d.taps_w, nrk = (y1 - y0) * d.taps_h;
-            for (int i = tid; i < nck; i += 256) t_k[i] = col_k[i];
-            for (int i = tid; i < nrk; i += 256) t_k[nck + i] = row_k[(size_t)y0 * d.taps_h + i];
+            if constexpr (WIN) {
+                for (int i = tid; i < nck; i += 256) {
+                    const int x = i / d.taps_w;
+                    t_k[i] = col_k[(size_t)col_of(x) * d.taps_w + (i - x * d.taps_w)];
+                }
+                for (int i = tid; i < nrk; i += 256) {
+                    const int ri = i / d.taps_h;
+                    t_k[nck + i] = row_k[(size_t)row_of(y0 + ri) * d.taps_h + (i - ri * d.taps_h)];
+                }
+            } else {
+                for (int i = tid; i < nck; i += 256) t_k[i] = col_k[i];
+                for (int i = tid; i < nrk; i += 256) t_k[nck + i] = row_k[(size_t)y0 * d.taps_h + i];
+            }
         }
     }
     __syncthreads();
     const int* ck = pl.k_in_lds ? t_k : col_k;                                            // [Wo][taps_w]
     const int* rk = pl.k_in_lds ? t_k + d.Wo * d.taps_w : row_k + (size_t)y0 * d.taps_h;  // [y1 - y0][taps_h]
+    // coefficients of output column x / output row `row`: the LDS copies are in output order, the global tables of the
+    // windows kernel are indexed through the clip's window
+    auto col_coeffs = [&](int x) {
+        if constexpr (WIN) return pl.k_in_lds ? ck + x * d.taps_w : col_k + (size_t)col_of(x) * d.taps_w;
+        else return ck + x * d.taps_w;
+    };
+    auto row_coeffs = [&](int row) {
+        if constexpr (WIN) return pl.k_in_lds ? rk + (row - y0) * d.taps_h : row_k + (size_t)row_of(row) * d.taps_h;
+        else return rk + (row - y0) * d.taps_h;
+    };
     const int cmin = hdr[0];
     const int span_bytes = max(hdr[1] - cmin, 0) * C;               // <= W * C
     const int px_end = max(hdr[1], cmin);                           // one past the last referenced column
@@ -390,7 +432,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
                 for (int x = lane; x < d.Wo; x += 64) {
                     const int lo = t_clo[x], n = t_cn[x];
                     const unsigned char* p = sw + off + (lo - cmin) * C;
-                    const int* kk = ck + x * d.taps_w;
+                    const int* kk = col_coeffs(x);
                     int acc[C];
 #pragma unroll
                     for (int c = 0; c < C; ++c) acc[c] = half;
@@ -416,7 +458,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
                 const int yy = it / q4, q = it - yy * q4, row = r + yy;
                 const int lo = t_rlo[row - y0], n = t_rn[row - y0];
                 const unsigned char* p = inter + (lo - lo0) * istride + q * 4;
-                const int* kk = rk + (row - y0) * d.taps_h;
+                const int* kk = row_coeffs(row);
                 int acc[4] = {half, half, half, half};
                 for (int j = 0; j < n; ++j) {
                     const int k = kk[j];
@@ -448,7 +490,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
                 const int cin = (nd.swap_rb && (c == 0 || c == 2)) ? 2 - c : c;
                 const int lo = t_rlo[row - y0], n = t_rn[row - y0];
                 const unsigned char* p = inter + (lo - lo0) * istride + cin;
-                const int* kk = rk + (row - y0) * d.taps_h;
+                const int* kk = row_coeffs(row);
                 int xo[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) xo[e] = min(xg * 4 + e, d.Wo - 1) * C;
@@ -862,15 +904,29 @@ extern "C" int ptx_resize_frames_u8_supported(const ptx_resize_desc* desc) {
     return resize_plan(desc, nullptr, &p, "ptx_resize_frames_u8_supported") == PTX_OK;
 }
 
-// Both sources: `frames` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.
+// The windows entry points' own host-side checks: tables of h x w entries that hold an Ho x Wo window (no device needed).
+static int resize_windows_check(const ptx_resize_desc* d, int h, int w, const char* who) {
+    if (h < d->Ho || w < d->Wo)
+        return fail(PTX_ERR_INVALID, "%s: the %dx%d window does not fit the %dx%d resized frame of the tables", who, d->Ho, d->Wo, h, w);
+    if ((int64_t)h * d->taps_h > INT32_MAX || (int64_t)w * d->taps_w > INT32_MAX)
+        return fail(PTX_ERR_UNSUPPORTED, "%s: a table exceeds 32-bit indexing", who);
+    return PTX_OK;
+}
+
+// Both sources: `frames` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.  Both kernels:
+// the fixed window (win == nullptr: the tables hold the window's entries) or one window per clip (win->wins, tables of
+// win->h x win->w entries).
 static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames, const ptx_yuv420_src* src, const int32_t* row_lo,
                              const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo, const int32_t* col_n,
-                             const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream, const char* who) {
+                             const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream, const char* who,
+                             const ResizeWindows* win = nullptr) {
     ResizePlan p;
     int s = resize_plan(desc, y, &p, who);
     if (s) return s;
     if (src && (s = yuv_check(src, desc->C, desc->H, desc->W, who))) return s;
-    if ((!frames && !src) || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k) return fail(PTX_ERR_INVALID, "%s: null pointer", who);
+    if (win && (s = resize_windows_check(desc, win->h, win->w, who))) return s;
+    if ((!frames && !src) || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k || (win && !win->wins))
+        return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     ptx_norm_desc nd = {};
     if (desc->out_mode != PTX_RESIZE_OUT_U8) {
         if (!norm) return fail(PTX_ERR_INVALID, "%s: null norm descriptor", who);
@@ -881,20 +937,32 @@ static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames,
     }
     const dim3 grid((unsigned)((int64_t)desc->N * desc->T * cdiv(desc->Ho, p.band)));
     hipStream_t st = (hipStream_t)stream;
-#define PTX_RESIZE_LAUNCH(CH)                                                                                               \
-    hipLaunchKernelGGL(resize_frames_u8_kernel<CH>, grid, dim3(256), p.lds_bytes, st, *desc, frames, row_lo, row_n, row_k, \
-                       col_lo, col_n, col_k, y, nd, p, ptx_yuv420_src{})
+    const ResizeWindows rw = win ? *win : ResizeWindows{};
+    const unsigned char* none = nullptr;
+#define PTX_RESIZE_LAUNCH(CH, YUV, WIN)                                                                                        \
+    hipLaunchKernelGGL((resize_frames_u8_kernel<CH, YUV, WIN>), grid, dim3(256), p.lds_bytes, st, *desc, YUV ? none : frames, \
+                       row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, YUV ? *src : ptx_yuv420_src{}, rw)
+#define PTX_RESIZE_LAUNCH_C(WIN)                          \
+    switch (desc->C) {                                    \
+        case 1: PTX_RESIZE_LAUNCH(1, false, WIN); break;  \
+        case 2: PTX_RESIZE_LAUNCH(2, false, WIN); break;  \
+        case 3: PTX_RESIZE_LAUNCH(3, false, WIN); break;  \
+        default: PTX_RESIZE_LAUNCH(4, false, WIN); break; \
+    }
     if (src) {
-        hipLaunchKernelGGL((resize_frames_u8_kernel<3, true>), grid, dim3(256), p.lds_bytes, st, *desc, (const unsigned char*)nullptr, row_lo, row_n,
-                           row_k, col_lo, col_n, col_k, y, nd, p, *src);
+        if (win) {
+            PTX_RESIZE_LAUNCH(3, true, true);
+        } else {
+            PTX_RESIZE_LAUNCH(3, true, false);
+        }
         return hip_check(hipGetLastError(), who);
     }
-    switch (desc->C) {
-        case 1: PTX_RESIZE_LAUNCH(1); break;
-        case 2: PTX_RESIZE_LAUNCH(2); break;
-        case 3: PTX_RESIZE_LAUNCH(3); break;
-        default: PTX_RESIZE_LAUNCH(4); break;
+    if (win) {
+        PTX_RESIZE_LAUNCH_C(true)
+        return hip_check(hipGetLastError(), who);
     }
+    PTX_RESIZE_LAUNCH_C(false)
+#undef PTX_RESIZE_LAUNCH_C
 #undef PTX_RESIZE_LAUNCH
     return hip_check(hipGetLastError(), "ptx_resize_frames_u8 launch");
 }
@@ -917,6 +985,41 @@ extern "C" int ptx_resize_frames_yuv420(const ptx_resize_desc* desc, const ptx_y
     const char* who = "ptx_resize_frames_yuv420";
     if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
     return resize_frames_run(desc, nullptr, src, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who);
+}
+
+extern "C" int ptx_resize_frames_u8_windows_supported(const ptx_resize_desc* desc, int32_t h, int32_t w) {
+    const char* who = "ptx_resize_frames_u8_windows_supported";
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, who) == PTX_OK && resize_windows_check(desc, h, w, who) == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_u8_windows(const ptx_resize_desc* desc, const uint8_t* frames, const int32_t* row_lo,
+                                            const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                                            const int32_t* col_n, const int32_t* col_k, int32_t h, int32_t w,
+                                            const ptx_resize_window* windows, void* y, const ptx_norm_desc* norm,
+                                            ptx_stream_t stream) {
+    const ResizeWindows win = {windows, h, w};
+    return resize_frames_run(desc, frames, nullptr, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream,
+                             "ptx_resize_frames_u8_windows", &win);
+}
+
+extern "C" int ptx_resize_frames_yuv420_windows_supported(const ptx_resize_desc* desc, const ptx_yuv420_src* src, int32_t h,
+                                                          int32_t w) {
+    const char* who = "ptx_resize_frames_yuv420_windows_supported";
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, who) == PTX_OK && yuv_check(src, desc->C, desc->H, desc->W, who) == PTX_OK &&
+           resize_windows_check(desc, h, w, who) == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_yuv420_windows(const ptx_resize_desc* desc, const ptx_yuv420_src* src, const int32_t* row_lo,
+                                                const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                                                const int32_t* col_n, const int32_t* col_k, int32_t h, int32_t w,
+                                                const ptx_resize_window* windows, void* y, const ptx_norm_desc* norm,
+                                                ptx_stream_t stream) {
+    const char* who = "ptx_resize_frames_yuv420_windows";
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    const ResizeWindows win = {windows, h, w};
+    return resize_frames_run(desc, nullptr, src, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, &win);
 }
 
 // y[r][0..W) = x[r][0..W), y[r][W..ld) = 0: gives rows whose length is not a multiple of 4 floats a 16-byte pitch

@@ -8,12 +8,14 @@ uint8 frames:
 * `FramesToTensor` is the tensor half alone (same fp32 operations in the same order: bit-identical), for frames
   that already have the model's input size.  Models go one step further with `model.forward_frames`, which
   fuses it into the stem's fold kernel so the fp32 clip never exists in HBM.
-* `TransformFrames` is both halves in one HIP launch: bilinear resize + crop (+ horizontal flip) of frames of
+* `TransformFrames` is both halves in one HIP launch: bilinear resize + crop (+ flips) of frames of
   any size, then either the normalised clip (`out="tensor"`) or the resized uint8 frames (`out="frames"`, what
   `forward_frames(.., transform=tf)` takes).  PIL resamples uint8 images in integer arithmetic (22-bit
   fixed-point coefficients, horizontal pass, uint8 intermediate, vertical pass); the coefficient tables are
   built here on the host in float64 exactly as PIL builds them and the kernel does integer work only, so the
-  result equals PIL's to the bit.  Crop and flip are folded into the tables.
+  result equals PIL's to the bit.  Crop and flip are folded into the tables.  With `random_crop` / `random_hflip` /
+  `random_vflip` (TransformImage's training switches, utils.py:36-70) every clip of a batch gets a window and flips of
+  its own, still in one launch: the tables then cover the whole resized frame and the kernel indexes them per clip.
 
 * `SampleViews` is test-time multi-view sampling of a whole decoded video: `clips` temporal clips x `crops` spatial
   crops, each resized + cropped as `TransformFrames` does (same tables, same bits), in one HIP launch per range of
@@ -306,21 +308,42 @@ def _select(table, start, count, reverse=False):
     return np.ascontiguousarray(lo), np.ascontiguousarray(n), np.ascontiguousarray(k[:, :taps])
 
 
-def build_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False):
-    """Row and column tables of resize + crop (+ flip) for H x W frames: only the S output rows / columns of the
-    window get entries.  Returns a dict with `rows`, `cols` ((lo, n, k) each), `S`, `resized`, `window`."""
+def _check_taps(rows, cols, H, W, h, w):
+    for name, t in (("rows", rows), ("columns", cols)):
+        if t[2].shape[1] > _lib.PTX_RESIZE_MAX_TAPS:
+            raise PtxError("TransformFrames: down-scaling the %s of a %dx%d frame to %dx%d needs %d taps, the kernel's cap is "
+                           "PTX_RESIZE_MAX_TAPS = %d" % (name, H, W, h, w, t[2].shape[1], _lib.PTX_RESIZE_MAX_TAPS))
+
+
+def build_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False):
+    """Row and column tables of resize + crop (+ flips) for H x W frames: only the S output rows / columns of the
+    window get entries (reversed where a flip asks for it).  Returns a dict with `rows`, `cols` ((lo, n, k) each), `S`,
+    `resized`, `window`."""
     S = int(max(input_size))
     h, w = resized_size(H, W, input_size, scale, preserve_aspect_ratio)
     if h <= 0 or w <= 0:
         raise PtxError("TransformFrames: resized frame %dx%d is empty" % (h, w))
     top, left = crop_window(h, w, S, crop)
-    rows = _select(resize_axis_table(H, h), top, S)
+    rows = _select(resize_axis_table(H, h), top, S, reverse=bool(vflip))
     cols = _select(resize_axis_table(W, w), left, S, reverse=bool(hflip))
-    for name, t in (("rows", rows), ("columns", cols)):
-        if t[2].shape[1] > _lib.PTX_RESIZE_MAX_TAPS:
-            raise PtxError("TransformFrames: down-scaling the %s of a %dx%d frame to %dx%d needs %d taps, the kernel's cap is "
-                           "PTX_RESIZE_MAX_TAPS = %d" % (name, H, W, h, w, t[2].shape[1], _lib.PTX_RESIZE_MAX_TAPS))
+    _check_taps(rows, cols, H, W, h, w)
     return {"rows": rows, "cols": cols, "S": S, "resized": (h, w), "window": (top, left)}
+
+
+def build_frame_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True):
+    """Row and column tables of the WHOLE resized frame (h rows, w columns): what the per-clip windows launch indexes.
+    `build_tables(.., crop=(top, left), hflip=.., vflip=..)` is the slice [top, top + S) x [left, left + S) of these,
+    reversed where a flip asks for it.  Returns a dict with `rows`, `cols`, `S`, `resized`."""
+    S = int(max(input_size))
+    h, w = resized_size(H, W, input_size, scale, preserve_aspect_ratio)
+    if h <= 0 or w <= 0:
+        raise PtxError("TransformFrames: resized frame %dx%d is empty" % (h, w))
+    if h < S or w < S:
+        raise PtxError("TransformFrames: a %dx%d crop does not fit the resized %dx%d frame (padding crops are not "
+                       "offered)" % (S, S, h, w))
+    rows, cols = resize_axis_table(H, h), resize_axis_table(W, w)
+    _check_taps(rows, cols, H, W, h, w)
+    return {"rows": rows, "cols": cols, "S": S, "resized": (h, w)}
 
 
 def apply_tables_numpy(frame, tables):
@@ -349,13 +372,19 @@ class TransformFrames:
 
     opts: a model or settings dict with input_size / input_space / input_range / mean / std.  scale and
     preserve_aspect_ratio as in TransformImage (utils.py:36-59); crop: "center" (CenterCrop(max(input_size))) or an
-    explicit (top, left) in the resized frame; hflip: flip the cropped window horizontally; dtype: torch.float32
-    or torch.bfloat16 (the fp32 value rounded once) for out="tensor"."""
+    explicit (top, left) in the resized frame; hflip / vflip: flip the cropped window horizontally / vertically; dtype:
+    torch.float32 or torch.bfloat16 (the fp32 value rounded once) for out="tensor".
+
+    random_crop / random_hflip / random_vflip (TransformImage's switches of the same names, utils.py:36-70): every CLIP of a
+    call gets a window / flips of its own, drawn by `draw` from `generator` (None: torch's default CPU generator, so
+    `torch.manual_seed` governs) and shared by all frames of the clip; the whole batch is still one launch and the draw is
+    kept as `last_params`.  `tf(frames, params=p)` applies given parameters instead (on any TransformFrames)."""
 
     CACHE_SIZE = 8
 
     def __init__(self, opts, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, out="tensor",
-                 dtype=torch.float32):
+                 dtype=torch.float32, *, random_crop=False, random_hflip=False, random_vflip=False, vflip=False,
+                 generator=None):
         if out not in ("tensor", "frames"):
             raise PtxError("TransformFrames: out must be 'tensor' or 'frames', got %r" % (out,))
         if dtype not in (torch.float32, torch.bfloat16):
@@ -369,7 +398,18 @@ class TransformFrames:
         self.mean, self.std = list(_opt(opts, "mean")), list(_opt(opts, "std"))
         self.norm = NormDesc.make(self.mean, self.std, self.input_space, self.input_range)
         self.scale, self.preserve_aspect_ratio = float(scale), bool(preserve_aspect_ratio)
-        self.crop, self.hflip, self.out, self.dtype = crop, bool(hflip), out, dtype
+        self.crop, self.hflip, self.vflip, self.out, self.dtype = crop, bool(hflip), bool(vflip), out, dtype
+        self.random_crop, self.random_hflip, self.random_vflip = bool(random_crop), bool(random_hflip), bool(random_vflip)
+        if self.random_crop and not isinstance(crop, str):
+            raise PtxError("TransformFrames: random_crop=True draws the window; it cannot be combined with crop=%r" % (crop,))
+        if self.random_hflip and self.hflip:
+            raise PtxError("TransformFrames: random_hflip=True draws the flip; it cannot be combined with hflip=True")
+        if self.random_vflip and self.vflip:
+            raise PtxError("TransformFrames: random_vflip=True draws the flip; it cannot be combined with vflip=True")
+        if generator is not None and not isinstance(generator, torch.Generator):
+            raise PtxError("TransformFrames: generator must be a torch.Generator or None, got %r" % (generator,))
+        self.random = self.random_crop or self.random_hflip or self.random_vflip
+        self.generator, self.last_params = generator, None
         self.size = int(max(self.input_size))
         if not isinstance(crop, str):
             crop_window(1 << 30, 1 << 30, self.size, crop)          # a malformed or negative window fails here
@@ -379,15 +419,69 @@ class TransformFrames:
 
     def tables(self, H, W):
         """Host tables for H x W frames (numpy; see build_tables)."""
-        return build_tables(H, W, self.input_size, self.scale, self.preserve_aspect_ratio, self.crop, self.hflip)
+        return build_tables(H, W, self.input_size, self.scale, self.preserve_aspect_ratio, self.crop, self.hflip, self.vflip)
 
-    def _device_tables(self, H, W, device):
-        key = (H, W, str(device))
+    def frame_tables(self, H, W):
+        """Host tables of the whole resized frame of H x W frames (numpy; see build_frame_tables)."""
+        return build_frame_tables(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
+
+    def draw(self, N, H, W):
+        """Parameters of N clips of H x W frames: a CPU int32 tensor [N, 4] of (top, left, hflip, vflip) in the resized
+        frame.  Per clip, in order (torchvision's consumption order for RandomCrop, RandomHorizontalFlip,
+        RandomVerticalFlip): random_crop draws top = randint(0, h - S + 1), then left = randint(0, w - S + 1); random_hflip
+        draws rand(1) < 0.5; random_vflip draws rand(1) < 0.5.  A switch that is off consumes nothing and gives the
+        constructor's crop / hflip / vflip."""
+        S, g = self.size, self.generator
+        h, w = resized_size(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
+        if self.random_crop:
+            crop_window(h, w, S, (0, 0))                            # the frame must hold a window
+        else:
+            top, left = crop_window(h, w, S, self.crop)
+        hf, vf = int(self.hflip), int(self.vflip)
+        out = torch.empty((int(N), 4), dtype=torch.int32)
+        for n in range(int(N)):
+            if self.random_crop:
+                top = int(torch.randint(0, h - S + 1, (1,), generator=g))
+                left = int(torch.randint(0, w - S + 1, (1,), generator=g))
+            if self.random_hflip:
+                hf = int(torch.rand(1, generator=g) < 0.5)
+            if self.random_vflip:
+                vf = int(torch.rand(1, generator=g) < 0.5)
+            out[n, 0], out[n, 1], out[n, 2], out[n, 3] = top, left, hf, vf
+        return out
+
+    def check_params(self, params, N, H, W):
+        """`params` ([N, 4] integers: an array or a CPU tensor) as a CPU int32 tensor, or PtxError: N does not match, a
+        window does not fit the resized frame of H x W frames, a flip is not 0 / 1."""
+        if isinstance(params, torch.Tensor):
+            if params.is_cuda:
+                raise PtxError("TransformFrames: params must be an integer array or a CPU tensor [N, 4], got a CUDA tensor")
+            params = params.numpy()
+        p = np.asarray(params)
+        if p.dtype.kind not in "iu":
+            raise PtxError("TransformFrames: params must hold integers, got dtype %s" % (p.dtype,))
+        if p.ndim != 2 or p.shape[1] != 4:
+            raise PtxError("TransformFrames: params must be [N, 4] (top, left, hflip, vflip), got shape %s" % (p.shape,))
+        if p.shape[0] != N:
+            raise PtxError("TransformFrames: params hold %d clips, the frames hold N = %d" % (p.shape[0], N))
+        p = p.astype(np.int64)
+        S = self.size
+        h, w = resized_size(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
+        for n, (top, left, hf, vf) in enumerate(p.tolist()):
+            if top < 0 or left < 0 or top + S > h or left + S > w:
+                raise PtxError("TransformFrames: params[%d]: the %dx%d crop at (%d, %d) does not fit the resized %dx%d frame "
+                               "(padding crops are not offered)" % (n, S, S, top, left, h, w))
+            if hf not in (0, 1) or vf not in (0, 1):
+                raise PtxError("TransformFrames: params[%d]: a flip must be 0 or 1, got hflip=%d vflip=%d" % (n, hf, vf))
+        return torch.from_numpy(p.astype(np.int32))
+
+    def _device_tables(self, H, W, device, whole=False):
+        key = (H, W, str(device)) + (("frame",) if whole else ())
         hit = self._cache.get(key)
         if hit is not None:
             self._cache.move_to_end(key)
             return hit
-        t = self.tables(H, W)
+        t = self.frame_tables(H, W) if whole else self.tables(H, W)
         parts = [a.reshape(-1) for a in t["rows"] + t["cols"]]
         offs = np.cumsum([0] + [p.size for p in parts])
         buf = torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(device)     # one small upload per input size
@@ -397,13 +491,16 @@ class TransformFrames:
             self._cache.popitem(last=False)
         return hit
 
-    def __call__(self, frames):
+    def __call__(self, frames, params=None):
         """uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3], any H, W  ->
         out="tensor": [N,3,T,S,S] | [3,T,S,S] | [3,S,S] (fp32 or bf16);  out="frames": uint8, same rank, H, W -> S, S.
         A `YUV420` source is taken in place of the frames (converted while the kernel stages its rows: the same bits as
-        the call on the converted frames); the result's rank follows `src.lead` as it follows the tensor's rank."""
+        the call on the converted frames); the result's rank follows `src.lead` as it follows the tensor's rank.
+        A random transform draws one (top, left, hflip, vflip) per clip (N draws for [N,T,..], one for the lower ranks;
+        per-image augmentation of an image batch is [N,1,H,W,3]) and keeps the draw as `last_params`; params ([N, 4]
+        integers, see `check_params`) applies given parameters instead.  Both are one launch."""
         if isinstance(frames, YUV420):
-            return self._call_yuv(frames)
+            return self._call_yuv(frames, params)
         if not isinstance(frames, torch.Tensor):
             raise PtxError("TransformFrames: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
         if frames.dim() not in (3, 4, 5):
@@ -418,6 +515,13 @@ class TransformFrames:
         if N * T == 0:
             raise PtxError("TransformFrames: empty batch")
         S = self.size
+        if params is not None or self.random:
+            y = self._call_windows(f5, None, N, T, H, W, frames.device, params)
+            if self.out == "frames":
+                return y.view(tuple(frames.shape[:-3]) + (S, S, Cc))
+            if lead == 5:
+                return y
+            return y[0] if lead == 4 else y[0, :, 0]
         with torch.cuda.device(frames.device):
             buf, offs, taps_h, taps_w = self._device_tables(H, W, frames.device)
             if self.out == "frames":
@@ -439,9 +543,44 @@ class TransformFrames:
         return y[0] if lead == 4 else y[0, :, 0]
 
 
-    def _call_yuv(self, src):
+    def _call_windows(self, f5, ysrc, N, T, H, W, device, params):
+        """The per-clip windows launch on frames f5 [N,T,H,W,3] or, when ysrc is given, on a YUV source: the drawn or the
+        given parameters, the tables of the whole resized frame (cached per input size), one small upload of the
+        parameters."""
+        S = self.size
+        if params is None:
+            p = self.last_params = self.draw(N, H, W)
+        else:
+            p = self.check_params(params, N, H, W)
+        with torch.cuda.device(device):
+            buf, offs, taps_h, taps_w = self._device_tables(H, W, device, whole=True)
+            h, w = resized_size(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
+            wins = p.contiguous().to(device)
+            if self.out == "frames":
+                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((N, T, S, S, 3), device=device, dtype=torch.uint8)
+            else:
+                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+                y = torch.empty((N, 3, T, S, S), device=device, dtype=self.dtype)
+            desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
+            base = buf.data_ptr()
+            name = "ptx_resize_frames_u8_windows" if ysrc is None else "ptx_resize_frames_yuv420_windows"
+            source = C.c_void_p(f5.data_ptr()) if ysrc is None else C.byref(ysrc)
+            check(getattr(_lib.lib(), name)(C.byref(desc), source, *[C.c_void_p(base + o) for o in offs], h, w,
+                                            C.c_void_p(wins.data_ptr()), C.c_void_p(y.data_ptr()), C.byref(self.norm),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
+        return y
+
+    def _call_yuv(self, src, params=None):
         ysrc, keep = src.source("TransformFrames")
         N, T, H, W, S = src.N, src.T, src.H, src.W, self.size
+        if params is not None or self.random:
+            y = self._call_windows(None, ysrc, N, T, H, W, src.device, params)
+            del keep
+            if self.out == "frames":
+                return y.view(src.lead_shape + (S, S, 3))
+            if src.lead == 3:
+                return y
+            return y[0] if src.lead == 2 else y[0, :, 0]
         with torch.cuda.device(src.device):
             buf, offs, taps_h, taps_w = self._device_tables(H, W, src.device)
             if self.out == "frames":
