@@ -531,6 +531,49 @@ int ptx_resize_frames_yuv420_windows(const ptx_resize_desc* desc, const ptx_yuv4
                                      const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k,
                                      int32_t h, int32_t w, const ptx_resize_window* windows,
                                      void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+/* Tables PER CLIP in one launch: every clip has a resize geometry of its own (per-clip short-side jitter,
+ * RandomResizedCrop), not only a window.  The arguments are ptx_resize_frames_u8's / _yuv420's, and every table has a
+ * leading clip dimension: row_lo / row_n [N][Ho], row_k [N][Ho][taps_h], col_lo / col_n [N][Wo], col_k [N][Wo][taps_w];
+ * desc->taps_h / taps_w is the common pitch (the largest tap count of any clip; unused slots are never read).
+ * The arithmetic per output pixel is unchanged: clip n's result is bit-identical to ptx_resize_frames_u8 on that clip with
+ * that clip's tables, and the yuv420 form to the u8 form on the converted frames.  Entries are clamped to the frame as
+ * everywhere: a wrong table gives wrong pixels, never a stray access.  The host checks what ptx_resize_frames_u8 checks.
+ * _supported: ptx_resize_frames_u8_supported's / _yuv420_supported's conditions.                                         */
+int ptx_resize_frames_u8_tables_supported(const ptx_resize_desc* desc);
+int ptx_resize_frames_u8_tables(const ptx_resize_desc* desc, const uint8_t* frames,
+                                const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, /* [N][Ho], [N][Ho], [N][Ho][taps_h] */
+                                const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, /* [N][Wo], [N][Wo], [N][Wo][taps_w] */
+                                void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+int ptx_resize_frames_yuv420_tables_supported(const ptx_resize_desc* desc, const ptx_yuv420_src* src);
+int ptx_resize_frames_yuv420_tables(const ptx_resize_desc* desc, const ptx_yuv420_src* src,
+                                    const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
+                                    const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k,
+                                    void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+/* The builder of those tables, on the device: one small launch writes the six per-clip tables from one geometry row per
+ * clip, so a call with fresh random geometries uploads N * 40 bytes and builds no table on the host.  A row means, in PIL
+ * terms: crop the box [box_top, +box_h) x [box_left, +box_w) out of the H x W frame; resize it to h x w with
+ * Image.BILINEAR (an axis with box extent == resized extent is not resampled: one tap of 2^22); crop the Ho x Wo window at
+ * (top, left) of that; mirror if hflip, flip if vflip.  Cropping first and resizing the crop equals the resize table of
+ * (box extent -> resized extent) with every lo shifted by the box origin, which is what is written: per axis PIL's
+ * precompute_coeffs + normalize_coeffs_8bpc in IEEE fp64 without contraction, in this order --
+ *   scale = n_in / n_out, fs = max(scale, 1), ss = 1 / fs, center = (i + 0.5) * scale,
+ *   lo = max((int)(center - fs + 0.5), 0), hi = min((int)(center + fs + 0.5), n_in), n = hi - lo,
+ *   w_j = 1 - |(j + lo - center + 0.5) * ss| (0 if not positive), summed sequentially over j, w_j / sum if sum != 0,
+ *   k_j = (int)(w_j * 4194304.0 + 0.5);  slots n .. taps - 1 are written as 0
+ * -- so an entry has the bits of the host builder of the other entry points.  desc: N, H, W, Ho, Wo and the pitches
+ * taps_h / taps_w (>= every n: for a down-scale n <= 2 * ceil(n_in / n_out) + 1) as the launch will get them.  geoms:
+ * DEVICE pointer, [N]; the tables are DEVICE pointers the caller sized as above.  A garbage row is safe: the box is clamped
+ * into the frame, h / w to >= 1, the window into h x w, n to the pitch, and any non-zero flip is 1.                      */
+typedef struct ptx_resize_geom {
+    int32_t box_top, box_left, box_h, box_w; /* the box in the input frame                        */
+    int32_t h, w;                            /* extent the box is resized to                      */
+    int32_t top, left;                       /* first row / column of the window in h x w         */
+    int32_t hflip, vflip;                    /* 0 / 1: mirror the window's columns / rows         */
+} ptx_resize_geom;
+int ptx_resize_build_tables(const ptx_resize_desc* desc, const ptx_resize_geom* geoms,
+                            int32_t* row_lo, int32_t* row_n, int32_t* row_k, /* [N][Ho], [N][Ho], [N][Ho][taps_h] */
+                            int32_t* col_lo, int32_t* col_n, int32_t* col_k, /* [N][Wo], [N][Wo], [N][Wo][taps_w] */
+                            ptx_stream_t stream);
 /* ptx_resize_views_u8 on a YUV video: the source's strides address the frames, desc->stride_n / desc->stride_t are
  * IGNORED.  _supported returns 0 / 1 / 2 as ptx_resize_views_u8_supported does. */
 int ptx_resize_views_yuv420_supported(const ptx_views_desc* desc, const ptx_yuv420_src* src);

@@ -104,6 +104,11 @@ class ResizeWindow(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("top", "left", "hflip", "vflip")]
 
 
+class ResizeGeom(C.Structure):
+    """ptx_resize_geom: one clip's resize geometry (ptx_resize_build_tables): box in the frame, resized extent, window, flips."""
+    _fields_ = [(n, C.c_int32) for n in ("box_top", "box_left", "box_h", "box_w", "h", "w", "top", "left", "hflip", "vflip")]
+
+
 PTX_RESIZE_OUT_U8, PTX_RESIZE_OUT_F32, PTX_RESIZE_OUT_BF16 = 0, 1, 2
 PTX_RESIZE_MAX_TAPS = 64
 PTX_VIEWS_MAX_CROPS = 4
@@ -233,6 +238,12 @@ SIGNATURES = {
     "ptx_resize_frames_yuv420_windows_supported": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src), _I, _I]),
     "ptx_resize_frames_yuv420_windows": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _I, _I,
                                                    _P, _P, C.POINTER(NormDesc), _P]),
+    "ptx_resize_frames_u8_tables_supported": (C.c_int, [C.POINTER(ResizeDesc)]),
+    "ptx_resize_frames_u8_tables": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+    "ptx_resize_frames_yuv420_tables_supported": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src)]),
+    "ptx_resize_frames_yuv420_tables": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _P,
+                                                  C.POINTER(NormDesc), _P]),
+    "ptx_resize_build_tables": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "ptx_resize_views_yuv420_supported": (C.c_int, [C.POINTER(ViewsDesc), C.POINTER(Yuv420Src)]),
     "ptx_resize_views_yuv420": (C.c_int, [C.POINTER(ViewsDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _P, _P,
                                           C.POINTER(NormDesc), _P]),

@@ -288,12 +288,16 @@ __global__ void __launch_bounds__(256) fold_kw_frames_u8_kernel(const unsigned c
 // fixed-window kernel copies entries y0 + i and x, and everything derived from the copied entries (the referenced column
 // span, the head / tail split of the row staging, the YUV group origin, the chunks of a band, whose rows now may descend)
 // follows per clip.  top / left are clamped so the window lies inside the tables.
+// TAB (ptx_resize_frames_*_tables): every clip has tables of its own, [N][Ho] / [N][Ho][taps_h] / [N][Wo] / [N][Wo][taps_w]
+// with d.taps_* the common pitch.  A workgroup of clip n moves the six table pointers to the clip's tables once and is
+// the fixed-window kernel from there on: tap loops run to the entry's n, never to the pitch, and the entries are clamped
+// as everywhere else.
 struct ResizeWindows {
     const ptx_resize_window* wins;   // device, [N]
     int h, w;                        // entries of the row / column tables
 };
 
-template <int C, bool YUV = false, bool WIN = false>
+template <int C, bool YUV = false, bool WIN = false, bool TAB = false>
 __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d, const unsigned char* __restrict__ f,
                                                                const int* __restrict__ row_lo, const int* __restrict__ row_n,
                                                                const int* __restrict__ row_k, const int* __restrict__ col_lo,
@@ -318,6 +322,15 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
     const int half = 1 << (kResizeBits - 1);
     const unsigned char* fin = YUV ? nullptr : f + (size_t)frame * d.H * d.W * C;
     const YuvFrame yf = YUV ? yuv_frame(ys, frame / d.T, frame % d.T) : YuvFrame{};
+    if constexpr (TAB) {
+        const size_t clip = (size_t)(frame / d.T);
+        row_lo += clip * d.Ho;
+        row_n += clip * d.Ho;
+        row_k += clip * d.Ho * d.taps_h;
+        col_lo += clip * d.Wo;
+        col_n += clip * d.Wo;
+        col_k += clip * d.Wo * d.taps_w;
+    }
     int top = 0, left = 0, hflip = 0, vflip = 0;
     if constexpr (WIN) {
         const ptx_resize_window wn = win.wins[frame / d.T];
@@ -533,6 +546,73 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
         }
         __syncthreads();                                             // the next chunk overwrites the intermediate image
         r = r1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The per-clip tables of ptx_resize_frames_*_tables, built on the device from one ptx_resize_geom per clip
+// (ptx_resize_build_tables): one thread per (clip, axis, output index) restates PIL's precompute_coeffs +
+// normalize_coeffs_8bpc for its entry in IEEE fp64, in the operation order of transforms.resize_axis_table -- the
+// host builder the fixed-window launch uses -- so the entry has that builder's bits.  Contraction is OFF: hipcc
+// otherwise fuses (i + 0.5) * scale - fs, 1 - |..| * ss and w * 2^22 + 0.5 into FMAs, which moves the last bit of
+// `center` and of the weights and with it a coefficient here and there.  The sum of the weights is taken sequentially.
+// Garbage rows are safe: the box is clamped into the frame, the resized extent to >= 1, the window into the resized
+// frame, the table index into [0, extent), n to the pitch; the resize kernel clamps the entries once more.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) resize_build_tables_kernel(ptx_resize_desc d, const ptx_resize_geom* __restrict__ geoms,
+                                                                  int* __restrict__ row_lo, int* __restrict__ row_n,
+                                                                  int* __restrict__ row_k, int* __restrict__ col_lo,
+                                                                  int* __restrict__ col_n, int* __restrict__ col_k) {
+#pragma clang fp contract(off)
+    const int per_clip = d.Ho + d.Wo;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)d.N * per_clip) return;
+    const int clip = (int)(idx / per_clip), e = (int)(idx - (long long)clip * per_clip);
+    const bool rows = e < d.Ho;
+    const int o = rows ? e : e - d.Ho;                               // output index on this axis
+    const int S = rows ? d.Ho : d.Wo, extent = rows ? d.H : d.W, taps = rows ? d.taps_h : d.taps_w;
+    const ptx_resize_geom g = geoms[clip];
+    const int origin = min(max(rows ? g.box_top : g.box_left, 0), extent - 1);
+    const int n_in = min(max(rows ? g.box_h : g.box_w, 1), extent - origin);
+    const int n_out = max(rows ? g.h : g.w, 1);
+    const int start = min(max(rows ? g.top : g.left, 0), max(n_out - S, 0));
+    const int flip = (rows ? g.vflip : g.hflip) != 0;
+    const int i = min(start + (flip ? S - 1 - o : o), n_out - 1);   // index in the resized box
+    const size_t at = (size_t)clip * S + o;
+    int* lo_t = rows ? row_lo : col_lo;
+    int* n_t = rows ? row_n : col_n;
+    int* k = (rows ? row_k : col_k) + at * taps;
+    if (n_in == n_out) {                                             // not resampled: one tap of 2^22
+        lo_t[at] = origin + i;
+        n_t[at] = 1;
+        k[0] = 1 << kResizeBits;
+        for (int j = 1; j < taps; ++j) k[j] = 0;
+        return;
+    }
+    const double scale = (double)n_in / (double)n_out;
+    const double fs = scale > 1.0 ? scale : 1.0;
+    const double ss = 1.0 / fs;
+    const double center = ((double)i + 0.5) * scale;
+    // C's (int) truncates; both values are >= -0.5 and, clamped in double first, inside int whatever the row held
+    const int lo = min(max((int)fmin(center - fs + 0.5, 2147483647.0), 0), n_in - 1);   // below n_in for every real row
+    const int hi = min((int)fmin(center + fs + 0.5, 2147483647.0), n_in);
+    const int n = min(max(hi - lo, 0), taps);
+    auto weight = [&](int j) {
+        const double w = 1.0 - fabs(((double)j + (double)lo - center + 0.5) * ss);
+        return w > 0.0 ? w : 0.0;
+    };
+    double ww = 0.0;
+    for (int j = 0; j < n; ++j) ww = ww + weight(j);
+    lo_t[at] = origin + lo;
+    n_t[at] = n;
+    for (int j = 0; j < taps; ++j) {
+        int c = 0;
+        if (j < n) {
+            double w = weight(j);
+            if (ww != 0.0) w = w / ww;
+            c = (int)(w * 4194304.0 + 0.5);
+        }
+        k[j] = c;
     }
 }
 
@@ -913,13 +993,13 @@ static int resize_windows_check(const ptx_resize_desc* d, int h, int w, const ch
     return PTX_OK;
 }
 
-// Both sources: `frames` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.  Both kernels:
-// the fixed window (win == nullptr: the tables hold the window's entries) or one window per clip (win->wins, tables of
-// win->h x win->w entries).
+// Both sources: `frames` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.  All three
+// table modes: the fixed window (win == nullptr: the tables hold the window's entries), one window per clip (win->wins,
+// tables of win->h x win->w entries) or tables per clip (per_clip: every table has a leading [N]).
 static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames, const ptx_yuv420_src* src, const int32_t* row_lo,
                              const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo, const int32_t* col_n,
                              const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream, const char* who,
-                             const ResizeWindows* win = nullptr) {
+                             const ResizeWindows* win = nullptr, bool per_clip = false) {
     ResizePlan p;
     int s = resize_plan(desc, y, &p, who);
     if (s) return s;
@@ -939,29 +1019,36 @@ static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames,
     hipStream_t st = (hipStream_t)stream;
     const ResizeWindows rw = win ? *win : ResizeWindows{};
     const unsigned char* none = nullptr;
-#define PTX_RESIZE_LAUNCH(CH, YUV, WIN)                                                                                        \
-    hipLaunchKernelGGL((resize_frames_u8_kernel<CH, YUV, WIN>), grid, dim3(256), p.lds_bytes, st, *desc, YUV ? none : frames, \
-                       row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, YUV ? *src : ptx_yuv420_src{}, rw)
-#define PTX_RESIZE_LAUNCH_C(WIN)                          \
-    switch (desc->C) {                                    \
-        case 1: PTX_RESIZE_LAUNCH(1, false, WIN); break;  \
-        case 2: PTX_RESIZE_LAUNCH(2, false, WIN); break;  \
-        case 3: PTX_RESIZE_LAUNCH(3, false, WIN); break;  \
-        default: PTX_RESIZE_LAUNCH(4, false, WIN); break; \
+#define PTX_RESIZE_LAUNCH(CH, YUV, WIN, TAB)                                                                          \
+    hipLaunchKernelGGL((resize_frames_u8_kernel<CH, YUV, WIN, TAB>), grid, dim3(256), p.lds_bytes, st, *desc,           \
+                       YUV ? none : frames, row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, YUV ? *src : ptx_yuv420_src{}, \
+                       rw)
+#define PTX_RESIZE_LAUNCH_C(WIN, TAB)                          \
+    switch (desc->C) {                                         \
+        case 1: PTX_RESIZE_LAUNCH(1, false, WIN, TAB); break;  \
+        case 2: PTX_RESIZE_LAUNCH(2, false, WIN, TAB); break;  \
+        case 3: PTX_RESIZE_LAUNCH(3, false, WIN, TAB); break;  \
+        default: PTX_RESIZE_LAUNCH(4, false, WIN, TAB); break; \
     }
     if (src) {
-        if (win) {
-            PTX_RESIZE_LAUNCH(3, true, true);
+        if (per_clip) {
+            PTX_RESIZE_LAUNCH(3, true, false, true);
+        } else if (win) {
+            PTX_RESIZE_LAUNCH(3, true, true, false);
         } else {
-            PTX_RESIZE_LAUNCH(3, true, false);
+            PTX_RESIZE_LAUNCH(3, true, false, false);
         }
         return hip_check(hipGetLastError(), who);
     }
-    if (win) {
-        PTX_RESIZE_LAUNCH_C(true)
+    if (per_clip) {
+        PTX_RESIZE_LAUNCH_C(false, true)
         return hip_check(hipGetLastError(), who);
     }
-    PTX_RESIZE_LAUNCH_C(false)
+    if (win) {
+        PTX_RESIZE_LAUNCH_C(true, false)
+        return hip_check(hipGetLastError(), who);
+    }
+    PTX_RESIZE_LAUNCH_C(false, false)
 #undef PTX_RESIZE_LAUNCH_C
 #undef PTX_RESIZE_LAUNCH
     return hip_check(hipGetLastError(), "ptx_resize_frames_u8 launch");
@@ -1020,6 +1107,50 @@ extern "C" int ptx_resize_frames_yuv420_windows(const ptx_resize_desc* desc, con
     if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
     const ResizeWindows win = {windows, h, w};
     return resize_frames_run(desc, nullptr, src, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, &win);
+}
+
+// Per-clip tables (every table has a leading [N]; desc->taps_* is the common pitch) and their builder on the device.
+extern "C" int ptx_resize_frames_u8_tables_supported(const ptx_resize_desc* desc) {
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, "ptx_resize_frames_u8_tables_supported") == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_u8_tables(const ptx_resize_desc* desc, const uint8_t* frames, const int32_t* row_lo,
+                                           const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                                           const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm,
+                                           ptx_stream_t stream) {
+    return resize_frames_run(desc, frames, nullptr, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream,
+                             "ptx_resize_frames_u8_tables", nullptr, true);
+}
+
+extern "C" int ptx_resize_frames_yuv420_tables_supported(const ptx_resize_desc* desc, const ptx_yuv420_src* src) {
+    const char* who = "ptx_resize_frames_yuv420_tables_supported";
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, who) == PTX_OK && yuv_check(src, desc->C, desc->H, desc->W, who) == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_yuv420_tables(const ptx_resize_desc* desc, const ptx_yuv420_src* src, const int32_t* row_lo,
+                                               const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                                               const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm,
+                                               ptx_stream_t stream) {
+    const char* who = "ptx_resize_frames_yuv420_tables";
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    return resize_frames_run(desc, nullptr, src, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, nullptr, true);
+}
+
+extern "C" int ptx_resize_build_tables(const ptx_resize_desc* desc, const ptx_resize_geom* geoms, int32_t* row_lo,
+                                       int32_t* row_n, int32_t* row_k, int32_t* col_lo, int32_t* col_n, int32_t* col_k,
+                                       ptx_stream_t stream) {
+    const char* who = "ptx_resize_build_tables";
+    ResizePlan p;
+    int s = resize_plan(desc, nullptr, &p, who);                     // the extents and pitches the launch will be given
+    if (s) return s;
+    if (!geoms || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k) return fail(PTX_ERR_INVALID, "%s: null pointer", who);
+    const int64_t entries = (int64_t)desc->N * ((int64_t)desc->Ho + desc->Wo);
+    if (entries > INT32_MAX) return fail(PTX_ERR_UNSUPPORTED, "%s: N * (Ho + Wo) exceeds 32-bit indexing", who);
+    hipLaunchKernelGGL(resize_build_tables_kernel, dim3((unsigned)cdiv64(entries, 256)), dim3(256), 0, (hipStream_t)stream,
+                       *desc, geoms, row_lo, row_n, row_k, col_lo, col_n, col_k);
+    return hip_check(hipGetLastError(), who);
 }
 
 // y[r][0..W) = x[r][0..W), y[r][W..ld) = 0: gives rows whose length is not a multiple of 4 floats a 16-byte pitch

@@ -16,6 +16,9 @@ uint8 frames:
   result equals PIL's to the bit.  Crop and flip are folded into the tables.  With `random_crop` / `random_hflip` /
   `random_vflip` (TransformImage's training switches, utils.py:36-70) every clip of a batch gets a window and flips of
   its own, still in one launch: the tables then cover the whole resized frame and the kernel indexes them per clip.
+  With `random_short_side` (per-clip scale jitter) or `random_resized_crop` (torchvision's RandomResizedCrop) every clip
+  has a resize GEOMETRY of its own: a small launch builds the clips' tables on the device from 10 integers per clip (the
+  same float64 operations in the same order as the host builder: the same bits) and one resize launch applies them.
 
 * `SampleViews` is test-time multi-view sampling of a whole decoded video: `clips` temporal clips x `crops` spatial
   crops, each resized + cropped as `TransformFrames` does (same tables, same bits), in one HIP launch per range of
@@ -242,15 +245,21 @@ class YUV420:
 # ---------------------------------------------------------------------------------------------
 # resize + crop: size rules (torchvision's documented Resize / CenterCrop semantics) and PIL's coefficient tables
 # ---------------------------------------------------------------------------------------------
+def resized_size_for(H, W, R):
+    """(h, w) of an H x W frame after Resize(R): the short side becomes R, the long side follows the aspect ratio
+    (truncated, as torchvision does)."""
+    H, W, R = int(H), int(W), int(R)
+    if (W <= H and W == R) or (H <= W and H == R):
+        return H, W                                       # short side already R: not resampled
+    if W < H:
+        return int(R * H / W), R
+    return R, int(R * W / H)
+
+
 def resized_size(H, W, input_size, scale=0.875, preserve_aspect_ratio=True):
     """(h, w) of the frame after TransformImage's Resize (utils.py:54-59)."""
     if preserve_aspect_ratio:
-        R = int(math.floor(max(input_size) / scale))
-        if (W <= H and W == R) or (H <= W and H == R):
-            return H, W                                   # short side already R: not resampled
-        if W < H:
-            return int(R * H / W), R
-        return R, int(R * W / H)
+        return resized_size_for(H, W, int(math.floor(max(input_size) / scale)))
     return int(input_size[1] / scale), int(input_size[2] / scale)
 
 
@@ -346,6 +355,76 @@ def build_frame_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True
     return {"rows": rows, "cols": cols, "S": S, "resized": (h, w)}
 
 
+# ---------------------------------------------------------------------------------------------
+# per-clip resize geometry: (box_top, box_left, box_h, box_w, h, w, top, left, hflip, vflip)
+# ---------------------------------------------------------------------------------------------
+GEOMETRY_FIELDS = ("box_top", "box_left", "box_h", "box_w", "h", "w", "top", "left", "hflip", "vflip")
+
+
+def geometry_tables(row, S):
+    """Row and column tables of ONE clip's geometry, in build_tables' form.  The row means, in PIL terms: crop the box
+    [box_top, +box_h) x [box_left, +box_w) out of the frame, resize it to h x w (Image.BILINEAR; an axis whose extent
+    does not change is not resampled), crop the S x S window at (top, left), mirror if hflip, flip if vflip.  Resizing
+    a crop references only the crop's pixels, at positions relative to its origin, so its table is
+    `resize_axis_table(box_len, out_len)` with `lo` shifted by the origin; window and flips select and order the
+    entries as in build_tables.  The numpy statement of the per-clip tables the device builds (the tests' oracle; the
+    product path does not call it)."""
+    bt, bl, bh, bw, h, w, top, left, hf, vf = (int(v) for v in row)
+    S = int(S)
+
+    def axis(origin, n_in, n_out, start, flip):
+        if start < 0 or start + S > n_out:
+            raise PtxError("TransformFrames: geometry: the %d-entry window at %d does not fit the resized extent %d" % (S, start, n_out))
+        lo, n, k = resize_axis_table(n_in, n_out)
+        return _select((lo + np.int32(origin), n, k), start, S, reverse=bool(flip))
+
+    return {"rows": axis(bt, bh, h, top, vf), "cols": axis(bl, bw, w, left, hf), "S": S, "resized": (h, w),
+            "window": (top, left)}
+
+
+def _axis_taps(n_in, n_out, start, S):
+    """Largest tap count of the entries [start, start + S) of resize_axis_table(n_in, n_out), per clip (int64 arrays
+    [N]): lo / hi of the table alone (the same float64 operations), no weight is computed."""
+    scale = n_in / n_out                                             # int64 / int64: the float64 quotient, as Python's
+    fs = np.maximum(scale, 1.0)[:, None]
+    center = ((start[:, None] + np.arange(S, dtype=np.int64)[None, :]).astype(np.float64) + 0.5) * scale[:, None]
+    lo = np.maximum((center - fs + 0.5).astype(np.int64), 0)
+    hi = np.minimum((center + fs + 0.5).astype(np.int64), n_in[:, None])
+    return np.where(n_in == n_out, 1, (hi - lo).max(axis=1))
+
+
+def random_resized_crop_box(H, W, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), generator=None):
+    """torchvision's RandomResizedCrop.get_params on an H x W frame: (i, j, h, w), the box's top, left, height, width.
+    Up to 10 attempts, each drawing `area = H * W * uniform_(scale[0], scale[1])` and then
+    `r = exp(uniform_(log(ratio[0]), log(ratio[1])))` (the logs taken in float32, as torch.log(torch.tensor(ratio)) gives
+    them), with w = int(round(sqrt(area * r))), h = int(round(sqrt(area / r))); the first attempt with 0 < w <= W and
+    0 < h <= H is accepted and then draws i = randint(0, H - h + 1), j = randint(0, W - w + 1).  After 10 rejections the
+    central fallback: the whole frame, cut to ratio[0] (full width) when W / H is below it or to ratio[1] (full height)
+    when above, centred; it draws nothing more."""
+    g = generator
+    area = H * W
+    log_ratio = torch.log(torch.tensor([float(ratio[0]), float(ratio[1])]))
+    for _ in range(10):
+        target = area * torch.empty(1).uniform_(float(scale[0]), float(scale[1]), generator=g).item()
+        r = torch.exp(torch.empty(1).uniform_(float(log_ratio[0]), float(log_ratio[1]), generator=g)).item()
+        w = int(round(math.sqrt(target * r)))
+        h = int(round(math.sqrt(target / r)))
+        if 0 < w <= W and 0 < h <= H:
+            i = int(torch.randint(0, H - h + 1, (1,), generator=g))
+            j = int(torch.randint(0, W - w + 1, (1,), generator=g))
+            return i, j, h, w
+    in_ratio = float(W) / float(H)
+    if in_ratio < min(ratio):
+        w = W
+        h = max(int(round(w / min(ratio))), 1)
+    elif in_ratio > max(ratio):
+        h = H
+        w = max(int(round(h * max(ratio))), 1)
+    else:
+        w, h = W, H
+    return (H - h) // 2, (W - w) // 2, h, w
+
+
 def apply_tables_numpy(frame, tables):
     """The kernel's arithmetic in numpy (uint8 [H,W,C] -> uint8 [S,S,C]): horizontal pass, uint8 intermediate,
     vertical pass.  The host-side model the tests compare with PIL; not a fallback (TransformFrames never calls it)."""
@@ -378,13 +457,23 @@ class TransformFrames:
     random_crop / random_hflip / random_vflip (TransformImage's switches of the same names, utils.py:36-70): every CLIP of a
     call gets a window / flips of its own, drawn by `draw` from `generator` (None: torch's default CPU generator, so
     `torch.manual_seed` governs) and shared by all frames of the clip; the whole batch is still one launch and the draw is
-    kept as `last_params`.  `tf(frames, params=p)` applies given parameters instead (on any TransformFrames)."""
+    kept as `last_params`.  `tf(frames, params=p)` applies given parameters instead (on any TransformFrames).
+
+    random_short_side=(a, b) / random_resized_crop=True | dict(scale=(0.08, 1.0), ratio=(3/4, 4/3)): every clip gets a
+    resize GEOMETRY of its own (see `draw_geometry`), still in one resize launch: a small launch builds the clips'
+    coefficient tables on the device from the [N, 10] geometry rows, which are kept as `last_geometry`.
+    random_short_side is the video recipes' scale jitter (the short side resized to R = randint(a, b + 1), then the
+    centre window or, with random_crop, a drawn one); it needs a >= max(input_size), preserve_aspect_ratio=True and
+    crop="center", and does not use `scale`.  random_resized_crop is torchvision's RandomResizedCrop
+    (`random_resized_crop_box` states the algorithm; torchvision is not needed): the drawn box is resized to S x S; it
+    excludes random_crop, random_short_side and an explicit crop and ignores scale / preserve_aspect_ratio.  Flips
+    apply as above.  `tf(frames, geometry=g)` applies given rows instead (on any TransformFrames)."""
 
     CACHE_SIZE = 8
 
     def __init__(self, opts, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, out="tensor",
                  dtype=torch.float32, *, random_crop=False, random_hflip=False, random_vflip=False, vflip=False,
-                 generator=None):
+                 generator=None, random_short_side=None, random_resized_crop=False):
         if out not in ("tensor", "frames"):
             raise PtxError("TransformFrames: out must be 'tensor' or 'frames', got %r" % (out,))
         if dtype not in (torch.float32, torch.bfloat16):
@@ -416,6 +505,52 @@ class TransformFrames:
         elif crop != "center":
             raise PtxError("TransformFrames: crop must be 'center' or (top, left), got %r" % (crop,))
         self._cache = collections.OrderedDict()                      # (H, W, device) -> device tables
+        self.random_short_side, self.random_resized_crop, self.last_geometry = None, None, None
+        if random_short_side is not None:
+            try:
+                a, b = random_short_side
+                ok = all(isinstance(v, int) and not isinstance(v, bool) for v in (a, b)) and a <= b
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise PtxError("TransformFrames: random_short_side must be a pair of integers (a, b) with a <= b, got %r" % (
+                    random_short_side,))
+            if a < self.size:
+                raise PtxError("TransformFrames: random_short_side=(%d, %d): the short side must hold the %dx%d window (a >= %d; "
+                               "padding crops are not offered)" % (a, b, self.size, self.size, self.size))
+            if not self.preserve_aspect_ratio:
+                raise PtxError("TransformFrames: random_short_side resizes the short side; it needs preserve_aspect_ratio=True")
+            if not isinstance(crop, str):
+                raise PtxError("TransformFrames: random_short_side draws the resized size; it cannot be combined with crop=%r "
+                               "(use random_crop=True or the centre window)" % (crop,))
+            self.random_short_side = (a, b)
+        if random_resized_crop is not False and random_resized_crop is not None:
+            rrc = {"scale": (0.08, 1.0), "ratio": (3.0 / 4.0, 4.0 / 3.0)}
+            if isinstance(random_resized_crop, dict):
+                extra = set(random_resized_crop) - set(rrc)
+                if extra:
+                    raise PtxError("TransformFrames: random_resized_crop takes scale and ratio, got %s" % sorted(extra))
+                rrc.update(random_resized_crop)
+            elif random_resized_crop is not True:
+                raise PtxError("TransformFrames: random_resized_crop must be True or dict(scale=.., ratio=..), got %r" % (
+                    random_resized_crop,))
+            for key in ("scale", "ratio"):
+                try:
+                    lo_, hi_ = (float(v) for v in rrc[key])
+                    ok = 0.0 < lo_ <= hi_ and math.isfinite(hi_)
+                except (TypeError, ValueError):
+                    ok = False
+                if not ok:
+                    raise PtxError("TransformFrames: random_resized_crop: %s must be a pair 0 < lo <= hi, got %r" % (key, rrc[key]))
+                rrc[key] = (lo_, hi_)
+            if self.random_crop:
+                raise PtxError("TransformFrames: random_resized_crop draws the box; it cannot be combined with random_crop=True")
+            if self.random_short_side is not None:
+                raise PtxError("TransformFrames: random_resized_crop cannot be combined with random_short_side")
+            if not isinstance(crop, str):
+                raise PtxError("TransformFrames: random_resized_crop draws the box; it cannot be combined with crop=%r" % (crop,))
+            self.random_resized_crop = rrc
+        self.per_clip_geometry = self.random_short_side is not None or self.random_resized_crop is not None
 
     def tables(self, H, W):
         """Host tables for H x W frames (numpy; see build_tables)."""
@@ -475,6 +610,85 @@ class TransformFrames:
                 raise PtxError("TransformFrames: params[%d]: a flip must be 0 or 1, got hflip=%d vflip=%d" % (n, hf, vf))
         return torch.from_numpy(p.astype(np.int32))
 
+    def draw_geometry(self, N, H, W):
+        """Geometries of N clips of H x W frames: a CPU int32 tensor [N, 10] of (box_top, box_left, box_h, box_w, h, w, top,
+        left, hflip, vflip) -- see `geometry_tables` for the meaning.  Per clip, in order, from `generator`:
+          1. random_short_side: R = randint(a, b + 1), (h, w) = resized_size_for(H, W, R), the box is the frame;  or
+             random_resized_crop: the `random_resized_crop_box` sequence, the box is resized to S x S;
+             neither: the box is the frame and (h, w) = resized_size(..) as for every clip of a plain call;
+          2. random_crop: top = randint(0, h - S + 1), then left = randint(0, w - S + 1) (else the centre window of h x w,
+             or the constructor's crop; (0, 0) for random_resized_crop);
+          3. random_hflip: rand(1) < 0.5;   4. random_vflip: rand(1) < 0.5.
+        A switch that is off consumes nothing."""
+        S, g = self.size, self.generator
+        N, H, W = int(N), int(H), int(W)
+        hf, vf = int(self.hflip), int(self.vflip)
+        out = torch.empty((N, 10), dtype=torch.int32)
+        for n in range(N):
+            box = (0, 0, H, W)
+            if self.random_short_side is not None:
+                a, b = self.random_short_side
+                h, w = resized_size_for(H, W, int(torch.randint(a, b + 1, (1,), generator=g)))
+            elif self.random_resized_crop is not None:
+                box = random_resized_crop_box(H, W, self.random_resized_crop["scale"], self.random_resized_crop["ratio"], g)
+                h, w = S, S
+            else:
+                h, w = resized_size(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
+            if self.random_crop:
+                crop_window(h, w, S, (0, 0))                        # the resized frame must hold a window
+                top = int(torch.randint(0, h - S + 1, (1,), generator=g))
+                left = int(torch.randint(0, w - S + 1, (1,), generator=g))
+            else:
+                top, left = crop_window(h, w, S, self.crop)
+            if self.random_hflip:
+                hf = int(torch.rand(1, generator=g) < 0.5)
+            if self.random_vflip:
+                vf = int(torch.rand(1, generator=g) < 0.5)
+            out[n] = torch.tensor(box + (h, w, top, left, hf, vf), dtype=torch.int32)
+        return out
+
+    def _checked_geometry(self, geometry, N, H, W):
+        if isinstance(geometry, torch.Tensor):
+            if geometry.is_cuda:
+                raise PtxError("TransformFrames: geometry must be an integer array or a CPU tensor [N, 10], got a CUDA tensor")
+            geometry = geometry.numpy()
+        p = np.asarray(geometry)
+        if p.dtype.kind not in "iu":
+            raise PtxError("TransformFrames: geometry must hold integers, got dtype %s" % (p.dtype,))
+        if p.ndim != 2 or p.shape[1] != 10:
+            raise PtxError("TransformFrames: geometry must be [N, 10] (%s), got shape %s" % (", ".join(GEOMETRY_FIELDS), p.shape))
+        if p.shape[0] != N:
+            raise PtxError("TransformFrames: geometry holds %d clips, the frames hold N = %d" % (p.shape[0], N))
+        p = p.astype(np.int64)
+        S = self.size
+        for n, (bt, bl, bh, bw, h, w, top, left, hf, vf) in enumerate(p.tolist()):
+            if bh < 1 or bw < 1 or bt < 0 or bl < 0 or bt + bh > H or bl + bw > W:
+                raise PtxError("TransformFrames: geometry[%d]: the %dx%d box at (%d, %d) is empty or does not lie inside the %dx%d "
+                               "frame" % (n, bh, bw, bt, bl, H, W))
+            if h < S or w < S:
+                raise PtxError("TransformFrames: geometry[%d]: a %dx%d crop does not fit the resized %dx%d box (padding crops are "
+                               "not offered)" % (n, S, S, h, w))
+            if top < 0 or left < 0 or top + S > h or left + S > w:
+                raise PtxError("TransformFrames: geometry[%d]: the %dx%d crop at (%d, %d) does not fit the resized %dx%d box "
+                               "(padding crops are not offered)" % (n, S, S, top, left, h, w))
+            if hf not in (0, 1) or vf not in (0, 1):
+                raise PtxError("TransformFrames: geometry[%d]: a flip must be 0 or 1, got hflip=%d vflip=%d" % (n, hf, vf))
+        if N == 0:
+            raise PtxError("TransformFrames: empty batch")
+        taps = (_axis_taps(p[:, 2], p[:, 4], p[:, 6], S), _axis_taps(p[:, 3], p[:, 5], p[:, 7], S))
+        for name, t, src, dst in (("rows", taps[0], 2, 4), ("columns", taps[1], 3, 5)):
+            n = int(np.argmax(t))
+            if t[n] > _lib.PTX_RESIZE_MAX_TAPS:
+                raise PtxError("TransformFrames: geometry[%d]: down-scaling %d %s to %d needs %d taps, the kernel's cap is "
+                               "PTX_RESIZE_MAX_TAPS = %d" % (n, p[n, src], name, p[n, dst], t[n], _lib.PTX_RESIZE_MAX_TAPS))
+        return torch.from_numpy(p.astype(np.int32)), int(taps[0].max()), int(taps[1].max())
+
+    def check_geometry(self, geometry, N, H, W):
+        """`geometry` ([N, 10] integers: an array or a CPU tensor, see `draw_geometry`) as a CPU int32 tensor, or PtxError: N
+        does not match, a box is empty or leaves the H x W frame, h or w is below S, a window does not fit h x w, a flip is
+        not 0 / 1, an axis needs more than PTX_RESIZE_MAX_TAPS taps.  No device is touched."""
+        return self._checked_geometry(geometry, N, H, W)[0]
+
     def _device_tables(self, H, W, device, whole=False):
         key = (H, W, str(device)) + (("frame",) if whole else ())
         hit = self._cache.get(key)
@@ -491,22 +705,32 @@ class TransformFrames:
             self._cache.popitem(last=False)
         return hit
 
-    def __call__(self, frames, params=None):
+    def __call__(self, frames, params=None, geometry=None):
         """uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3], any H, W  ->
         out="tensor": [N,3,T,S,S] | [3,T,S,S] | [3,S,S] (fp32 or bf16);  out="frames": uint8, same rank, H, W -> S, S.
         A `YUV420` source is taken in place of the frames (converted while the kernel stages its rows: the same bits as
         the call on the converted frames); the result's rank follows `src.lead` as it follows the tensor's rank.
         A random transform draws one (top, left, hflip, vflip) per clip (N draws for [N,T,..], one for the lower ranks;
         per-image augmentation of an image batch is [N,1,H,W,3]) and keeps the draw as `last_params`; params ([N, 4]
-        integers, see `check_params`) applies given parameters instead.  Both are one launch."""
+        integers, see `check_params`) applies given parameters instead.  Both are one launch.
+        With random_short_side / random_resized_crop one geometry row is drawn per clip in the same way and kept as
+        `last_geometry`; geometry ([N, 10] integers, see `check_geometry`) applies given rows instead, on any transform.
+        Both are a table-builder launch plus one resize launch."""
+        if params is not None and geometry is not None:
+            raise PtxError("TransformFrames: params= and geometry= cannot be combined (a geometry row holds the window and flips)")
+        if params is not None and self.per_clip_geometry:
+            raise PtxError("TransformFrames: params= are windows in ONE resized frame; with random_short_side / "
+                           "random_resized_crop every clip has its own: pass geometry=")
         if isinstance(frames, YUV420):
-            return self._call_yuv(frames, params)
+            return self._call_yuv(frames, params, geometry)
         if not isinstance(frames, torch.Tensor):
             raise PtxError("TransformFrames: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
         if frames.dim() not in (3, 4, 5):
             raise PtxError("TransformFrames: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (tuple(frames.shape),))
         if frames.shape[-1] != 3:
             raise PtxError("TransformFrames: frames must have 3 interleaved channels, got %d" % frames.shape[-1])
+        if geometry is not None:                                     # validated before a device is touched
+            geometry = self.check_geometry(geometry, frames.shape[0] if frames.dim() == 5 else 1, frames.shape[-3], frames.shape[-2])
         if not frames.is_cuda or frames.dtype != torch.uint8:
             raise PtxError("TransformFrames: frames must be a uint8 CUDA tensor (no CPU fallback)")
         lead = frames.dim()
@@ -515,8 +739,11 @@ class TransformFrames:
         if N * T == 0:
             raise PtxError("TransformFrames: empty batch")
         S = self.size
-        if params is not None or self.random:
-            y = self._call_windows(f5, None, N, T, H, W, frames.device, params)
+        if params is not None or geometry is not None or self.random or self.per_clip_geometry:
+            if geometry is not None or self.per_clip_geometry:
+                y = self._call_geometry(f5, None, N, T, H, W, frames.device, geometry)
+            else:
+                y = self._call_windows(f5, None, N, T, H, W, frames.device, params)
             if self.out == "frames":
                 return y.view(tuple(frames.shape[:-3]) + (S, S, Cc))
             if lead == 5:
@@ -570,11 +797,45 @@ class TransformFrames:
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
         return y
 
-    def _call_yuv(self, src, params=None):
+    def _call_geometry(self, f5, ysrc, N, T, H, W, device, geometry):
+        """The per-clip tables path on frames f5 [N,T,H,W,3] or, when ysrc is given, on a YUV source: the drawn or the given
+        geometry rows (one upload of N x 40 bytes), ptx_resize_build_tables into a scratch buffer, the tables launch.  The
+        host only derives the tap pitch of each axis (from lo / hi of the entries; no weights)."""
+        S = self.size
+        if geometry is None:
+            self.last_geometry = self.draw_geometry(N, H, W)
+        g, taps_h, taps_w = self._checked_geometry(self.last_geometry if geometry is None else geometry, N, H, W)
+        with torch.cuda.device(device):
+            geo = g.contiguous().to(device)
+            sizes = [N * S, N * S, N * S * taps_h, N * S, N * S, N * S * taps_w]
+            buf = torch.empty(sum(sizes), device=device, dtype=torch.int32)
+            offs = np.cumsum([0] + sizes[:-1])
+            tabs = [C.c_void_p(buf.data_ptr() + int(o) * 4) for o in offs]
+            if self.out == "frames":
+                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((N, T, S, S, 3), device=device, dtype=torch.uint8)
+            else:
+                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+                y = torch.empty((N, 3, T, S, S), device=device, dtype=self.dtype)
+            desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            check(_lib.lib().ptx_resize_build_tables(C.byref(desc), C.c_void_p(geo.data_ptr()), *tabs, stream),
+                  "ptx_resize_build_tables")
+            name = "ptx_resize_frames_u8_tables" if ysrc is None else "ptx_resize_frames_yuv420_tables"
+            source = C.c_void_p(f5.data_ptr()) if ysrc is None else C.byref(ysrc)
+            check(getattr(_lib.lib(), name)(C.byref(desc), source, *tabs, C.c_void_p(y.data_ptr()), C.byref(self.norm), stream),
+                  name)
+        return y
+
+    def _call_yuv(self, src, params=None, geometry=None):
+        if geometry is not None:                                     # validated before a device is touched
+            geometry = self.check_geometry(geometry, src.N, src.H, src.W)
         ysrc, keep = src.source("TransformFrames")
         N, T, H, W, S = src.N, src.T, src.H, src.W, self.size
-        if params is not None or self.random:
-            y = self._call_windows(None, ysrc, N, T, H, W, src.device, params)
+        if params is not None or geometry is not None or self.random or self.per_clip_geometry:
+            if geometry is not None or self.per_clip_geometry:
+                y = self._call_geometry(None, ysrc, N, T, H, W, src.device, geometry)
+            else:
+                y = self._call_windows(None, ysrc, N, T, H, W, src.device, params)
             del keep
             if self.out == "frames":
                 return y.view(src.lead_shape + (S, S, 3))
