@@ -250,6 +250,40 @@ int ptx_pack_stem_f32_weight(const ptx_conv3d_desc* desc, const float* w_folded,
 int ptx_conv_stem_f32_fwd(const ptx_conv3d_desc* desc, const float* x, int64_t stride_n, int64_t stride_c, int64_t stride_t,
                           const float* w_stem, const float* bias, float* y, ptx_stream_t stream);
 
+/* RGB STEM convolution on the bf16 matrix cores, input patch resident in LDS (csrc/conv_stem_bf16.hip) -- the stem of a
+ * bf16 plan under Engine.bf16_stem = "direct", instead of ptx_im2col_hw_bf16 + a (kT,1,1) conv on the generic bf16 tiles.
+ * A workgroup owns up to 256 consecutive outputs of one output frame x 64 channels, stages the input patch of a temporal
+ * tap once as pixel-interleaved bf16 (c0, c1, c2, 0) and serves all kH x kW taps from it; K = 8 pixels x 4 channels = 32
+ * per (kt, kh) tap = one v_mfma_f32_16x16x32_bf16 k-step (32 / 21 of the algorithmic MACs issued for kW = 7); temporal
+ * taps outside the clip are skipped.  bf16 operands, fp32 accumulate, bias (+ ReLU) in fp32, ONE round-to-nearest-even to
+ * bf16 per output (NaN kept).
+ * x, by `src`:
+ *   PTX_STEM_SRC_BF16_NCDHW  the contiguous bf16 clip [N][3][Ti][Hi][Wi], any 2-byte alignment;
+ *   PTX_STEM_SRC_U8_NTHWC    decoded uint8 frames [N][Ti][Hi][Wi][3], any byte alignment, with *norm: the operand of a pixel
+ *                            is bf16(normalise(u8)) with ptx_frames_u8_to_ncdhw's operations and BGR swap, rounded once --
+ *                            exactly PTX_RESIZE_OUT_BF16's value.  Positions outside the image are bf16 0 (zero in the
+ *                            NORMALISED domain), not pixel 0.  norm is ignored (may be NULL) for the bf16 clip.
+ * desc: the stem's own geometry -- Ci = 3, kW <= 8, stride_w = 2, any kT / kH / sT / sH, symmetric padding (extents must
+ *   satisfy out = (in + 2 pad - k) / stride + 1: SAME-padded stems are refused), flags within PTX_EPI_RELU (the bf16 operand
+ *   / output flags are accepted and implied); ldx and Kc are ignored; ldy counts bf16 elements, a multiple of 8, >= Co;
+ *   Co_pad = the packed filter's row count (multiple of 64).  One input frame (Hi*Wi*3 elements) and one output frame
+ *   (Ho*Wo*ldy*2 bytes) must stay below 2^31: offsets are 64-bit per frame, 32-bit inside one, and never wrap.
+ * y: bf16 [N][To][Ho][Wo][ldy], 16-byte aligned; channels [Co, ldy) are written as zero.
+ * w_stem: ptx_pack_stem_bf16_weight of w_packed = ptx_pack_conv_weight(f16 = PTX_PACK_BF16) of the (kh, kw)-folded filter
+ *   ([kT][Co_pad][Kc] bf16, k = (kh*kW + kw)*3 + c, Kc = kH*kW*3 rounded up to 32: the fold path's own filter, BatchNorm
+ *   folded, rounded once) -- a bit-exact re-lay into MFMA fragment order, ptx_stem_bf16_weight_elems bf16 values, 16-byte
+ *   aligned.  bias: [Co_pad] fp32 from the same pack.  The two stems multiply identical operands and differ only in
+ *   summation order.
+ * ptx_conv_stem_bf16_supported: 1 if the descriptor can run here for `src`, else 0 with the reason in ptx_last_error(). */
+#define PTX_STEM_SRC_BF16_NCDHW 0
+#define PTX_STEM_SRC_U8_NTHWC 1
+struct ptx_norm_desc;
+int ptx_conv_stem_bf16_supported(const ptx_conv3d_desc* desc, int32_t src);
+size_t ptx_stem_bf16_weight_elems(const ptx_conv3d_desc* desc);
+int ptx_pack_stem_bf16_weight(const ptx_conv3d_desc* desc, const void* w_packed, void* w_stem, ptx_stream_t stream);
+int ptx_conv_stem_bf16_fwd(const ptx_conv3d_desc* desc, const void* x, int32_t src, const struct ptx_norm_desc* norm,
+                           const void* w_stem, const float* bias, void* y, ptx_stream_t stream);
+
 /* 3x3x3 BODY convolution on the fp32 matrix cores, input patch resident in LDS -- `conv2` of every Bottleneck
  * (resnet3D.py:117,129-131: conv3x3x3 -> bn2 -> relu) and both convs of a BasicBlock (resnet3D.py:86-104), the layers that
  * hold 48 % of config 2's FLOPs.  A workgroup owns 256 (or 64) consecutive outputs of one frame x 64 channels; per

@@ -111,6 +111,7 @@ class ResizeGeom(C.Structure):
 
 PTX_RESIZE_OUT_U8, PTX_RESIZE_OUT_F32, PTX_RESIZE_OUT_BF16 = 0, 1, 2
 PTX_RESIZE_MAX_TAPS = 64
+PTX_STEM_SRC_BF16_NCDHW, PTX_STEM_SRC_U8_NTHWC = 0, 1       # ptx_conv_stem_bf16_fwd: where the stem reads its input
 PTX_VIEWS_MAX_CROPS = 4
 PTX_VIEWS_SHARE_AUTO, PTX_VIEWS_SHARE_ALWAYS, PTX_VIEWS_SHARE_NEVER = 0, 1, 2
 
@@ -208,6 +209,10 @@ SIGNATURES = {
     "ptx_stem_f32_weight_elems": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "ptx_pack_stem_f32_weight": (C.c_int, [C.POINTER(ConvDesc), _P, _I, _P, _P]),
     "ptx_conv_stem_f32_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _L, _L, _L, _P, _P, _P, _P]),
+    "ptx_conv_stem_bf16_supported": (C.c_int, [C.POINTER(ConvDesc), _I]),
+    "ptx_stem_bf16_weight_elems": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "ptx_pack_stem_bf16_weight": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P]),
+    "ptx_conv_stem_bf16_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _I, C.POINTER(NormDesc), _P, _P, _P, _P]),
     "ptx_packed_weight_elems": (_Z, [C.POINTER(PackDesc)]),
     "ptx_pack_conv_weight": (C.c_int, [C.POINTER(PackDesc), _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P]),
     "ptx_checksum_f32": (C.c_int, [_P, _I, _P, _P]),

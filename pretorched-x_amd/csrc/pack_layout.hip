@@ -1251,3 +1251,6 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 // The multi-view resize kernel is a file of its own compiled as part of this translation unit (build.py follows the
 // include, so its bytes are in this object's stamp and in ptx_version()'s source hash).
 #include "resize_views.hip"
+
+// So is the patch-resident bf16 stem (it normalises uint8 frames with resize_common.h's normalise_u8 while it stages them).
+#include "conv_stem_bf16.hip"

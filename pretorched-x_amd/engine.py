@@ -32,7 +32,7 @@ from ._lib import NormDesc, PtxError, check
 from .heads import check_views, linear, relation_mlp, relation_scale, run_views, views_chunk, views_mean  # noqa: F401
 from .plan import BF16_FAMILIES, BF16_GEN_KINDS, BF16_NL_KINDS, Plan, _foldable, model_precision  # noqa: F401
 from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput,  # noqa: F401
-                    StemF32Step, StemStep, _ConcatRowsPack, _Ref, _dense16, _device_ctx, _geom, _ptr, _r4, _r8, _r128,
+                    StemBf16Step, StemF32Step, StemStep, _ConcatRowsPack, _Ref, _dense16, _device_ctx, _geom, _ptr, _r4, _r8, _r128,
                     _same_geometry, _stem_ld, _stream, _t3, _tag, _tile_dims, issued_conv_flop)
 from .tuned import (BODY_FILTERS, BODY_SHAPES, _TUNED_PATH, _chain_config_index, _config_index, _flags_kind,  # noqa: F401
                     _tile_kind, _tuned_table, alt_lookup, alt_store, body_lookup, body_store, chain_key, chain_lookup,
@@ -132,6 +132,13 @@ class Engine:
         # It governs float32 models only: a model whose parameters are bfloat16 runs the bf16 plans (bf16 operands on the
         # bf16 matrix cores, fp32 accumulate, bf16 activations) whatever it is set to (INTEGRATION.md, bf16 inference).
         self._precision = os.environ.get("PTX_PRECISION", "fp32")
+        # Stem of the bf16 plans (opt-in, like PTX_PROGRAM / PTX_NL_STREAMK):
+        #   "fold"    (default) ptx_im2col_hw_bf16 + a (kT,1,1) conv on the generic bf16 tiles; bf16 models take bf16 clips only;
+        #   "direct"  ptx_conv_stem_bf16_fwd: one patch-resident kernel that reads the bf16 clip -- or decoded uint8 frames,
+        #             normalised while they are staged, so forward_frames / frames-out forward_views accept bf16 models.
+        # Changing it drops the compiled plans.  Same operands as "fold", another summation order.
+        self._bf16_stem = "fold"
+        self.bf16_stem = os.environ.get("PTX_BF16_STEM", "fold")
         # Opt-in autograd routing (eager.wanted): with grad mode on and trainable parameters, eval-mode calls run the
         # zoo's torch.nn children and return a differentiable output, as the reference does (frozen-BN fine-tuning).
         # Off by default: every nn.Parameter requires grad, so plain inference without torch.no_grad() would leave
@@ -192,6 +199,18 @@ class Engine:
             raise PtxError("Engine.precision must be 'fp32' or 'x3' (got %r)" % (value,))
         if value != self._precision:
             self._precision = value
+            self.invalidate()
+
+    @property
+    def bf16_stem(self):
+        return self._bf16_stem
+
+    @bf16_stem.setter
+    def bf16_stem(self, value):
+        if value not in ("fold", "direct"):
+            raise PtxError("Engine.bf16_stem must be 'fold' or 'direct' (got %r)" % (value,))
+        if value != self._bf16_stem:
+            self._bf16_stem = value
             self.invalidate()
 
     def __deepcopy__(self, memo):
@@ -293,7 +312,7 @@ class Engine:
         nkey = None if norm is None else (tuple(norm.mean), tuple(norm.std), norm.swap_rb, norm.to_255)
         key = (shape, x.device.index, nkey) + ((lane,) if lane else ())
         if model_precision(model) == "bf16":
-            key += ("bf16",)
+            key += ("bf16",) + (("direct",) if self._bf16_stem == "direct" else ())
         with self._lock:
             plan = self._plans.get(key)
             fresh = plan is None
@@ -647,8 +666,10 @@ class Engine:
                            "pretrained models, torchvision_models.py:162-166): pass opts=pretrained_settings[...]")
         if model.training:
             raise PtxError("pretorched-x_amd is a forward-only (inference) engine: call model.eval() first")
-        if model_precision(model) != "fp32":
-            raise PtxError("forward_frames runs float32 models only (this model's parameters are %s)" % model_precision(model))
+        prec = model_precision(model)
+        if prec != "fp32" and not (prec == "bf16" and self._bf16_stem == "direct"):
+            raise PtxError("forward_frames runs float32 models only (this model's parameters are %s)%s" % (
+                prec, "; engine().bf16_stem = 'direct' lets a bfloat16 model read the frames in its stem" if prec == "bf16" else ""))
         dims = model.arch.dims
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
             raise PtxError("forward_frames: frames must be a uint8 CUDA tensor")
@@ -679,19 +700,21 @@ class Engine:
         (a `transforms.SampleViews`: clips x crops, sampled on the device) of softmax(logits) (reduce="softmax"), of the
         logits ("logits"), or the logits of every view [N, V, classes] in the model's dtype (None).
         float32 models take the views as uint8 frames through forward_frames (views.out == "frames", `opts` as there);
-        bfloat16 models take the normalised bf16 clip through forward() (views: out="tensor", dtype=torch.bfloat16).
+        bfloat16 models take the normalised bf16 clip through forward() (views: out="tensor", dtype=torch.bfloat16) -- and,
+        under bf16_stem = "direct", also a frames-out sampler through forward_frames.
         Views are produced `chunk` at a time (default `views_chunk(N, V, max_batch)`: as many as the per-launch size
         limit allows), so only one chunk of views exists at any time."""
         prec = model_precision(model)
         if prec not in ("fp32", "bf16"):
             raise PtxError("forward_views runs float32 and bfloat16 models (this model's parameters are %s)" % prec)
-        check_views(views, model, "frames" if prec == "fp32" else "bf16")
+        frames_in = prec == "fp32" or (self._bf16_stem == "direct" and getattr(views, "out", None) == "frames")
+        check_views(views, model, "frames" if frames_in else "bf16", bf16_stem=self._bf16_stem)
         if getattr(model.arch, "dims", 3) != 3:
             raise PtxError("forward_views: a 2-D model takes images, not clips (TRN.forward_views runs a 2-D backbone on the "
                            "frames of a clip)")
         S = views.size
         mb = self._max_batch(model, (3, views.num_frames, S, S))
-        if prec == "fp32":
+        if frames_in:
             run = lambda frames: self.forward_frames(model, frames, opts)
         else:
             run = lambda clip: self.forward(model, clip)

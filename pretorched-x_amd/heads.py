@@ -71,7 +71,9 @@ def run_views(video, views, run, max_batch, reduce="softmax", chunk=None, who="f
     return buf if reduce is None else views_mean(buf, N, V, reduce)
 
 
-def check_views(views, model, want_out, who="forward_views"):
+def check_views(views, model, want_out, who="forward_views", bf16_stem="fold"):
+    """want_out: "frames" (the views go through forward_frames) or "bf16" (the normalised bf16 clip through forward()).
+    bf16_stem: the engine's switch -- under "direct" a bfloat16 model takes either kind, and the message says so."""
     from .transforms import SampleViews
     if not isinstance(views, SampleViews):
         raise PtxError("%s: views must be a pretorched.transforms.SampleViews, got %r" % (who, views))
@@ -80,7 +82,8 @@ def check_views(views, model, want_out, who="forward_views"):
                        "out='frames'" % who)
     if want_out == "bf16" and (views.out != "tensor" or views.dtype != torch.bfloat16):
         raise PtxError("%s: a bfloat16 model takes the views as the normalised bf16 clip: build the SampleViews with "
-                       "out='tensor', dtype=torch.bfloat16" % who)
+                       "out='tensor', dtype=torch.bfloat16%s" % (who, " (or out='frames': bf16_stem = 'direct' reads them in the stem)"
+                                                                if bf16_stem == "direct" else ""))
 
 
 # ---------------------------------------------------------------------------------------------

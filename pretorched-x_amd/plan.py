@@ -20,8 +20,8 @@ from ._lib import (ConvDesc, ConvFusedExt, ConvProgramInfo, ConvStage, NonlocalD
                    PTX_EPI_DUAL_RAW, PTX_EPI_OUT_F16, PTX_EPI_RELU, PTX_EPI_RES_ADD, PTX_EPI_RES_PADA, PTX_EPI_RES_UP, PTX_EPI_TANH,
                    PTX_F16_OPERANDS, PTX_F16X3_OPERANDS, PTX_NL_BF16, PTX_NL_F16, PTX_NL_OUT_F16, PTX_NL_RELU, PTX_NL_SCALE,
                    PTX_NL_SOFTMAX, PTX_NL_X3, PTX_POOL_BF16, PTX_POOL_PAD_ZERO, PTX_POOL_SAME, PTX_PRO_UP2, PTX_RES_F16,
-                   PTX_SPLITK_FUSED, PtxError, check)
-from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemF32Step,
+                   PTX_SPLITK_FUSED, PTX_STEM_SRC_BF16_NCDHW, PTX_STEM_SRC_U8_NTHWC, PtxError, check)
+from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step,
                     StemStep, _ConcatRowsPack, _Ref, _device_ctx, _geom, _ptr, _r4, _r8, _r128, _same_geometry, _stem_ld, _stream,
                     _t3, _tag)
 from .tuned import (BODY_FILTERS, BODY_SHAPES, _flags_kind, alt_lookup, body_lookup, chain_key, chain_lookup, prog_lookup,
@@ -95,6 +95,7 @@ class Plan:
         self._cur = model                # the model (or DataParallel replica) whose tensors are valid right now
         self.program_steps = []  # ProgramStep: runs of small-M convs as one persistent launch
         self.stem_bf16_step = None       # the bf16 stem's ConvStep (the tuner bounds its issued work)
+        self.bf16_stem = getattr(engine, "bf16_stem", "fold")            # "fold" | "direct" (ptx_conv_stem_bf16_fwd)
         self.stem_steps = self.patch_steps = self.attn_steps = 0         # launches outside conv_steps, by kind
         self.attn_descs, self.attn_operands = [], []                     # bf16 attention launches: descriptors, (th, ph, g, y)
         self._stem_src = {}              # stem_source()'s buffers by (uint8 frames?, row pitch)
@@ -586,14 +587,20 @@ class Plan:
         ptx_im2col_hw_bf16 folds the (kh, kw) taps of the caller's bf16 NCDHW clip into 147 channels (rows padded to 160),
         and the stem becomes a (kT, 1, 1) conv over them on the bf16 tiles -- 160 / 147 = 1.09x the algorithmic MACs
         issued (plus tile padding), no torch layout pass."""
-        if raw.norm is not None or raw.t_step != 1 or not isinstance(conv, nn.Conv3d):
-            raise PtxError("%s: the bf16 stem reads a bf16 NCDHW clip (uint8 frames / frame sub-sampling are fp32 only)" % label)
+        direct = self.bf16_stem == "direct"
+        if (raw.norm is not None and not direct) or raw.t_step != 1 or not isinstance(conv, nn.Conv3d):
+            raise PtxError("%s: the bf16 stem reads a bf16 NCDHW clip (uint8 frames / frame sub-sampling are fp32 only%s)" % (
+                label, "" if direct else "; Engine.bf16_stem = 'direct' reads uint8 frames"))
         (kT, kH, kW), (sT, sH, sW), (pT, pH, pW) = _geom(conv)
         if getattr(conv, "tf_same", False):
             raise PtxError("%s: SAME-padded stems are not supported in bf16" % label)
         Ho, Wo = (raw.H + 2 * pH - kH) // sH + 1, (raw.W + 2 * pW - kW) // sW + 1
         if min(Ho, Wo) < 1:
             raise PtxError("%s: input too small for the stem" % label)
+        if direct:
+            y = self.stem_bf16_direct(raw, conv, bn, relu, label)
+            if y is not None:
+                return y
         K = kH * kW * raw.C
         xf = self.act(raw.N, raw.T, Ho, Wo, K, ld=(K + 31) // 32 * 32, f16=True)
         lib, yp = self.lib, _ptr(xf.t)
@@ -604,6 +611,49 @@ class Plan:
         self.steps.append(_tag(im2col, "im2col_hw_bf16", 2 * N * Cc * T * H * W + 2 * xf.t.numel()))
         y = self.conv(xf, self.pack(conv, bn, fold_hw=True), (sT, 1, 1), (pT, 0, 0), relu=relu, label=label)
         self.stem_bf16_step = self.conv_steps[-1]
+        self.stem_steps += 1
+        return y
+
+    def stem_bf16_direct(self, raw, conv, bn, relu, label):
+        """Engine.bf16_stem = "direct": ONE ptx_conv_stem_bf16_fwd launch reads the caller's bf16 NCDHW clip -- or the decoded
+        uint8 frames, normalised while the patch is staged -- and serves every (kh, kw) tap from an LDS-resident patch: no
+        im2col pass, no 160-channel copy.  The filter is the fold path's own packed filter (same BN fold, same single
+        rounding), re-laid bit-exactly into the kernel's fragment order.  Returns None when the kernel refuses a bf16-clip
+        geometry (the fold path then runs); a refused uint8 geometry raises with the kernel's reason."""
+        (kT, kH, kW), (sT, sH, sW), (pT, pH, pW) = _geom(conv)
+        To, Ho, Wo = (raw.T + 2 * pT - kT) // sT + 1, (raw.H + 2 * pH - kH) // sH + 1, (raw.W + 2 * pW - kW) // sW + 1
+        Co = conv.out_channels
+        d = ConvDesc()
+        d.N, d.Ti, d.Hi, d.Wi, d.Ci, d.ldx = raw.N, raw.T, raw.H, raw.W, raw.C, 0
+        d.To, d.Ho, d.Wo, d.Co, d.ldy = To, Ho, Wo, Co, _r8(Co)
+        d.kT, d.kH, d.kW, d.sT, d.sH, d.sW, d.pT, d.pH, d.pW = kT, kH, kW, sT, sH, sW, pT, pH, pW
+        d.Co_pad = _r128(Co)
+        d.flags = PTX_F16_OPERANDS | PTX_BF16_OPERANDS | PTX_EPI_OUT_F16 | (PTX_EPI_RELU if relu else 0)
+        src = PTX_STEM_SRC_U8_NTHWC if raw.norm is not None else PTX_STEM_SRC_BF16_NCDHW
+        lib = self.lib
+        if To < 1 or not lib.ptx_conv_stem_bf16_supported(C.byref(d), src):
+            if raw.norm is not None:
+                raise PtxError("%s: the direct bf16 stem cannot read these uint8 frames: %s" % (
+                    label, lib.ptx_last_error().decode(errors="replace") if To >= 1 else "input too short for the stem"))
+            return None
+        pk = self.pack(conv, bn, fold_hw=True)           # [kT][Co_pad][Kc] bf16, k = (kh*kW + kw)*Cin + c: the fold path's filter
+        w2 = torch.empty(lib.ptx_stem_bf16_weight_elems(C.byref(d)), device=self.dev, dtype=torch.bfloat16)
+        self.keepalive.append(w2)
+        wsrc, w2p = _ptr(pk.w), _ptr(w2)
+
+        def relay():
+            check(lib.ptx_pack_stem_bf16_weight(C.byref(d), wsrc, w2p, _stream()), "ptx_pack_stem_bf16_weight")
+        self.refreshers.append(relay)
+        y = self.act(raw.N, To, Ho, Wo, Co, f16=True)
+        st = StemBf16Step()
+        st.d, st.plan, st.src, st.w, st.b, st.y, st.label = d, self, src, w2p, _ptr(pk.b), _ptr(y.t), label
+        if raw.norm is not None:
+            st.norm = raw.norm
+            self.keepalive.append(raw.norm)
+        st.macs = raw.N * To * Ho * Wo * Co * raw.C * kT * kH * kW
+        # compulsory traffic: the clip (or the frames) once in, the bf16 activation out, the filter
+        st.hbm_bytes = raw.N * raw.C * raw.T * raw.H * raw.W * (1 if raw.norm is not None else 2) + 2 * y.t.numel() + 2 * w2.numel()
+        self.steps.append(st)
         self.stem_steps += 1
         return y
 
@@ -1224,7 +1274,7 @@ class Plan:
         out = []
         for s in self.steps:
             for t in (s.active() if isinstance(s, (AltStep, ProgramStep)) else [s]):
-                if isinstance(t, (ConvStep, ChainStep, StemStep, StemF32Step, PatchConvStep, ProgramStep)):
+                if isinstance(t, (ConvStep, ChainStep, StemStep, StemF32Step, StemBf16Step, PatchConvStep, ProgramStep)):
                     out.append(t)
         return out
 

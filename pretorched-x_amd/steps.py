@@ -599,3 +599,39 @@ class StemF32Step(_Step):
         # src: a plan-owned fp32 NCDHW buffer (normalised uint8 frames / pitch-padded rows) or None = the caller's tensor
         x = self.src if self.src is not None else self.plan.in_ptr
         check(_lib.lib().ptx_conv_stem_f32_fwd(C.byref(self.d), x, sn, sc, stt, self.w, self.b, self.y, st), self.label)
+
+
+def stem_bf16_tiles(d):
+    """Tiles per output frame of ptx_conv_stem_bf16_fwd (host-side twin of stem_bf16_geom, csrc/conv_stem_bf16.hip): raster
+    runs of 256 outputs while the full-width input patch fits 40 KiB of LDS, else segments of <= 256 outputs of one row."""
+    nrows = min(d.Ho, (255 + d.Wo - 1) // d.Wo + 1)
+    if ((nrows - 1) * d.sH + d.kH) * ((d.Wo - 1) * d.sW + 8) * 8 <= 40960:
+        return -(-(d.Ho * d.Wo) // 256)
+    return d.Ho * -(-d.Wo // 256)
+
+
+class StemBf16Step(_Step):
+    """One ptx_conv_stem_bf16_fwd launch (Engine.bf16_stem = "direct"): the RGB stem of a bf16 plan on the bf16 matrix
+    cores, read straight from the caller's bf16 NCDHW clip or from decoded uint8 frames (bound per run: plan.in_ptr;
+    `norm` set = uint8 frames, normalised while the patch is staged) -- no im2col pass, no folded copy."""
+    __slots__ = ("d", "plan", "src", "norm", "w", "b", "y", "label", "macs", "hbm_bytes")
+    _defaults = {"hbm_bytes": 0, "norm": None}
+    kernel = "conv_stem_bf16"
+
+    def issued_flop(self):
+        """FLOP of the MFMAs one launch ISSUES: per 256-output tile and (kt, kh) step inside the clip, 4 waves x 4 position
+        tiles x one v_mfma_f32_16x16x32_bf16 (K = 8 pixels x 4 channels = 32 for the 21 live entries of a kW = 7 row; 16384
+        FLOP) per 16-channel tile that holds channels below ldy."""
+        d = self.d
+        tiles = stem_bf16_tiles(d)
+        per_step = 4 * 4 * -(-d.ldy // 16) * 16384
+        steps = 0
+        for to in range(d.To):
+            t0 = to * d.sT - d.pT
+            steps += max(0, min(d.kT - 1, d.Ti - 1 - t0) - max(0, -t0) + 1) * d.kH
+        return float(d.N * tiles * steps * per_step)
+
+    def __call__(self, st):
+        norm = C.byref(self.norm) if self.norm is not None else None
+        check(_lib.lib().ptx_conv_stem_bf16_fwd(C.byref(self.d), self.plan.in_ptr, self.src, norm, self.w, self.b, self.y, st),
+              self.label)

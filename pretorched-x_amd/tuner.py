@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import PtxError
-from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemF32Step, StemStep, _dense16, _r4,
+from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemBf16Step, StemF32Step, StemStep, _dense16, _r4,
                     _stream, issued_conv_flop)
 from .tuned import (BODY_SHAPES, _flags_kind, _tile_kind, alt_lookup, alt_store, body_lookup, body_store, chain_lookup,
                     chain_store, lanes_key, lanes_lookup, lanes_store, prog_lookup, prog_store, save_tuned_table, tuned_lookup,
@@ -422,7 +422,7 @@ def profile_steps(engine, plan, iters=5, isolated=None):
             rows.append((stp.label, "stem", 0, stp.macs, ms, stp.kernel))
         elif isinstance(stp, ConvStep):
             rows.append((stp.label, "conv", 0, stp.macs, ms, _lib.lib().ptx_conv3d_config_name(stp.cfg).decode(), stp))
-        elif isinstance(stp, (StemStep, StemF32Step, PatchConvStep)):      # direct (patch) kernels are convs too
+        elif isinstance(stp, (StemStep, StemF32Step, StemBf16Step, PatchConvStep)):      # direct (patch) kernels are convs too
             rows.append((stp.label, "stem", 0, stp.macs, ms, stp.kernel))
         elif isinstance(stp, (ChainStep, ProgramStep)):     # several convs in one launch, their own tile tables
             rows.append((stp.label, "chain", 0, stp.macs, ms, stp.kernel))
