@@ -321,6 +321,36 @@ int ptx_conv_body_chain_f32_fwd(const ptx_conv3d_desc* conv, const ptx_conv3d_de
                                 const float* bias, const float* w_tail, const float* bias2, const float* res, float* y, int shape,
                                 ptx_stream_t stream);
 
+/* Stride-1 (kT,3,3) fp32 convolution as Winograd F(2x2,3x3) transforms around a grouped GEMM (csrc/conv_wino_f32.hip) -- a
+ * third execution of `conv2` of a Bottleneck / the convs of a BasicBlock (resnet3D.py:86-104,117,129-131), chosen per problem
+ * by measurement: 16 multiplies per 2x2 outputs and channel pair instead of 36, the temporal taps extend K.  Three launches:
+ *   ptx_wino_in_f32    V = B^T d B on the 4x4 input patch at rows 2i-1..2i+2, columns 2j-1..2j+2 (zero outside the image):
+ *                      x [N][T][H][W][ldx] -> V [N][T][H/2][W/2][16 * Cg], Cg = round_up(Ci, 4), transform position
+ *                      xi = 4 a + b (row a, column b) major over channels; pad channels are written as zero.
+ *   ptx_conv3d_fwd     on the descriptor ptx_conv_wino_f32_gemm_desc fills: groups = 16 (the transform positions), filter
+ *                      (kT,1,1), padding (kT/2,0,0), Ci = ldx = 16 * Cg, Co = ldy = 16 * Cog (Cog = round_up(Co, 4)), Kc = Cg,
+ *                      no flags; bias = res = NULL, split_k = 1, any tile the grouped descriptor runs on: V -> M.
+ *   ptx_wino_out_f32   y = A^T m A + bias (+ res) (ReLU): M [N][T][H/2][W/2][16 * Cog] -> y [N][T][H][W][ldy]; columns
+ *                      [0, round_up(Co, 4)) of every row are written ([Co, ..) as zero), columns beyond are left untouched,
+ *                      as ptx_conv3d_fwd does.  bias: [Co_pad] of the conv's own pack (may be NULL); res: same shape as y,
+ *                      row stride ldr (PTX_EPI_RES_ADD).
+ *   desc: the DIRECT convolution's descriptor -- fp32 operands, kH = kW = 3, kT in {1, 3}, unit strides, padding (kT/2,1,1),
+ *         groups <= 1, Hi and Wi even, flags within PTX_EPI_RELU | PTX_EPI_RES_ADD; x, y, res, V, M and the filters each
+ *         below 2 GiB.  ptx_conv_wino_f32_supported: 1 if it can run here, else 0 with the reason in ptx_last_error().
+ *   workspace: ptx_conv_wino_f32_workspace_bytes(desc) = V, rounded up to 256 bytes, then M.
+ *   w_wino: ptx_pack_wino_f32_weight(desc, w_packed) from the ptx_pack_conv_weight image of the same filter
+ *         ([tap][Co_pad][Kc], BN folded): U = G g G^T per (co, kt, ci) in the packed layout of the grouped descriptor
+ *         ([kt][rows][Cg], row = xi * Cog + co), ptx_wino_f32_weight_elems floats.  The bias is not touched.
+ * Arithmetic: fp32 throughout; the result differs from the direct path by fp32 reorder noise (1e-6 of the output scale). */
+int ptx_conv_wino_f32_supported(const ptx_conv3d_desc* desc);
+size_t ptx_conv_wino_f32_workspace_bytes(const ptx_conv3d_desc* desc);
+int ptx_conv_wino_f32_gemm_desc(const ptx_conv3d_desc* desc, ptx_conv3d_desc* gemm);
+size_t ptx_wino_f32_weight_elems(const ptx_conv3d_desc* desc);
+int ptx_pack_wino_f32_weight(const ptx_conv3d_desc* desc, const float* w_packed, float* w_wino, ptx_stream_t stream);
+int ptx_wino_in_f32(const ptx_conv3d_desc* desc, const float* x, float* V, ptx_stream_t stream);
+int ptx_wino_out_f32(const ptx_conv3d_desc* desc, const float* M, const float* bias, const float* res, float* y,
+                     ptx_stream_t stream);
+
 /* Operands of the fused generator-stage epilogue (see PTX_EPI_AFFINE / PTX_EPI_DUAL_RAW). */
 typedef struct ptx_conv_fused_ext {
     const float* scale;   /* [N][ld_affine] per-sample, per-output-channel scale (ptx_cbn_fold)  */

@@ -1254,3 +1254,6 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 
 // So is the patch-resident bf16 stem (it normalises uint8 frames with resize_common.h's normalise_u8 while it stages them).
 #include "conv_stem_bf16.hip"
+
+// So are the Winograd F(2x2, 3x3) transforms around the grouped implicit GEMM (two memory-bound passes and a filter transform).
+#include "conv_wino_f32.hip"

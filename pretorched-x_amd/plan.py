@@ -21,11 +21,11 @@ from ._lib import (ConvDesc, ConvFusedExt, ConvProgramInfo, ConvStage, NonlocalD
                    PTX_F16_OPERANDS, PTX_F16X3_OPERANDS, PTX_NL_BF16, PTX_NL_F16, PTX_NL_OUT_F16, PTX_NL_RELU, PTX_NL_SCALE,
                    PTX_NL_SOFTMAX, PTX_NL_X3, PTX_POOL_BF16, PTX_POOL_PAD_ZERO, PTX_POOL_SAME, PTX_PRO_UP2, PTX_RES_F16,
                    PTX_SPLITK_FUSED, PTX_STEM_SRC_BF16_NCDHW, PTX_STEM_SRC_U8_NTHWC, PtxError, check)
-from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step,
+from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step, WinoStep,
                     StemStep, _ConcatRowsPack, _Ref, _device_ctx, _geom, _ptr, _r4, _r8, _r128, _same_geometry, _stem_ld, _stream,
                     _t3, _tag)
 from .tuned import (BODY_FILTERS, BODY_SHAPES, _flags_kind, alt_lookup, body_lookup, chain_key, chain_lookup, prog_lookup,
-                    tuned_lookup)
+                    tuned_lookup, wino_lookup)
 
 # bf16 inference (a model whose floating-point parameters are torch.bfloat16): the families whose plans run end to end on the
 # bf16 kernels.  Everything else raises at plan build time.
@@ -94,6 +94,8 @@ class Plan:
         self._names = {id(m): n for n, m in model.named_modules()}
         self._cur = model                # the model (or DataParallel replica) whose tensors are valid right now
         self.program_steps = []  # ProgramStep: runs of small-M convs as one persistent launch
+        self.wino_steps = []     # WinoStep: direct launch | Winograd transforms around a grouped conv, chosen by measurement
+        self.wino_bytes, self.wino_arena = 0, None       # V / M arena of the Winograd steps (the largest step's need)
         self.stem_bf16_step = None       # the bf16 stem's ConvStep (the tuner bounds its issued work)
         self.bf16_stem = getattr(engine, "bf16_stem", "fold")            # "fold" | "direct" (ptx_conv_stem_bf16_fwd)
         self.stem_steps = self.patch_steps = self.attn_steps = 0         # launches outside conv_steps, by kind
@@ -106,6 +108,7 @@ class Plan:
         with _device_ctx(dev):
             self._build(model)
             self._fuse_programs()
+            self._bind_wino_arena()
             if self.ws_bytes:
                 self.ws = torch.zeros(self.ws_bytes // 4, device=dev, dtype=torch.float32)
                 self.ws_ptr = _ptr(self.ws)
@@ -193,7 +196,7 @@ class Plan:
             return (y, raw_act) if raw else y
         self._body_kernel(st, pk, x2)
         self._pick_tile(st, 4 * x.N * out[0] * out[1] * out[2] * y.ld)
-        self.steps.append(st)
+        self.steps.append(self._wino(st, pk, x2) or st)
         self.conv_steps.append(st)
         return (y, raw_act) if raw else y
 
@@ -354,6 +357,63 @@ class Plan:
             self.refreshers.append(repack_body)
         st.body = self._body_choice(json.dumps(d.key()), st.body_ok)
 
+    def _wino(self, st, pk, x2):
+        """Winograd F(2x2,3x3) (csrc/conv_wino_f32.hip): a further execution of a stride-1 (kT,3,3) fp32 conv as three launches
+        -- input transform, a 16-group (kT,1,1) conv on the ordinary tiles, output transform -- chosen per problem by the
+        tuner ("wino:" keys; default direct).  Returns the WinoStep that stands for `st` in the plan, or None when the conv is
+        not eligible (ptx_conv_wino_f32_supported) or PTX_CONV_WINO=0.  The grouped conv is NOT one of `conv_steps`: the tuner
+        sweeps its tile in the Winograd phase, only where a verdict is being measured."""
+        mode = os.environ.get("PTX_CONV_WINO", "auto")
+        d, lib_ = st.d, self.lib
+        if (mode == "0" or st.fused or x2 is not None or not isinstance(pk, Packed) or pk.f16 or pk.x3 or pk.fold_kw or pk.groups > 1
+                or (d.kH, d.kW) != (3, 3) or not lib_.ptx_conv_wino_f32_supported(C.byref(d))):
+            return None
+        gd = ConvDesc()
+        check(lib_.ptx_conv_wino_f32_gemm_desc(C.byref(d), C.byref(gd)), "ptx_conv_wino_f32_gemm_desc")
+        u = torch.empty(int(lib_.ptx_wino_f32_weight_elems(C.byref(d))), device=self.dev, dtype=torch.float32)
+        self.keepalive.append(u)
+        wsrc, wdst = _ptr(pk.w), _ptr(u)
+
+        def repack_wino(d=d, lib_=lib_, wsrc=wsrc, wdst=wdst):
+            check(lib_.ptx_pack_wino_f32_weight(C.byref(d), wsrc, wdst, _stream()), "ptx_pack_wino_f32_weight")
+        if torch.device(self.dev).type != "meta":
+            self.refreshers.append(repack_wino)
+        g = ConvStep()
+        g.d, g.w, g.b, g.res, g.plan, g.label, g.macs = gd, wdst, C.c_void_p(0), C.c_void_p(0), self, st.label + ".wino_gemm", st.macs
+        tuned = tuned_lookup(json.dumps(gd.key()), "")
+        if tuned is not None and lib_.ptx_conv3d_config_supported(C.byref(gd), tuned[0]):
+            g.cfg, g.from_table = tuned[0], True
+        else:
+            g.cfg = lib_.ptx_conv3d_pick_config(C.byref(gd), None)
+        w = WinoStep()
+        w.gemm, w.direct, w.label, w.key = g, [st], st.label, json.dumps(d.key())
+        w.arena_bytes = int(lib_.ptx_conv_wino_f32_workspace_bytes(C.byref(d)))
+        w.v_bytes = w.arena_bytes - 4 * gd.N * gd.To * gd.Ho * gd.Wo * gd.ldy
+        self.wino_bytes = max(self.wino_bytes, w.arena_bytes)
+        xp, bp, rp, yp, label = st.x, st.b, st.res, st.y, st.label
+
+        def wino_in(stream, w=w, d=d, lib_=lib_, xp=xp, label=label):
+            check(lib_.ptx_wino_in_f32(C.byref(d), xp, w.v_ptr, stream), label + ".wino_in")
+
+        def wino_out(stream, w=w, d=d, lib_=lib_, bp=bp, rp=rp, yp=yp, label=label):
+            check(lib_.ptx_wino_out_f32(C.byref(d), w.m_ptr, bp, rp, yp, stream), label + ".wino_out")
+        pos, tiles = d.N * d.Ti * d.Hi * d.Wi, gd.N * gd.To * gd.Ho * gd.Wo
+        w.wino = [_tag(wino_in, "wino_in", 4 * (pos * d.Ci + tiles * gd.ldx)), g,
+                  _tag(wino_out, "wino_out", 4 * (tiles * gd.ldy + pos * d.Co * (2 if d.flags & PTX_EPI_RES_ADD else 1)))]
+        w.use_wino = mode == "1" or bool(wino_lookup(w.key))
+        self.wino_steps.append(w)
+        return w
+
+    def _bind_wino_arena(self):
+        """One arena for V and M of every Winograd step, sized for the largest: a step's two buffers are live only between
+        its own three launches."""
+        if not self.wino_bytes:
+            return
+        self.wino_arena = torch.empty(self.wino_bytes // 4, device=self.dev, dtype=torch.float32)
+        for w in self.wino_steps:
+            w.v_ptr, w.m_ptr = _ptr(self.wino_arena), _ptr(self.wino_arena, w.v_bytes // 4)
+            w.gemm.x, w.gemm.y = w.v_ptr, w.m_ptr
+
     def _pick_tile(self, st, out_bytes):
         """Tile configuration and split-K of a ConvStep: the tuned table's entry when this build can run it, else the library's
         own pick; and room in the split-K workspace."""
@@ -462,9 +522,19 @@ class Plan:
         a.chain, a.pair, a.label, a.key = chain, pair, label, chain.key
         known = alt_lookup(chain.key)
         a.use_chain = known if known is not None else (_r4(chain.d.Co) <= int(os.environ.get("PTX_CHAIN_DEFAULT_MAX_N1", "64")))
+        for w in pair:
+            if isinstance(w, WinoStep):      # the pair's first conv also has a Winograd form: its verdict is the pair's
+                w.alt, w.key = a, chain.key
+                w.use_wino = os.environ.get("PTX_CONV_WINO", "auto") == "1" or bool(wino_lookup(w.key))
+                if w.use_wino:
+                    a.use_chain = False
         force = os.environ.get("PTX_CHAIN_FORCE")          # "1" / "0": A/B runs
         if force in ("0", "1"):
             a.use_chain = force == "1"
+        if a.use_chain:                                    # (a forced chain: the pair's Winograd form does not run)
+            for w in pair:
+                if isinstance(w, WinoStep):
+                    w.use_wino = False
         self.steps.append(a)
         self.alt_steps.append(a)
         return a
@@ -1273,7 +1343,7 @@ class Plan:
         autotuner owns) and the direct stem kernels."""
         out = []
         for s in self.steps:
-            for t in (s.active() if isinstance(s, (AltStep, ProgramStep)) else [s]):
+            for t in (s.active() if isinstance(s, (AltStep, ProgramStep, WinoStep)) else [s]):
                 if isinstance(t, (ConvStep, ChainStep, StemStep, StemF32Step, StemBf16Step, PatchConvStep, ProgramStep)):
                     out.append(t)
         return out

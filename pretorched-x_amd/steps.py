@@ -347,7 +347,8 @@ def issued_conv_flop(d, tile, words=1):
     M = d.N * d.To * d.Ho * d.Wo
     ncol = _r4(d.Co)
     n_tiles = -(-ncol // BN)
-    kch = -(-max(d.ldx, d.Kc) // BK)
+    # a grouped conv walks its own group's input columns only (Kc per tap), not the whole row
+    kch = -(-(d.Kc if d.groups > 1 else max(d.ldx, d.Kc)) // BK)
     if d.x2_C > 0 and d.x2_ld > 0:
         kch = -(-d.ldx // BK) + -(-d.x2_ld // BK)
     m = np.arange(M, dtype=np.int64)
@@ -499,7 +500,28 @@ class AltStep(_Step):
                 s(st)
 
     def active(self):
-        return [self.chain] if self.use_chain else list(self.pair)
+        if self.use_chain:
+            return [self.chain]
+        return [t for s in self.pair for t in (s.active() if isinstance(s, WinoStep) else [s])]
+
+
+class WinoStep(_Step):
+    """A stride-1 (kT,3,3) fp32 conv with two compiled executions: the direct launch (`direct`: its ConvStep, on a tile or
+    the body kernel) or Winograd F(2x2,3x3) as three launches (`wino`: the input transform, the grouped (kT,1,1) ConvStep
+    `gemm` on the ordinary tiles, the output transform with the conv's bias / residual / ReLU; csrc/conv_wino_f32.hip).
+    Which one runs is measured per problem by the tuner ("wino:" keys) and defaults to direct; PTX_CONV_WINO=0 compiles no
+    such step, =1 runs the Winograd launches wherever they exist.  `alt`: the AltStep whose pair this conv is the first
+    launch of (a bottleneck's conv2 + conv3), or None: the Winograd form then competes with the chained launch too, and
+    winning it switches the AltStep to its pair.  V and M live in the plan's Winograd arena (bound once it is allocated)."""
+    __slots__ = ("direct", "wino", "gemm", "use_wino", "alt", "label", "key", "v_ptr", "m_ptr", "v_bytes", "arena_bytes")
+    _defaults = {"use_wino": False}
+
+    def __call__(self, st):
+        for s in (self.wino if self.use_wino else self.direct):
+            s(st)
+
+    def active(self):
+        return list(self.wino if self.use_wino else self.direct)
 
 
 

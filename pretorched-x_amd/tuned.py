@@ -6,6 +6,7 @@ One dict, key -> (name, number), behind one lock.  The entry kinds share it by k
     alt:<pair key>      ("chain" | "pair", 1)                      alt_lookup / alt_store
     prog:<run hash>     ("program" | "launches", 1)                prog_lookup / prog_store
     body:<key>          ("tall" | "square" | "igemm", 1)           body_lookup / body_store
+    wino:<key>          (grouped conv's tile NAME, 1 | 2)          wino_lookup / wino_store   (1 Winograd runs, 2 direct stays)
     lanes:<model key>   ("lanes", n)                               lanes_lookup / lanes_store
 Tiles are stored by NAME, so inserting / reordering the library's configuration tables cannot remap an entry silently.
 """
@@ -173,6 +174,18 @@ def body_lookup(key):
 
 def body_store(key, shape):
     _put("body:" + key, BODY_SHAPES[shape] if shape is not None and shape >= 0 else "igemm")
+
+
+def wino_lookup(key):
+    """Tuned verdict of a stride-1 (kT,3,3) problem (conv key, or the chain key of the pair it opens) on the Winograd
+    launches: True = they run, False = the direct execution stays, None = never measured.  Like every entry the value names
+    a tile -- the one the grouped conv was measured on -- and the number carries the verdict: 1 Winograd, 2 direct."""
+    ent = _get("wino:" + key)
+    return None if ent is None else ent[1] == 1
+
+
+def wino_store(key, use_wino, cfg_index):
+    _put("wino:" + key, _lib.lib().ptx_conv3d_config_name(int(cfg_index)).decode(), 1 if use_wino else 2)
 
 
 def lanes_key(model, shape, precision="fp32"):

@@ -1,6 +1,6 @@
 """Autotune and profiling, as functions of (engine, plan): every decision the tuned table (tuned.py) remembers is measured
 here with HIP events on the plan's own buffers -- conv tiles and split-K, chained tiles, the body kernels against either,
-chained launch vs its pair, conv program vs its launches, clip lanes -- and so are the per-launch times bench.py reports.
+chained launch vs its pair, Winograd launches vs the direct execution, conv program vs its launches, clip lanes -- and so are the per-launch times bench.py reports.
 `Engine.autotune / _autotune / tune_lanes / profile_convs / profile_steps` delegate here.
 """
 import ctypes as C
@@ -12,11 +12,11 @@ import torch
 
 from . import _lib
 from ._lib import PtxError
-from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemBf16Step, StemF32Step, StemStep, _dense16, _r4,
-                    _stream, issued_conv_flop)
+from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemBf16Step, StemF32Step, StemStep, WinoStep, _dense16,
+                    _r4, _stream, issued_conv_flop)
 from .tuned import (BODY_SHAPES, _flags_kind, _tile_kind, alt_lookup, alt_store, body_lookup, body_store, chain_lookup,
                     chain_store, lanes_key, lanes_lookup, lanes_store, prog_lookup, prog_store, save_tuned_table, tuned_lookup,
-                    tuned_store)
+                    tuned_store, wino_lookup, wino_store)
 
 
 def _time_ms(run, iters):
@@ -93,6 +93,7 @@ def _autotune(engine, model, x, iters=3, verbose=False, persist=False, only_untu
         _tune_conv_tiles(t)
         _tune_chain_tiles(t)
         _tune_chain_vs_pair(t)
+        _tune_wino_vs_direct(t)
         _tune_program_vs_launches(t)
         plan.run_features(_dense16(x))
         plan.tuned = True
@@ -177,9 +178,9 @@ def _tune_conv_tiles(t):
                 t.lib.ptx_conv3d_config_name(best[1]).decode(), best[2], best[0], 2e-9 * stp.macs / best[0]))
 
 
-def _best_conv_tile(t, stp, key, kind):
+def _best_conv_tile(t, stp, key, kind, split_k=True):
     """(ms, tile index, split-K) of the fastest admissible tile for one conv step (ms NaN and the library's default when
-    nothing admissible could be timed)."""
+    nothing admissible could be timed).  split_k=False: split 1 only (the grouped conv of a Winograd step)."""
     lib, d, best = t.lib, stp.d, None
     # PTX_TUNE_CANDIDATES="dma4/re,dma3/re": a targeted session -- only tiles whose name holds one of the
     # substrings are timed, next to the table's incumbent, which keeps its place unless beaten by 2 %
@@ -209,7 +210,7 @@ def _best_conv_tile(t, stp, key, kind):
             continue
         blocks = ((M + tile[0] - 1) // tile[0]) * ((ncol + tile[1] - 1) // tile[1])
         splits = [1]
-        if blocks < 512:
+        if blocks < 512 and split_k:
             splits += [s for s in (2, 3, 4, 6, 8) if steps_k // s >= 4 and blocks * s <= 2048]
         for sk in splits:
             if sk > 1 and lib.ptx_conv3d_workspace_bytes(C.byref(d), sk) > t.plan.ws_bytes:
@@ -295,8 +296,52 @@ def _tune_chain_vs_pair(t):
                "tune %-34s chain %.4f ms | pair %.4f ms -> %s" % (a.label, ms2[0], ms2[1], verdict))
 
 
+def _tune_wino_vs_direct(t):
+    """Phase 4, Winograd F(2x2,3x3) vs the direct execution of every distinct eligible stride-1 (kT,3,3) problem: tune the
+    grouped conv's tile like any conv (split 1), then time the three launches against the best direct execution the earlier
+    phases left in place -- the tile or body kernel, or, where the conv opens a bottleneck tail, the chain-or-pair verdict
+    with the tail's conv3 on both sides -- under the same 3 % margin as _tune_chain_vs_pair."""
+    if os.environ.get("PTX_CONV_WINO", "auto") in ("0", "1"):
+        return
+    seen = {}
+    for w in t.plan.wino_steps:
+        g, a = w.gemm, w.alt
+        if w.key in seen:
+            w.use_wino, g.cfg = seen[w.key]
+            if w.use_wino and a is not None:
+                a.use_chain = False
+            continue
+        if t.only_untuned and wino_lookup(w.key) is not None:
+            continue
+        if a is not None and os.environ.get("PTX_CHAIN_FORCE") == "1":
+            continue                         # the chained launch is pinned: nothing to decide for the pair's first conv
+        gkey = json.dumps(g.d.key())
+        if not (t.only_untuned and tuned_lookup(gkey, "") is not None):
+            best = _best_conv_tile(t, g, gkey, "", split_k=False)
+            g.cfg, g.split, g.from_table = best[1], 1, False
+            tuned_store(gkey, best[1], 1)
+        run = _launch(a if a is not None else w)
+        n = max(t.iters, 3)
+        keep_chain = a.use_chain if a is not None else False
+        w.use_wino = False
+        ms_direct = _time_ms(run, n)
+        w.use_wino = True
+        if a is not None:
+            a.use_chain = False
+        ms_wino = _time_ms(run, n)
+        w.use_wino = ms_wino < 0.97 * ms_direct
+        if a is not None and not w.use_wino:
+            a.use_chain = keep_chain
+        seen[w.key] = (w.use_wino, g.cfg)
+        wino_store(w.key, w.use_wino, g.cfg)
+        verdict = "wino" if w.use_wino else "direct"
+        tile = t.lib.ptx_conv3d_config_name(g.cfg).decode()
+        t.note("%s\tdirect %.4f ms\twino %.4f ms (%s)\t-> %s\n" % (w.label, ms_direct, ms_wino, tile, verdict),
+               "tune %-34s direct %.4f ms | wino %.4f ms (%s) -> %s" % (w.label, ms_direct, ms_wino, tile, verdict))
+
+
 def _tune_program_vs_launches(t):
-    """Phase 4, conv program vs the launches it replaces (PTX_PROGRAM=auto only): time both executions of every run, keep
+    """Phase 5, conv program vs the launches it replaces (PTX_PROGRAM=auto only): time both executions of every run, keep
     the faster (same margin rule); a program that loses is dissolved into its launches."""
     plan = t.plan
     if os.environ.get("PTX_PROGRAM", "0") != "auto":
@@ -410,7 +455,7 @@ def profile_steps(engine, plan, iters=5, isolated=None):
     if isolated is None:
         isolated = os.environ.get("PTX_PROFILE_ISOLATED", "0") == "1"
     st = _stream()
-    flat = [t for s in plan.steps for t in (s.active() if isinstance(s, (AltStep, ProgramStep)) else [s])]
+    flat = [t for s in plan.steps for t in (s.active() if isinstance(s, (AltStep, ProgramStep, WinoStep)) else [s])]
     engine.last_profile = None
     if isolated:
         ms_of = [_time_ms(lambda stp=stp: stp(st), iters) for stp in flat]
