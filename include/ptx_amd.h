@@ -638,6 +638,46 @@ int ptx_resize_build_tables(const ptx_resize_desc* desc, const ptx_resize_geom* 
                             int32_t* row_lo, int32_t* row_n, int32_t* row_k, /* [N][Ho], [N][Ho], [N][Ho][taps_h] */
                             int32_t* col_lo, int32_t* col_n, int32_t* col_k, /* [N][Wo], [N][Wo], [N][Wo][taps_w] */
                             ptx_stream_t stream);
+/* Training clips from videos of ANY size in one launch: every output clip has a SOURCE of its own as well as tables of its
+ * own -- a batch made of N separately decoded videos of different frame sizes and lengths, read in place through a frame
+ * index row per clip, with no gathered or same-size copy of any video.  srcs: DEVICE array [N], one row per OUTPUT clip
+ * (several clips of one video repeat its row); frame_idx: DEVICE [N][T], output frame ti of clip n is source frame
+ * clamp(frame_idx[n * T + ti], 0, Tv_n - 1) at base_n + t * stride_t_n.  desc: N output clips of T frames; H / W are the
+ * LARGEST frame extents of any source (the launch plan's row staging is sized from them); Ho = Wo = S; taps_h / taps_w the
+ * common pitch; out_mode as everywhere.  The six tables and the output are laid out as for ptx_resize_frames_u8_tables
+ * (y: uint8 [N][T][Ho][Wo][C], or fp32 / bf16 [N][C][T][Ho][Wo]).
+ * From the clip's frame on the arithmetic is ptx_resize_frames_u8_tables': clip n's result is bit-identical to that entry
+ * point on the clip's gathered frames with the clip's tables, and the yuv420 form to the u8 form on the converted frames.
+ * A garbage row gives wrong pixels, never a stray access inside the frame arithmetic: the kernel clamps a row's H / W into
+ * [1, desc->H] / [1, desc->W], Tv to >= 1, frame indices into [0, Tv) and table entries to the clip's own frame.  Base
+ * pointers (and a YUV row's pitches) are trusted, exactly as `frames` is.  The host checks what needs no device: null
+ * pointers and everything ptx_resize_frames_u8 checks (the yuv420 form: C == 3).  _supported: 1 if the call runs, else 0. */
+typedef struct ptx_clip_src {      /* one row per OUTPUT clip; DEVICE array [N]                               */
+    const uint8_t* base;           /* frame 0 of the clip's video; frames [H][W][C] contiguous, any alignment */
+    int64_t stride_t;              /* bytes between frames, >= H * W * C                                      */
+    int32_t H, W, Tv;              /* this video's frame size and length                                      */
+    int32_t reserved;              /* 0                                                                       */
+} ptx_clip_src;
+typedef struct ptx_clip_src_yuv420 {
+    ptx_yuv420_src planes;         /* y/u/v at frame 0 of the clip's video; stride_n_* ignored                */
+    int32_t H, W, Tv, reserved;
+} ptx_clip_src_yuv420;
+int ptx_resize_clips_u8_supported(const ptx_resize_desc* desc);
+int ptx_resize_clips_u8(const ptx_resize_desc* desc, const ptx_clip_src* srcs, const int32_t* frame_idx, /* [N], [N][T] */
+                        const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, /* [N][Ho], [N][Ho], [N][Ho][taps_h] */
+                        const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, /* [N][Wo], [N][Wo], [N][Wo][taps_w] */
+                        void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+int ptx_resize_clips_yuv420_supported(const ptx_resize_desc* desc);
+int ptx_resize_clips_yuv420(const ptx_resize_desc* desc, const ptx_clip_src_yuv420* srcs, const int32_t* frame_idx,
+                            const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
+                            const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k,
+                            void* y, const ptx_norm_desc* norm, ptx_stream_t stream);
+/* ptx_resize_build_tables with the frame extents of clip n taken from srcs[n].H / .W (clamped into [1, desc->H] /
+ * [1, desc->W]) instead of desc: the same fp64 operations in the same order, the same bits.  Only H and W of a row are
+ * read, so the rows of the u8 form serve; a YUV batch passes rows that carry H and W alone.                             */
+int ptx_resize_build_tables_clips(const ptx_resize_desc* desc, const ptx_clip_src* srcs, const ptx_resize_geom* geoms,
+                                  int32_t* row_lo, int32_t* row_n, int32_t* row_k,
+                                  int32_t* col_lo, int32_t* col_n, int32_t* col_k, ptx_stream_t stream);
 /* ptx_resize_views_u8 on a YUV video: the source's strides address the frames, desc->stride_n / desc->stride_t are
  * IGNORED.  _supported returns 0 / 1 / 2 as ptx_resize_views_u8_supported does. */
 int ptx_resize_views_yuv420_supported(const ptx_views_desc* desc, const ptx_yuv420_src* src);

@@ -132,6 +132,17 @@ class Yuv420Src(C.Structure):
                [(n, C.c_int32) for n in ("pitch_y", "pitch_c", "step_c", "y_off", "ky", "krv", "kgu", "kgv", "kbu")]
 
 
+class ClipSrc(C.Structure):
+    """ptx_clip_src: the source of one OUTPUT clip of ptx_resize_clips_u8 (its video's frame 0, frame stride, size, length)."""
+    _fields_ = [("base", C.c_void_p), ("stride_t", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("Tv", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ClipSrcYuv420(C.Structure):
+    """ptx_clip_src_yuv420: the same for ptx_resize_clips_yuv420 (the planes at frame 0 of the clip's video)."""
+    _fields_ = [("planes", Yuv420Src), ("H", C.c_int32), ("W", C.c_int32), ("Tv", C.c_int32), ("reserved", C.c_int32)]
+
+
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
 
@@ -256,6 +267,11 @@ SIGNATURES = {
     "ptx_resize_frames_yuv420_tables": (C.c_int, [C.POINTER(ResizeDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _P,
                                                   C.POINTER(NormDesc), _P]),
     "ptx_resize_build_tables": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ptx_resize_clips_u8_supported": (C.c_int, [C.POINTER(ResizeDesc)]),
+    "ptx_resize_clips_u8": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+    "ptx_resize_clips_yuv420_supported": (C.c_int, [C.POINTER(ResizeDesc)]),
+    "ptx_resize_clips_yuv420": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+    "ptx_resize_build_tables_clips": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ptx_resize_views_yuv420_supported": (C.c_int, [C.POINTER(ViewsDesc), C.POINTER(Yuv420Src)]),
     "ptx_resize_views_yuv420": (C.c_int, [C.POINTER(ViewsDesc), C.POINTER(Yuv420Src), _P, _P, _P, _P, _P, _P, _P, _P,
                                           C.POINTER(NormDesc), _P]),

@@ -297,13 +297,24 @@ struct ResizeWindows {
     int h, w;                        // entries of the row / column tables
 };
 
-template <int C, bool YUV = false, bool WIN = false, bool TAB = false>
+// CLIPS (ptx_resize_clips_*, resize_clips.hip): every clip has a SOURCE of its own as well as tables of its own: row
+// clip of `clips` gives the video's frame 0, frame stride, frame size H x W and length Tv, and frame_idx [N][T] the source
+// frame of every output frame.  The workgroup reads its clip's row once (uniform), takes the clamped frame in place and
+// is the TAB kernel from there on with the clip's H, W where that reads d.H, d.W; d.H / d.W are the batch maxima the plan
+// sized the row stages from, and H, W are clamped into them.
+struct ResizeClips {
+    const ptx_clip_src* srcs;              // device, [N] (RGB)
+    const ptx_clip_src_yuv420* ysrcs;      // device, [N] (YUV)
+    const int* frame_idx;                  // device, [N][T]
+};
+
+template <int C, bool YUV = false, bool WIN = false, bool TAB = false, bool CLIPS = false>
 __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d, const unsigned char* __restrict__ f,
                                                                const int* __restrict__ row_lo, const int* __restrict__ row_n,
                                                                const int* __restrict__ row_k, const int* __restrict__ col_lo,
                                                                const int* __restrict__ col_n, const int* __restrict__ col_k,
                                                                void* __restrict__ y, ptx_norm_desc nd, ResizePlan pl,
-                                                               ptx_yuv420_src ys, ResizeWindows win) {
+                                                               ptx_yuv420_src ys, ResizeWindows win, ResizeClips clips) {
     extern __shared__ __attribute__((aligned(16))) unsigned char resize_smem[];
     int* hdr = reinterpret_cast<int*>(resize_smem);                 // [0] first, [1] one-past-last referenced column
     int* t_clo = hdr + 4;                                           // clamped table entries: columns [Wo], [Wo] ...
@@ -320,9 +331,29 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int WoC = d.Wo * C, istride = pl.istride;
     const int half = 1 << (kResizeBits - 1);
-    const unsigned char* fin = YUV ? nullptr : f + (size_t)frame * d.H * d.W * C;
-    const YuvFrame yf = YUV ? yuv_frame(ys, frame / d.T, frame % d.T) : YuvFrame{};
-    if constexpr (TAB) {
+    int H = d.H, W = d.W;                                           // the frame extents of this workgroup's source
+    const unsigned char* fin = YUV || CLIPS ? nullptr : f + (size_t)frame * d.H * d.W * C;
+    YuvFrame yf = YUV && !CLIPS ? yuv_frame(ys, frame / d.T, frame % d.T) : YuvFrame{};
+    if constexpr (CLIPS) {
+        int Tv;
+        int64_t stride_t = 0;
+        const unsigned char* base = nullptr;
+        if constexpr (YUV) {
+            const ptx_clip_src_yuv420 cs = clips.ysrcs[frame / d.T];
+            ys = cs.planes;
+            H = cs.H, W = cs.W, Tv = cs.Tv;
+        } else {
+            const ptx_clip_src cs = clips.srcs[frame / d.T];
+            base = cs.base, stride_t = cs.stride_t;
+            H = cs.H, W = cs.W, Tv = cs.Tv;
+        }
+        H = min(max(H, 1), d.H);                                    // a garbage row cannot outrun the row stages
+        W = min(max(W, 1), d.W);
+        const int t = min(max(clips.frame_idx[frame], 0), max(Tv, 1) - 1);
+        if constexpr (YUV) yf = yuv_frame(ys, 0, t);
+        else fin = base + (int64_t)t * stride_t;
+    }
+    if constexpr (TAB || CLIPS) {
         const size_t clip = (size_t)(frame / d.T);
         row_lo += clip * d.Ho;
         row_n += clip * d.Ho;
@@ -343,15 +374,15 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
     auto row_of = [&](int r) { return WIN ? top + (vflip ? d.Ho - 1 - r : r) : r; };        // table row of output row r
 
     if (tid == 0) {
-        hdr[0] = d.W;
+        hdr[0] = W;
         hdr[1] = 0;
     }
     __syncthreads();
     {
-        int cmin = d.W, cmax = 0;
+        int cmin = W, cmax = 0;
         for (int x = tid; x < d.Wo; x += 256) {
             int lo, n;
-            resize_entry(col_lo, col_n, col_of(x), d.W, d.taps_w, lo, n);
+            resize_entry(col_lo, col_n, col_of(x), W, d.taps_w, lo, n);
             t_clo[x] = lo;
             t_cn[x] = n;
             cmin = min(cmin, lo);
@@ -361,7 +392,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
         atomicMax(&hdr[1], cmax);
         for (int i = tid; i < y1 - y0; i += 256) {
             int lo, n;
-            resize_entry(row_lo, row_n, row_of(y0 + i), d.H, min(d.taps_h, pl.lds_rows), lo, n);
+            resize_entry(row_lo, row_n, row_of(y0 + i), H, min(d.taps_h, pl.lds_rows), lo, n);
             t_rlo[i] = lo;
             t_rn[i] = n;
         }
@@ -421,7 +452,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
         ResizeRow pre = {};
         YuvRow ypre = {};
         if constexpr (YUV) yuv_fetch_row(ypre, 0 + wave, nrows, ys, yf, lo0, cmin, px_end, lane);
-        else resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
+        else resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, W, cmin, C, span_bytes, lane);
         for (int i0 = 0; i0 < nrows; i0 += 4) {
             const int i = i0 + wave;
             int off = 0;
@@ -429,7 +460,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
                 if (i < nrows) off = yuv_stage_row(sw, ypre, ys, yf, lo0 + i, cmin, px_end, lane);
             } else if (i < nrows) {
                 int vb, ve, end;
-                const unsigned char* g = resize_row_span(fin, lo0 + i, d.W, cmin, C, span_bytes, off, vb, ve, end);
+                const unsigned char* g = resize_row_span(fin, lo0 + i, W, cmin, C, span_bytes, off, vb, ve, end);
                 if (lane < vb - off) sw[off + lane] = (unsigned char)pre.head;
                 if (vb + lane * 16 < ve) *reinterpret_cast<u32x4*>(sw + vb + lane * 16) = pre.v0;
                 if (vb + (64 + lane) * 16 < ve) *reinterpret_cast<u32x4*>(sw + vb + (64 + lane) * 16) = pre.v1;
@@ -440,7 +471,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
             }
             __syncthreads();
             if constexpr (YUV) yuv_fetch_row(ypre, i + 4, nrows, ys, yf, lo0, cmin, px_end, lane);
-            else resize_fetch_row(pre, i + 4, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
+            else resize_fetch_row(pre, i + 4, nrows, fin, lo0, W, cmin, C, span_bytes, lane);
             if (i < nrows) {
                 for (int x = lane; x < d.Wo; x += 64) {
                     const int lo = t_clo[x], n = t_cn[x];
@@ -559,18 +590,16 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
 // Garbage rows are safe: the box is clamped into the frame, the resized extent to >= 1, the window into the resized
 // frame, the table index into [0, extent), n to the pitch; the resize kernel clamps the entries once more.
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) resize_build_tables_kernel(ptx_resize_desc d, const ptx_resize_geom* __restrict__ geoms,
-                                                                  int* __restrict__ row_lo, int* __restrict__ row_n,
-                                                                  int* __restrict__ row_k, int* __restrict__ col_lo,
-                                                                  int* __restrict__ col_n, int* __restrict__ col_k) {
+// The entry of (clip, axis entry e) for frames of H x W: the body shared by resize_build_tables_kernel (H, W of the
+// descriptor) and resize_build_tables_clips_kernel (resize_clips.hip: H, W of the clip's source row).
+__device__ __forceinline__ void resize_build_entry(const ptx_resize_desc& d, int H, int W, int clip, int e,
+                                                   const ptx_resize_geom* __restrict__ geoms, int* __restrict__ row_lo,
+                                                   int* __restrict__ row_n, int* __restrict__ row_k, int* __restrict__ col_lo,
+                                                   int* __restrict__ col_n, int* __restrict__ col_k) {
 #pragma clang fp contract(off)
-    const int per_clip = d.Ho + d.Wo;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)d.N * per_clip) return;
-    const int clip = (int)(idx / per_clip), e = (int)(idx - (long long)clip * per_clip);
     const bool rows = e < d.Ho;
     const int o = rows ? e : e - d.Ho;                               // output index on this axis
-    const int S = rows ? d.Ho : d.Wo, extent = rows ? d.H : d.W, taps = rows ? d.taps_h : d.taps_w;
+    const int S = rows ? d.Ho : d.Wo, extent = rows ? H : W, taps = rows ? d.taps_h : d.taps_w;
     const ptx_resize_geom g = geoms[clip];
     const int origin = min(max(rows ? g.box_top : g.box_left, 0), extent - 1);
     const int n_in = min(max(rows ? g.box_h : g.box_w, 1), extent - origin);
@@ -614,6 +643,17 @@ __global__ void __launch_bounds__(256) resize_build_tables_kernel(ptx_resize_des
         }
         k[j] = c;
     }
+}
+
+__global__ void __launch_bounds__(256) resize_build_tables_kernel(ptx_resize_desc d, const ptx_resize_geom* __restrict__ geoms,
+                                                                  int* __restrict__ row_lo, int* __restrict__ row_n,
+                                                                  int* __restrict__ row_k, int* __restrict__ col_lo,
+                                                                  int* __restrict__ col_n, int* __restrict__ col_k) {
+    const int per_clip = d.Ho + d.Wo;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)d.N * per_clip) return;
+    const int clip = (int)(idx / per_clip), e = (int)(idx - (long long)clip * per_clip);
+    resize_build_entry(d, d.H, d.W, clip, e, geoms, row_lo, row_n, row_k, col_lo, col_n, col_k);
 }
 
 static unsigned grid_for(size_t work_items) {
@@ -993,6 +1033,17 @@ static int resize_windows_check(const ptx_resize_desc* d, int h, int w, const ch
     return PTX_OK;
 }
 
+// The normalisation of a launch that writes planes (left zeroed for uint8 output), checked.
+static int resize_norm(const ptx_resize_desc* desc, const ptx_norm_desc* norm, ptx_norm_desc* nd, const char* who) {
+    if (desc->out_mode == PTX_RESIZE_OUT_U8) return PTX_OK;
+    if (!norm) return fail(PTX_ERR_INVALID, "%s: null norm descriptor", who);
+    for (int c = 0; c < desc->C; ++c)
+        if (!(norm->std[c] != 0.f)) return fail(PTX_ERR_INVALID, "%s: std[%d] must be non-zero", who, c);
+    if (norm->swap_rb && desc->C < 3) return fail(PTX_ERR_INVALID, "%s: BGR swap needs 3 channels", who);
+    *nd = *norm;
+    return PTX_OK;
+}
+
 // Both sources: `frames` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.  All three
 // table modes: the fixed window (win == nullptr: the tables hold the window's entries), one window per clip (win->wins,
 // tables of win->h x win->w entries) or tables per clip (per_clip: every table has a leading [N]).
@@ -1008,13 +1059,7 @@ static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames,
     if ((!frames && !src) || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k || (win && !win->wins))
         return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     ptx_norm_desc nd = {};
-    if (desc->out_mode != PTX_RESIZE_OUT_U8) {
-        if (!norm) return fail(PTX_ERR_INVALID, "%s: null norm descriptor", who);
-        for (int c = 0; c < desc->C; ++c)
-            if (!(norm->std[c] != 0.f)) return fail(PTX_ERR_INVALID, "%s: std[%d] must be non-zero", who, c);
-        if (norm->swap_rb && desc->C < 3) return fail(PTX_ERR_INVALID, "%s: BGR swap needs 3 channels", who);
-        nd = *norm;
-    }
+    if ((s = resize_norm(desc, norm, &nd, who))) return s;
     const dim3 grid((unsigned)((int64_t)desc->N * desc->T * cdiv(desc->Ho, p.band)));
     hipStream_t st = (hipStream_t)stream;
     const ResizeWindows rw = win ? *win : ResizeWindows{};
@@ -1022,7 +1067,7 @@ static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames,
 #define PTX_RESIZE_LAUNCH(CH, YUV, WIN, TAB)                                                                          \
     hipLaunchKernelGGL((resize_frames_u8_kernel<CH, YUV, WIN, TAB>), grid, dim3(256), p.lds_bytes, st, *desc,           \
                        YUV ? none : frames, row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, YUV ? *src : ptx_yuv420_src{}, \
-                       rw)
+                       rw, ResizeClips{})
 #define PTX_RESIZE_LAUNCH_C(WIN, TAB)                          \
     switch (desc->C) {                                         \
         case 1: PTX_RESIZE_LAUNCH(1, false, WIN, TAB); break;  \
@@ -1251,6 +1296,9 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 // The multi-view resize kernel is a file of its own compiled as part of this translation unit (build.py follows the
 // include, so its bytes are in this object's stamp and in ptx_version()'s source hash).
 #include "resize_views.hip"
+
+// So are the entry points that sample training clips from videos of any size (a source row per clip).
+#include "resize_clips.hip"
 
 // So is the patch-resident bf16 stem (it normalises uint8 frames with resize_common.h's normalise_u8 while it stages them).
 #include "conv_stem_bf16.hip"

@@ -651,7 +651,9 @@ class Engine:
         is fused into the stem's fold kernel: no fp32 NCDHW clip is ever materialised.  `opts`: anything
         with mean / std / input_space / input_range (default: the model's own pretrained settings).
         `transform`: a `transforms.TransformFrames(.., out="frames")` applied to the frames first (resize + crop of
-        frames of any size on the device, utils.py:53-64); None: the frames already have the input size.
+        frames of any size on the device, utils.py:53-64), or a `transforms.SampleClips(.., out="frames")`, for which
+        `frames` is a batch of VIDEOS of any sizes and lengths (a list) that it samples clips from; None: the frames
+        already have the input size.
         `frames` may be a `transforms.YUV420` source (NV12 / I420 planes); it needs a transform, whose kernel converts
         the colours while it stages the rows."""
         from .transforms import YUV420, apply_frames_transform

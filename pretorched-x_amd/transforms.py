@@ -25,6 +25,11 @@ uint8 frames:
   views.  Frames are read in place through an index table and the crop windows of a sampled frame share one
   horizontal pass.  `model.forward_views` feeds the views to a model chunk by chunk and averages the predictions.
 
+* `SampleClips` is training-time sampling of a BATCH of decoded videos of any sizes and lengths: per output clip a
+  random (or the test-time) frame index row and a resize geometry row drawn as `TransformFrames.draw_geometry` draws it,
+  applied in place by one table-builder launch plus one resize launch whose workgroups each read their own clip's source
+  row.  No gathered or same-size copy of any video is made; every clip has the bits of `TransformFrames` on its frames.
+
 * `YUV420` describes decoder output (NV12 / I420 planes, any row pitch) and is accepted wherever RGB frames are:
   the two resize kernels convert to RGB while they stage an input row on chip (`yuv_coefficients` is the integer
   contract, `yuv420_to_rgb_numpy` its numpy statement), so the RGB frame never exists in HBM and every output bit
@@ -40,7 +45,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import NormDesc, PtxError, ResizeDesc, ViewsDesc, Yuv420Src, check
+from ._lib import ClipSrc, ClipSrcYuv420, NormDesc, PtxError, ResizeDesc, ViewsDesc, Yuv420Src, check
 
 PRECISION_BITS = 22       # PIL's fixed-point coefficient precision for 8-bit channels (32 - 8 - 2)
 
@@ -864,14 +869,15 @@ class TransformFrames:
 
 
 def apply_frames_transform(transform, frames, who="forward_frames"):
-    """The `transform=` hook of forward_frames: a TransformFrames with out="frames", applied to the raw frames.  A
-    `YUV420` source has no RGB frames to pass on, so it needs one (a crop-only transform serves frames of the input size)."""
+    """The `transform=` hook of forward_frames: a TransformFrames with out="frames", applied to the raw frames, or a
+    SampleClips with out="frames", applied to the raw videos (a list of any sizes and lengths).  A `YUV420` source has no
+    RGB frames to pass on, so it needs one (a crop-only transform serves frames of the input size)."""
     if transform is None:
         if isinstance(frames, YUV420):
             raise PtxError("%s: a YUV420 source needs transform=TransformFrames(.., out='frames') (the colour conversion "
                            "runs in its row staging; a crop-only transform serves frames that have the input size)" % who)
         return frames
-    if not isinstance(transform, TransformFrames) or transform.out != "frames":
+    if not isinstance(transform, (TransformFrames, SampleClips)) or transform.out != "frames":
         raise PtxError("%s: transform must be a pretorched.transforms.TransformFrames with out='frames', got %r" % (
             who, transform))
     return transform(frames)
@@ -1129,3 +1135,261 @@ class SampleViews:
                   "ptx_resize_views_yuv420")
             del keep
         return y if src.lead == 3 else y[0]
+
+
+# ---------------------------------------------------------------------------------------------
+# training clips from a batch of videos of any sizes and lengths: a source row, an index row and a geometry row per clip
+# ---------------------------------------------------------------------------------------------
+_CLIP_SRC = np.dtype([("base", "<u8"), ("stride_t", "<i8"), ("H", "<i4"), ("W", "<i4"), ("Tv", "<i4"), ("reserved", "<i4")])
+
+
+class SampleClips:
+    """Training clips from decoded videos of ANY sizes and lengths in one resize launch: `clips` clips of `num_frames`
+    frames per video, every clip resized + cropped (+ flipped) exactly as `TransformFrames` with the same spatial switches
+    does on the clip's gathered frames (bit-identical), read in place through a frame index row per clip.
+
+    opts, scale, preserve_aspect_ratio, crop, hflip, vflip, random_crop, random_hflip, random_vflip, random_short_side,
+    random_resized_crop, out, dtype, generator: exactly TransformFrames' (same meaning, same checks; the transform is kept
+    as `spatial`).  num_frames / frame_stride / clips / sampling: as for SampleViews.  random_start=True draws the
+    temporal position per clip (see `draw`); False takes SampleViews' deterministic rows (`clip_frame_indices`).
+
+    A call draws one index row and one geometry row per output clip (kept as `last_indices`, CPU int64 [N*clips, T], and
+    `last_geometry`, CPU int32 [N*clips, 10]); `sc(videos, indices=.., geometry=..)` applies given rows instead, on any
+    SampleClips.  Output clip j comes from video j // clips."""
+
+    def __init__(self, opts, num_frames=16, frame_stride=4, clips=1, sampling="dense", random_start=True, scale=0.875,
+                 preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False, random_crop=False, random_hflip=False,
+                 random_vflip=False, random_short_side=None, random_resized_crop=False, out="tensor", dtype=torch.float32,
+                 generator=None):
+        for name, v in (("num_frames", num_frames), ("frame_stride", frame_stride), ("clips", clips)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+                raise PtxError("SampleClips: %s must be a positive integer, got %r" % (name, v))
+        if sampling not in ("dense", "segments"):
+            raise PtxError("SampleClips: sampling must be 'dense' or 'segments', got %r" % (sampling,))
+        self.spatial = TransformFrames(opts, scale, preserve_aspect_ratio, crop, hflip, out, dtype, random_crop=random_crop,
+                                       random_hflip=random_hflip, random_vflip=random_vflip, vflip=vflip, generator=generator,
+                                       random_short_side=random_short_side, random_resized_crop=random_resized_crop)
+        self.num_frames, self.frame_stride, self.clips, self.sampling = num_frames, frame_stride, clips, sampling
+        self.random_start, self.generator = bool(random_start), generator
+        self.out, self.dtype, self.size, self.norm = out, dtype, self.spatial.size, self.spatial.norm
+        self.last_indices, self.last_geometry = None, None
+
+    # ---- host only: no device is touched -------------------------------------------------------
+    @staticmethod
+    def _shapes(shapes):
+        try:
+            out = [tuple(int(v) for v in s) for s in shapes]
+        except (TypeError, ValueError):
+            out = None
+        if not out or any(len(s) != 3 for s in out):
+            raise PtxError("SampleClips: shapes must be a non-empty list of (Tv, H, W), got %r" % (shapes,))
+        for i, s in enumerate(out):
+            if min(s) < 1:
+                raise PtxError("SampleClips: videos[%d] is empty (Tv, H, W = %d, %d, %d)" % ((i,) + s))
+        return out
+
+    def draw_indices(self, Tv):
+        """One clip's frame index row (a list of T ints in [0, Tv)) from `generator`.
+        dense: span = (T - 1) * frame_stride + 1; Tv >= span draws start = randint(0, Tv - span + 1) (one draw), a shorter
+        video starts at 0 and consumes nothing; frame i is min(start + i * frame_stride, Tv - 1).
+        segments (TSN training): lo_i = (i * Tv) // T, hi_i = max(((i + 1) * Tv) // T, lo_i + 1); one call
+        r = randint(0, 2**30, (T,)); frame i is lo_i + r_i % (hi_i - lo_i)."""
+        T, g, Tv = self.num_frames, self.generator, int(Tv)
+        if self.sampling == "dense":
+            span = (T - 1) * self.frame_stride + 1
+            start = int(torch.randint(0, Tv - span + 1, (1,), generator=g)) if Tv >= span else 0
+            return [min(start + i * self.frame_stride, Tv - 1) for i in range(T)]
+        r = torch.randint(0, 2 ** 30, (T,), generator=g).tolist()
+        out = []
+        for i in range(T):
+            lo = (i * Tv) // T
+            hi = max(((i + 1) * Tv) // T, lo + 1)
+            out.append(lo + r[i] % (hi - lo))
+        return out
+
+    def draw(self, shapes):
+        """(indices, geometry) for videos of `shapes` = [(Tv, H, W), ...]: CPU int64 [N*clips, T] and CPU int32 [N*clips, 10].
+        Video by video, clip by clip: first the temporal draw (`draw_indices`; with random_start=False nothing is drawn and
+        clip c takes row c of `clip_frame_indices(Tv, T, frame_stride, clips, sampling)`), then the spatial one, which is
+        `spatial.draw_geometry(1, H, W)` -- a fixed transform draws nothing and gives every clip of a video the same row."""
+        shapes = self._shapes(shapes)
+        K, T = self.clips, self.num_frames
+        idx = torch.empty((len(shapes) * K, T), dtype=torch.int64)
+        geo = torch.empty((len(shapes) * K, 10), dtype=torch.int32)
+        for i, (Tv, H, W) in enumerate(shapes):
+            fixed = None if self.random_start else clip_frame_indices(Tv, T, self.frame_stride, K, self.sampling)
+            for c in range(K):
+                j = i * K + c
+                idx[j] = torch.tensor(self.draw_indices(Tv) if fixed is None else fixed[c], dtype=torch.int64)
+                try:
+                    geo[j] = self.spatial.draw_geometry(1, H, W)[0]
+                except PtxError as e:
+                    raise PtxError("SampleClips: clip %d (videos[%d], %dx%d): %s" % (j, i, H, W, e))
+        return idx, geo
+
+    def _checked(self, indices, geometry, shapes):
+        shapes = self._shapes(shapes)
+        K, T = self.clips, self.num_frames
+        NC = len(shapes) * K
+        arrs = []
+        for name, a, cols in (("indices", indices, T), ("geometry", geometry, 10)):
+            if isinstance(a, torch.Tensor):
+                if a.is_cuda:
+                    raise PtxError("SampleClips: %s must be an integer array or a CPU tensor [N*clips, %d], got a CUDA tensor" % (
+                        name, cols))
+                a = a.numpy()
+            a = np.asarray(a)
+            if a.dtype.kind not in "iu":
+                raise PtxError("SampleClips: %s must hold integers, got dtype %s" % (name, a.dtype))
+            if a.ndim != 2 or a.shape[1] != cols:
+                raise PtxError("SampleClips: %s must be [N*clips, %d], got shape %s" % (name, cols, a.shape))
+            if a.shape[0] != NC:
+                raise PtxError("SampleClips: %s holds %d clips, %d videos x %d clips need %d" % (name, a.shape[0], len(shapes), K, NC))
+            arrs.append(a.astype(np.int64))
+        idx, geo = arrs
+        taps_h = taps_w = 1
+        rows = []
+        for i, (Tv, H, W) in enumerate(shapes):
+            mine = idx[i * K:(i + 1) * K]
+            bad = np.argwhere((mine < 0) | (mine >= Tv))
+            if len(bad):
+                c, t = (int(v) for v in bad[0])
+                raise PtxError("SampleClips: clip %d (videos[%d]): frame index %d (position %d) is outside [0, %d)" % (
+                    i * K + c, i, mine[c, t], t, Tv))
+            try:
+                g, th, tw = self.spatial._checked_geometry(geo[i * K:(i + 1) * K], K, H, W)
+            except PtxError:
+                for c in range(K):                                   # name the clip: its row alone fails the same way
+                    try:
+                        self.spatial._checked_geometry(geo[i * K + c:i * K + c + 1], 1, H, W)
+                    except PtxError as e:
+                        raise PtxError("SampleClips: clip %d (videos[%d], %dx%d): %s" % (i * K + c, i, H, W, e))
+                raise
+            rows.append(g)
+            taps_h, taps_w = max(taps_h, th), max(taps_w, tw)
+        return torch.from_numpy(idx), torch.cat(rows), taps_h, taps_w
+
+    def check(self, indices, geometry, shapes):
+        """`indices` ([N*clips, T]) and `geometry` ([N*clips, 10]) -- integer arrays or CPU tensors -- for videos of `shapes`
+        as (CPU int64, CPU int32) tensors, or PtxError naming the clip: a wrong row count, an index outside [0, Tv_i), a row
+        that `check_geometry` refuses for video i's own H x W."""
+        return self._checked(indices, geometry, shapes)[:2]
+
+    # ---- the call ------------------------------------------------------------------------------
+    @staticmethod
+    def _videos(videos):
+        """The batch as a list of per-video sources (uint8 tensors [Tv,H,W,3] or YUV420 with planes [Tv,H,W]), checked on
+        the host."""
+        if isinstance(videos, YUV420):
+            if videos.lead == 3:
+                return [YUV420(videos.y[n], videos.u[n], None if videos.v is None else videos.v[n], videos.matrix,
+                               videos.color_range) for n in range(videos.N)]
+            if videos.lead != 2:
+                raise PtxError("SampleClips: expected a YUV420 source with planes [N,Tv,H,W] or [Tv,H,W], got %d leading "
+                               "dimension(s)" % (videos.lead - 1))
+            return [videos]
+        if isinstance(videos, torch.Tensor):
+            if videos.dim() not in (4, 5):
+                raise PtxError("SampleClips: expected [N,Tv,H,W,3], [Tv,H,W,3] or a list of videos, got shape %s" % (
+                    tuple(videos.shape),))
+            videos = list(videos) if videos.dim() == 5 else [videos]
+        elif isinstance(videos, (list, tuple)):
+            videos = list(videos)
+        else:
+            raise PtxError("SampleClips: videos must be a list of uint8 CUDA tensors [Tv,H,W,3] or YUV420 sources, one tensor "
+                           "or one YUV420, got %s" % type(videos).__name__)
+        if not videos:
+            raise PtxError("SampleClips: empty batch (no videos)")
+        yuv = isinstance(videos[0], YUV420)
+        for i, v in enumerate(videos):
+            if yuv != isinstance(v, YUV420):
+                raise PtxError("SampleClips: videos[%d]: a batch is all tensors or all YUV420 sources" % i)
+            if yuv:
+                if v.lead != 2:
+                    raise PtxError("SampleClips: videos[%d]: expected a YUV420 source with planes [Tv,H,W], got %d leading "
+                                   "dimension(s)" % (i, v.lead - 1))
+                continue
+            if not isinstance(v, torch.Tensor):
+                raise PtxError("SampleClips: videos[%d] must be a uint8 CUDA tensor [Tv,H,W,3], got %s" % (i, type(v).__name__))
+            if v.dtype != torch.uint8:
+                raise PtxError("SampleClips: videos[%d] must be a uint8 tensor, got %s" % (i, v.dtype))
+            if v.dim() != 4 or v.shape[-1] != 3:
+                raise PtxError("SampleClips: videos[%d]: expected [Tv,H,W,3], got shape %s" % (i, tuple(v.shape)))
+        devs = [v.device for v in videos]
+        if len(set(devs)) != 1:
+            i = next(i for i, d in enumerate(devs) if d != devs[0])
+            raise PtxError("SampleClips: videos[%d] is on %s, videos[0] on %s: a batch lives on one device" % (i, devs[i], devs[0]))
+        return videos
+
+    def __call__(self, videos, indices=None, geometry=None):
+        """videos: a list / tuple of uint8 CUDA tensors [Tv_i,H_i,W_i,3] of any sizes and lengths on one device | one
+        [N,Tv,H,W,3] tensor (N videos) | one [Tv,H,W,3] tensor | a list of `YUV420` sources with planes [Tv,H,W] | one
+        `YUV420` with planes [N,Tv,H,W] or [Tv,H,W]  ->  out="tensor": [N*clips,3,T,S,S] (fp32 or bf16); out="frames": uint8
+        [N*clips,T,S,S,3].  A video is read in place when its frames are contiguous [H,W,3] blocks (slices and steps over
+        Tv included); any other video costs one `.contiguous()` copy of that video only.  One call is one upload (source,
+        index and geometry rows in one buffer), one table-builder launch and one resize launch, whatever the batch holds;
+        the tap pitches are the maxima over the batch."""
+        if (indices is None) != (geometry is None):
+            raise PtxError("SampleClips: indices= and geometry= are given together (a replay) or not at all (a draw)")
+        vids = self._videos(videos)
+        yuv = isinstance(vids[0], YUV420)
+        shapes = [(v.T, v.H, v.W) if yuv else tuple(int(n) for n in v.shape[:3]) for v in vids]
+        if indices is None:                                          # validated before a device is touched
+            drawn = self.draw(shapes)
+            idx, geo, taps_h, taps_w = self._checked(drawn[0], drawn[1], shapes)
+        else:
+            idx, geo, taps_h, taps_w = self._checked(indices, geometry, shapes)
+        device = vids[0].device
+        if device.type != "cuda":
+            raise PtxError("SampleClips: videos must be uint8 CUDA tensors (no CPU fallback)")
+        K, T, S = self.clips, self.num_frames, self.size
+        NC = len(vids) * K
+        keep = []
+        src = np.zeros(len(vids), _CLIP_SRC)
+        ysrc = (ClipSrcYuv420 * len(vids))() if yuv else None
+        for i, (v, (Tv, H, W)) in enumerate(zip(vids, shapes)):
+            src[i]["H"], src[i]["W"], src[i]["Tv"] = H, W, Tv
+            if yuv:
+                ysrc[i].planes, planes = v.source("SampleClips")
+                ysrc[i].H, ysrc[i].W, ysrc[i].Tv = H, W, Tv
+                keep.append(planes)
+                continue
+            frame = H * W * 3
+            if tuple(v.stride()[1:]) != (W * 3, 3, 1) or (Tv > 1 and v.stride(0) < frame):
+                v = v.contiguous()                                   # frames that are not [H,W,3] blocks: one copy of this video
+            keep.append(v)
+            src[i]["base"], src[i]["stride_t"] = v.data_ptr(), (v.stride(0) if Tv > 1 else frame)
+        parts = [np.repeat(src, K).view(np.uint8)]
+        if yuv:
+            parts.append(np.repeat(np.frombuffer(ysrc, dtype=np.uint8).reshape(len(vids), -1), K, axis=0).reshape(-1))
+        parts += [idx.numpy().astype(np.int32).reshape(-1).view(np.uint8), geo.numpy().astype(np.int32).reshape(-1).view(np.uint8)]
+        offs, total = [], 0
+        for p in parts:                                              # every part starts on a 16-byte boundary
+            offs.append(total)
+            total += (p.size + 15) & ~15
+        host = np.zeros(total, np.uint8)
+        for o, p in zip(offs, parts):
+            host[o:o + p.size] = p
+        Hm, Wm = max(s[1] for s in shapes), max(s[2] for s in shapes)
+        with torch.cuda.device(device):
+            rows = torch.from_numpy(host).to(device)                 # the one upload of the call
+            at = [C.c_void_p(rows.data_ptr() + o) for o in offs]
+            sizes = [NC * S, NC * S, NC * S * taps_h, NC * S, NC * S, NC * S * taps_w]
+            buf = torch.empty(sum(sizes), device=device, dtype=torch.int32)
+            tabs = [C.c_void_p(buf.data_ptr() + int(o) * 4) for o in np.cumsum([0] + sizes[:-1])]
+            if self.out == "frames":
+                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((NC, T, S, S, 3), device=device, dtype=torch.uint8)
+            else:
+                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+                y = torch.empty((NC, 3, T, S, S), device=device, dtype=self.dtype)
+            desc = ResizeDesc(NC, T, Hm, Wm, 3, S, S, taps_h, taps_w, mode)
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            check(_lib.lib().ptx_resize_build_tables_clips(C.byref(desc), at[0], at[-1], *tabs, stream),
+                  "ptx_resize_build_tables_clips")
+            name = "ptx_resize_clips_yuv420" if yuv else "ptx_resize_clips_u8"
+            check(getattr(_lib.lib(), name)(C.byref(desc), at[1] if yuv else at[0], at[-2], *tabs, C.c_void_p(y.data_ptr()),
+                                            C.byref(self.norm), stream), name)
+            del keep                                                 # videos (copies included) stayed alive up to the launch
+        if indices is None:
+            self.last_indices, self.last_geometry = idx, geo
+        return y
