@@ -350,6 +350,7 @@ int ptx_pack_wino_f32_weight(const ptx_conv3d_desc* desc, const float* w_packed,
 int ptx_wino_in_f32(const ptx_conv3d_desc* desc, const float* x, float* V, ptx_stream_t stream);
 int ptx_wino_out_f32(const ptx_conv3d_desc* desc, const float* M, const float* bias, const float* res, float* y,
                      ptx_stream_t stream);
+/* The Winograd F(4x4,3x3) form of the same convolution has seven calls of its own, declared in ptx_amd_wino4.h. */
 
 /* Operands of the fused generator-stage epilogue (see PTX_EPI_AFFINE / PTX_EPI_DUAL_RAW). */
 typedef struct ptx_conv_fused_ext {

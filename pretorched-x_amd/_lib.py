@@ -11,6 +11,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libptx_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd.h")
+WINO4_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_wino4.h")      # the F(4x4) Winograd calls
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -311,6 +312,19 @@ SIGNATURES = {
 }
 
 
+# include/ptx_amd_wino4.h: the Winograd F(4x4,3x3) entry points, bound next to SIGNATURES (tests/test_wino4_host.py keeps the
+# header, this table and the library's exports in step)
+SIGNATURES_WINO4 = {
+    "ptx_conv_wino4_f32_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "ptx_conv_wino4_f32_workspace_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "ptx_conv_wino4_f32_gemm_desc": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
+    "ptx_wino4_f32_weight_elems": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "ptx_pack_wino4_f32_weight": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P]),
+    "ptx_wino4_in_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P]),
+    "ptx_wino4_out_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -344,7 +358,7 @@ def lib():
                 "`python pretorched-x_amd/csrc/build.py` (or __graft_entry__.build()); "
                 "this package has no CPU / eager fallback" % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

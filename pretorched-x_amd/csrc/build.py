@@ -23,7 +23,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 SOURCES = ["conv_igemm.hip", "conv_chain.hip", "conv_program.hip", "pack_layout.hip", "pool_head.hip", "nonlocal_attn.hip",
            "conv_stem_x3.hip", "conv_stem_f32.hip", "conv_body_f32.hip", "gen_stage_f16.hip"]
-HEADERS = ["ptx_common.h", "conv_igemm_kernel.h", "resize_common.h", os.path.join("..", "..", "include", "ptx_amd.h")]
+HEADERS = ["ptx_common.h", "conv_igemm_kernel.h", "resize_common.h", os.path.join("..", "..", "include", "ptx_amd.h"),
+           os.path.join("..", "..", "include", "ptx_amd_wino4.h")]
 LIB = os.path.join(PKG, "libptx_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
@@ -35,12 +36,12 @@ VERSION_SOURCE = "pack_layout.hip"       # defines ptx_version(): compiled with 
 
 
 def source_hash():
-    """sha256 over every source the library is compiled from (csrc/*.hip, csrc/*.h, include/ptx_amd.h; sorted by file
+    """sha256 over every source the library is compiled from (csrc/*.hip, csrc/*.h, include/ptx_amd*.h; sorted by file
     name, each as name + NUL + bytes).  Compiled into ptx_version() so a test run can prove WHICH source the loaded
     binary was built from (the .so travels prebuilt to the GPU box; VERDICT r3 #10)."""
     h = hashlib.sha256()
     files = sorted(f for f in os.listdir(HERE) if f.endswith((".hip", ".h")))
-    for path in [os.path.join(HERE, f) for f in files] + [os.path.join(HERE, "..", "..", "include", "ptx_amd.h")]:
+    for path in [os.path.join(HERE, f) for f in files] + [os.path.join(HERE, "..", "..", "include", h) for h in ("ptx_amd.h", "ptx_amd_wino4.h")]:
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:
             h.update(f.read())

@@ -21,11 +21,11 @@ from ._lib import (ConvDesc, ConvFusedExt, ConvProgramInfo, ConvStage, NonlocalD
                    PTX_F16_OPERANDS, PTX_F16X3_OPERANDS, PTX_NL_BF16, PTX_NL_F16, PTX_NL_OUT_F16, PTX_NL_RELU, PTX_NL_SCALE,
                    PTX_NL_SOFTMAX, PTX_NL_X3, PTX_POOL_BF16, PTX_POOL_PAD_ZERO, PTX_POOL_SAME, PTX_PRO_UP2, PTX_RES_F16,
                    PTX_SPLITK_FUSED, PTX_STEM_SRC_BF16_NCDHW, PTX_STEM_SRC_U8_NTHWC, PtxError, check)
-from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step, WinoStep,
+from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step, Wino4Step, WinoStep, _WinoExec,
                     StemStep, _ConcatRowsPack, _Ref, _device_ctx, _geom, _ptr, _r4, _r8, _r128, _same_geometry, _stem_ld, _stream,
                     _t3, _tag)
 from .tuned import (BODY_FILTERS, BODY_SHAPES, _flags_kind, alt_lookup, body_lookup, chain_key, chain_lookup, prog_lookup,
-                    tuned_lookup, wino_lookup)
+                    tuned_lookup, wino4_lookup, wino_lookup)
 
 # bf16 inference (a model whose floating-point parameters are torch.bfloat16): the families whose plans run end to end on the
 # bf16 kernels.  Everything else raises at plan build time.
@@ -95,7 +95,8 @@ class Plan:
         self._cur = model                # the model (or DataParallel replica) whose tensors are valid right now
         self.program_steps = []  # ProgramStep: runs of small-M convs as one persistent launch
         self.wino_steps = []     # WinoStep: direct launch | Winograd transforms around a grouped conv, chosen by measurement
-        self.wino_bytes, self.wino_arena = 0, None       # V / M arena of the Winograd steps (the largest step's need)
+        self.wino4_steps = []    # every step with a Winograd F(4x4) form: those of wino_steps, then the F(4x4)-only Wino4Steps
+        self.wino_bytes, self.wino_arena = 0, None       # V / M arena of the Winograd steps (the largest need of either form)
         self.stem_bf16_step = None       # the bf16 stem's ConvStep (the tuner bounds its issued work)
         self.bf16_stem = getattr(engine, "bf16_stem", "fold")            # "fold" | "direct" (ptx_conv_stem_bf16_fwd)
         self.stem_steps = self.patch_steps = self.attn_steps = 0         # launches outside conv_steps, by kind
@@ -358,61 +359,120 @@ class Plan:
         st.body = self._body_choice(json.dumps(d.key()), st.body_ok)
 
     def _wino(self, st, pk, x2):
-        """Winograd F(2x2,3x3) (csrc/conv_wino_f32.hip): a further execution of a stride-1 (kT,3,3) fp32 conv as three launches
-        -- input transform, a 16-group (kT,1,1) conv on the ordinary tiles, output transform -- chosen per problem by the
-        tuner ("wino:" keys; default direct).  Returns the WinoStep that stands for `st` in the plan, or None when the conv is
-        not eligible (ptx_conv_wino_f32_supported) or PTX_CONV_WINO=0.  The grouped conv is NOT one of `conv_steps`: the tuner
-        sweeps its tile in the Winograd phase, only where a verdict is being measured."""
+        """Winograd F(2x2,3x3) and F(4x4,3x3) (csrc/conv_wino_f32.hip): further executions of a stride-1 (kT,3,3) fp32 conv as
+        three launches each -- input transform, a 16- / 36-group (kT,1,1) conv on the ordinary tiles, output transform -- chosen
+        per problem by the tuner ("wino:" / "wino4:" keys; default direct).  Returns the WinoStep (Wino4Step where only F(4x4)
+        takes the frame: odd H or W) that stands for `st` in the plan, or None when the conv is not eligible or
+        PTX_CONV_WINO=0.  The grouped convs are NOT among `conv_steps`: the tuner sweeps their tiles in the Winograd phase, only
+        where a verdict is being measured."""
         mode = os.environ.get("PTX_CONV_WINO", "auto")
         d, lib_ = st.d, self.lib
         if (mode == "0" or st.fused or x2 is not None or not isinstance(pk, Packed) or pk.f16 or pk.x3 or pk.fold_kw or pk.groups > 1
-                or (d.kH, d.kW) != (3, 3) or not lib_.ptx_conv_wino_f32_supported(C.byref(d))):
+                or (d.kH, d.kW) != (3, 3)):
             return None
-        gd = ConvDesc()
-        check(lib_.ptx_conv_wino_f32_gemm_desc(C.byref(d), C.byref(gd)), "ptx_conv_wino_f32_gemm_desc")
-        u = torch.empty(int(lib_.ptx_wino_f32_weight_elems(C.byref(d))), device=self.dev, dtype=torch.float32)
-        self.keepalive.append(u)
-        wsrc, wdst = _ptr(pk.w), _ptr(u)
+        ok2, ok4 = bool(lib_.ptx_conv_wino_f32_supported(C.byref(d))), bool(lib_.ptx_conv_wino4_f32_supported(C.byref(d)))
+        if not (ok2 or ok4):
+            return None
+        w = WinoStep() if ok2 else Wino4Step()
+        w.direct, w.label, w.key = [st], st.label, json.dumps(d.key())
+        if ok2:
+            self._wino_form(w, st, pk, 2)
+            self.wino_steps.append(w)
+        if ok4:
+            self._wino_form(w, st, pk, 4)
+            self.wino4_steps.append(w)
+        self._wino_choice(w)
+        return w
 
-        def repack_wino(d=d, lib_=lib_, wsrc=wsrc, wdst=wdst):
-            check(lib_.ptx_pack_wino_f32_weight(C.byref(d), wsrc, wdst, _stream()), "ptx_pack_wino_f32_weight")
-        if torch.device(self.dev).type != "meta":
-            self.refreshers.append(repack_wino)
+    def _wino_form(self, w, st, pk, m):
+        """Compile the F(m x m) execution of `st` into `w`: the grouped ConvStep and the two transform launches."""
+        d, lib_, tag = st.d, self.lib, "wino" if m == 2 else "wino4"
+        fn = {n: getattr(lib_, n % tag) for n in ("ptx_conv_%s_f32_gemm_desc", "ptx_%s_f32_weight_elems", "ptx_pack_%s_f32_weight",
+                                                  "ptx_conv_%s_f32_workspace_bytes", "ptx_%s_in_f32", "ptx_%s_out_f32")}
+        gd = ConvDesc()
+        check(fn["ptx_conv_%s_f32_gemm_desc"](C.byref(d), C.byref(gd)), "ptx_conv_%s_f32_gemm_desc" % tag)
         g = ConvStep()
-        g.d, g.w, g.b, g.res, g.plan, g.label, g.macs = gd, wdst, C.c_void_p(0), C.c_void_p(0), self, st.label + ".wino_gemm", st.macs
+        g.d, g.b, g.res, g.plan, g.label, g.macs = gd, C.c_void_p(0), C.c_void_p(0), self, "%s.%s_gemm" % (st.label, tag), st.macs
         tuned = tuned_lookup(json.dumps(gd.key()), "")
         if tuned is not None and lib_.ptx_conv3d_config_supported(C.byref(gd), tuned[0]):
             g.cfg, g.from_table = tuned[0], True
         else:
             g.cfg = lib_.ptx_conv3d_pick_config(C.byref(gd), None)
-        w = WinoStep()
-        w.gemm, w.direct, w.label, w.key = g, [st], st.label, json.dumps(d.key())
-        w.arena_bytes = int(lib_.ptx_conv_wino_f32_workspace_bytes(C.byref(d)))
-        w.v_bytes = w.arena_bytes - 4 * gd.N * gd.To * gd.Ho * gd.Wo * gd.ldy
-        self.wino_bytes = max(self.wino_bytes, w.arena_bytes)
+        arena = int(fn["ptx_conv_%s_f32_workspace_bytes"](C.byref(d)))
+        v_bytes = arena - 4 * gd.N * gd.To * gd.Ho * gd.Wo * gd.ldy
+        w.arena_bytes = max(w.arena_bytes or 0, arena)
+        self.wino_bytes = max(self.wino_bytes, arena)
         xp, bp, rp, yp, label = st.x, st.b, st.res, st.y, st.label
+        t_in, t_out, mslot = fn["ptx_%s_in_f32"], fn["ptx_%s_out_f32"], "m_ptr" if m == 2 else "m4_ptr"
 
-        def wino_in(stream, w=w, d=d, lib_=lib_, xp=xp, label=label):
-            check(lib_.ptx_wino_in_f32(C.byref(d), xp, w.v_ptr, stream), label + ".wino_in")
+        def wino_in(stream, w=w, d=d, xp=xp, label=label):
+            check(t_in(C.byref(d), xp, w.v_ptr, stream), "%s.%s_in" % (label, tag))
 
-        def wino_out(stream, w=w, d=d, lib_=lib_, bp=bp, rp=rp, yp=yp, label=label):
-            check(lib_.ptx_wino_out_f32(C.byref(d), w.m_ptr, bp, rp, yp, stream), label + ".wino_out")
+        def wino_out(stream, w=w, d=d, bp=bp, rp=rp, yp=yp, label=label):
+            check(t_out(C.byref(d), getattr(w, mslot), bp, rp, yp, stream), "%s.%s_out" % (label, tag))
         pos, tiles = d.N * d.Ti * d.Hi * d.Wi, gd.N * gd.To * gd.Ho * gd.Wo
-        w.wino = [_tag(wino_in, "wino_in", 4 * (pos * d.Ci + tiles * gd.ldx)), g,
-                  _tag(wino_out, "wino_out", 4 * (tiles * gd.ldy + pos * d.Co * (2 if d.flags & PTX_EPI_RES_ADD else 1)))]
-        w.use_wino = mode == "1" or bool(wino_lookup(w.key))
-        self.wino_steps.append(w)
-        return w
+        form = [_tag(wino_in, tag + "_in", 4 * (pos * d.Ci + tiles * gd.ldx)), g,
+                _tag(wino_out, tag + "_out", 4 * (tiles * gd.ldy + pos * d.Co * (2 if d.flags & PTX_EPI_RES_ADD else 1)))]
+        wsrc, n_u = _ptr(pk.w), int(fn["ptx_%s_f32_weight_elems"](C.byref(d)))
+        pack = fn["ptx_pack_%s_f32_weight"]
+
+        def weights(now=False):
+            """Allocate the transformed filter, point the grouped conv at it and register its repack (`now`: the packed
+            filters are already in place -- transform this one right away)."""
+            u = torch.empty(n_u, device=self.dev, dtype=torch.float32)
+            self.keepalive.append(u)
+            g.w = wdst = _ptr(u)
+
+            def repack_wino(d=d, wsrc=wsrc, wdst=wdst):
+                check(pack(C.byref(d), wsrc, wdst, _stream()), "ptx_pack_%s_f32_weight" % tag)
+            if torch.device(self.dev).type != "meta":
+                self.refreshers.append(repack_wino)
+                if now:
+                    repack_wino()
+        if m == 2:
+            w.wino, w.gemm, w.v_bytes = form, g, v_bytes
+            weights()
+        else:           # U4 of a 256-channel conv is 28 MB: only where the step can run (wino4_weights)
+            w.wino4, w.gemm4, w.v4_bytes, w.need_u4 = form, g, v_bytes, weights
+
+    def wino4_weights(self, w, now=False):
+        """Make the F(4x4) execution of `w` runnable: allocate and pack U4 once (a stored verdict, the forced mode, or the tuner
+        about to time it)."""
+        if w.need_u4 is not None:
+            need, w.need_u4 = w.need_u4, None
+            need(now)
+
+    def _wino_choice(self, w):
+        """The execution of a Winograd-capable step at compile time: PTX_CONV_WINO=1 / =4 force F(2x2) / F(4x4) wherever that
+        form exists (a conv without the forced form keeps its `auto` behaviour), else the tuned table's verdicts -- "wino4:"
+        first, a missing one means not F(4x4)."""
+        mode = os.environ.get("PTX_CONV_WINO", "auto")
+        has2, has4 = w.wino is not None, w.wino4 is not None
+        if mode == "1" and has2:
+            w.use_wino, w.use_wino4 = True, False
+        elif mode == "4" and has4:
+            w.use_wino, w.use_wino4 = False, True
+        else:
+            w.use_wino4 = has4 and bool(wino4_lookup(w.key))
+            w.use_wino = has2 and not w.use_wino4 and bool(wino_lookup(w.key))
 
     def _bind_wino_arena(self):
-        """One arena for V and M of every Winograd step, sized for the largest: a step's two buffers are live only between
-        its own three launches."""
+        """One arena for V and M of every Winograd step, sized for the largest need of either form: a step's two buffers are
+        live only between its own three launches.  Also the point where the selected F(4x4) steps get their filters."""
         if not self.wino_bytes:
             return
+        for w in self.wino4_steps:       # the choice is final here (a pair re-keys its first conv): U4 only where F(4x4) runs
+            if w.use_wino4:
+                self.wino4_weights(w)
         self.wino_arena = torch.empty(self.wino_bytes // 4, device=self.dev, dtype=torch.float32)
-        for w in self.wino_steps:
-            w.v_ptr, w.m_ptr = _ptr(self.wino_arena), _ptr(self.wino_arena, w.v_bytes // 4)
-            w.gemm.x, w.gemm.y = w.v_ptr, w.m_ptr
+        for w in set(self.wino_steps + self.wino4_steps):
+            w.v_ptr = _ptr(self.wino_arena)
+            if w.gemm is not None:
+                w.m_ptr = _ptr(self.wino_arena, w.v_bytes // 4)
+                w.gemm.x, w.gemm.y = w.v_ptr, w.m_ptr
+            if w.gemm4 is not None:
+                w.m4_ptr = _ptr(self.wino_arena, w.v4_bytes // 4)
+                w.gemm4.x, w.gemm4.y = w.v_ptr, w.m4_ptr
 
     def _pick_tile(self, st, out_bytes):
         """Tile configuration and split-K of a ConvStep: the tuned table's entry when this build can run it, else the library's
@@ -523,18 +583,18 @@ class Plan:
         known = alt_lookup(chain.key)
         a.use_chain = known if known is not None else (_r4(chain.d.Co) <= int(os.environ.get("PTX_CHAIN_DEFAULT_MAX_N1", "64")))
         for w in pair:
-            if isinstance(w, WinoStep):      # the pair's first conv also has a Winograd form: its verdict is the pair's
+            if isinstance(w, _WinoExec):     # the pair's first conv also has a Winograd form: its verdict is the pair's
                 w.alt, w.key = a, chain.key
-                w.use_wino = os.environ.get("PTX_CONV_WINO", "auto") == "1" or bool(wino_lookup(w.key))
-                if w.use_wino:
+                self._wino_choice(w)
+                if w.use_wino or w.use_wino4:
                     a.use_chain = False
         force = os.environ.get("PTX_CHAIN_FORCE")          # "1" / "0": A/B runs
         if force in ("0", "1"):
             a.use_chain = force == "1"
         if a.use_chain:                                    # (a forced chain: the pair's Winograd form does not run)
             for w in pair:
-                if isinstance(w, WinoStep):
-                    w.use_wino = False
+                if isinstance(w, _WinoExec):
+                    w.use_wino = w.use_wino4 = False
         self.steps.append(a)
         self.alt_steps.append(a)
         return a
@@ -1343,7 +1403,7 @@ class Plan:
         autotuner owns) and the direct stem kernels."""
         out = []
         for s in self.steps:
-            for t in (s.active() if isinstance(s, (AltStep, ProgramStep, WinoStep)) else [s]):
+            for t in (s.active() if isinstance(s, (AltStep, ProgramStep, _WinoExec)) else [s]):
                 if isinstance(t, (ConvStep, ChainStep, StemStep, StemF32Step, StemBf16Step, PatchConvStep, ProgramStep)):
                     out.append(t)
         return out

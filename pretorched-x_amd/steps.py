@@ -502,26 +502,47 @@ class AltStep(_Step):
     def active(self):
         if self.use_chain:
             return [self.chain]
-        return [t for s in self.pair for t in (s.active() if isinstance(s, WinoStep) else [s])]
+        return [t for s in self.pair for t in (s.active() if isinstance(s, _WinoExec) else [s])]
 
 
-class WinoStep(_Step):
-    """A stride-1 (kT,3,3) fp32 conv with two compiled executions: the direct launch (`direct`: its ConvStep, on a tile or
-    the body kernel) or Winograd F(2x2,3x3) as three launches (`wino`: the input transform, the grouped (kT,1,1) ConvStep
-    `gemm` on the ordinary tiles, the output transform with the conv's bias / residual / ReLU; csrc/conv_wino_f32.hip).
-    Which one runs is measured per problem by the tuner ("wino:" keys) and defaults to direct; PTX_CONV_WINO=0 compiles no
-    such step, =1 runs the Winograd launches wherever they exist.  `alt`: the AltStep whose pair this conv is the first
-    launch of (a bottleneck's conv2 + conv3), or None: the Winograd form then competes with the chained launch too, and
-    winning it switches the AltStep to its pair.  V and M live in the plan's Winograd arena (bound once it is allocated)."""
-    __slots__ = ("direct", "wino", "gemm", "use_wino", "alt", "label", "key", "v_ptr", "m_ptr", "v_bytes", "arena_bytes")
-    _defaults = {"use_wino": False}
+_WINO_SLOTS = ("direct", "wino", "gemm", "use_wino", "wino4", "gemm4", "use_wino4", "need_u4", "alt", "label", "key", "v_ptr", "m_ptr",
+               "m4_ptr", "v_bytes", "v4_bytes", "arena_bytes")
+
+
+class _WinoExec(_Step):
+    """A stride-1 (kT,3,3) fp32 conv with up to three compiled executions, one of which runs (`active()`):
+    `direct`  its ConvStep, on a tile or the body kernel -- the default;
+    `wino`    Winograd F(2x2,3x3) as three launches: the input transform, the 16-group (kT,1,1) ConvStep `gemm` on the ordinary
+              tiles, the output transform with the conv's bias / residual / ReLU (csrc/conv_wino_f32.hip); `use_wino`;
+    `wino4`   Winograd F(4x4,3x3), the same three launches on 6x6 patches around the 36-group ConvStep `gemm4`; `use_wino4`,
+              exclusive with `use_wino`.  Its filter U4 is allocated and packed only where the step can run (`need_u4`:
+              Plan.wino4_weights -- a stored verdict, the forced mode, or the tuner about to time it).
+    Which one runs is measured per problem by the tuner ("wino:" / "wino4:" keys); PTX_CONV_WINO=0 compiles no such step, =1
+    runs F(2x2) wherever it exists, =4 F(4x4) wherever it exists.  `alt`: the AltStep whose pair this conv is the first launch
+    of (a bottleneck's conv2 + conv3), or None: the Winograd forms then compete with the chained launch too, and winning it
+    switches the AltStep to its pair.  V and M live in the plan's Winograd arena (bound once it is allocated)."""
+    __slots__ = ()
+    _defaults = {"use_wino": False, "use_wino4": False}
+
+    def _steps(self):
+        return self.wino4 if self.use_wino4 else self.wino if self.use_wino else self.direct
 
     def __call__(self, st):
-        for s in (self.wino if self.use_wino else self.direct):
+        for s in self._steps():
             s(st)
 
     def active(self):
-        return list(self.wino if self.use_wino else self.direct)
+        return list(self._steps())
+
+
+class WinoStep(_WinoExec):
+    """A conv with the F(2x2) form (even H and W) -- and, by the wider rule, the F(4x4) form next to it."""
+    __slots__ = _WINO_SLOTS
+
+
+class Wino4Step(_WinoExec):
+    """A conv only F(4x4) takes (odd H or W: partial tiles): `wino` and `gemm` are None, `use_wino` stays False."""
+    __slots__ = _WINO_SLOTS
 
 
 

@@ -7,6 +7,7 @@ One dict, key -> (name, number), behind one lock.  The entry kinds share it by k
     prog:<run hash>     ("program" | "launches", 1)                prog_lookup / prog_store
     body:<key>          ("tall" | "square" | "igemm", 1)           body_lookup / body_store
     wino:<key>          (grouped conv's tile NAME, 1 | 2)          wino_lookup / wino_store   (1 Winograd runs, 2 direct stays)
+    wino4:<key>         (36-group conv's tile NAME, 1 | 2)         wino4_lookup / wino4_store (1 F(4x4) runs, 2 it does not)
     lanes:<model key>   ("lanes", n)                               lanes_lookup / lanes_store
 Tiles are stored by NAME, so inserting / reordering the library's configuration tables cannot remap an entry silently.
 """
@@ -186,6 +187,18 @@ def wino_lookup(key):
 
 def wino_store(key, use_wino, cfg_index):
     _put("wino:" + key, _lib.lib().ptx_conv3d_config_name(int(cfg_index)).decode(), 1 if use_wino else 2)
+
+
+def wino4_lookup(key):
+    """Tuned verdict of the same problem on the Winograd F(4x4,3x3) launches: True = they run (instead of whatever the
+    "wino:" verdict says), False = they do not, None = never measured -- which reads as False.  The name is the tile the
+    36-group conv was measured on."""
+    ent = _get("wino4:" + key)
+    return None if ent is None else ent[1] == 1
+
+
+def wino4_store(key, use_wino4, cfg_index):
+    _put("wino4:" + key, _lib.lib().ptx_conv3d_config_name(int(cfg_index)).decode(), 1 if use_wino4 else 2)
 
 
 def lanes_key(model, shape, precision="fp32"):

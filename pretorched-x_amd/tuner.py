@@ -12,11 +12,11 @@ import torch
 
 from . import _lib
 from ._lib import PtxError
-from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemBf16Step, StemF32Step, StemStep, WinoStep, _dense16,
+from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemBf16Step, StemF32Step, StemStep, _WinoExec, _dense16,
                     _r4, _stream, issued_conv_flop)
 from .tuned import (BODY_SHAPES, _flags_kind, _tile_kind, alt_lookup, alt_store, body_lookup, body_store, chain_lookup,
                     chain_store, lanes_key, lanes_lookup, lanes_store, prog_lookup, prog_store, save_tuned_table, tuned_lookup,
-                    tuned_store, wino_lookup, wino_store)
+                    tuned_store, wino4_lookup, wino4_store, wino_lookup, wino_store)
 
 
 def _time_ms(run, iters):
@@ -297,47 +297,79 @@ def _tune_chain_vs_pair(t):
 
 
 def _tune_wino_vs_direct(t):
-    """Phase 4, Winograd F(2x2,3x3) vs the direct execution of every distinct eligible stride-1 (kT,3,3) problem: tune the
-    grouped conv's tile like any conv (split 1), then time the three launches against the best direct execution the earlier
-    phases left in place -- the tile or body kernel, or, where the conv opens a bottleneck tail, the chain-or-pair verdict
-    with the tail's conv3 on both sides -- under the same 3 % margin as _tune_chain_vs_pair."""
-    if os.environ.get("PTX_CONV_WINO", "auto") in ("0", "1"):
+    """Phase 4, the Winograd forms vs the direct execution of every distinct eligible stride-1 (kT,3,3) problem.  First
+    F(2x2,3x3): tune the grouped conv's tile like any conv (split 1), then time the three launches against the best direct
+    execution the earlier phases left in place -- the tile or body kernel, or, where the conv opens a bottleneck tail, the
+    chain-or-pair verdict with the tail's conv3 on both sides -- under the same 3 % margin as _tune_chain_vs_pair.  Then
+    F(4x4,3x3) the same way (the 36-group conv's tile, the three launches) against the best execution so far, direct or
+    F(2x2), under the same margin."""
+    if os.environ.get("PTX_CONV_WINO", "auto") in ("0", "1", "4"):
         return
-    seen = {}
-    for w in t.plan.wino_steps:
-        g, a = w.gemm, w.alt
-        if w.key in seen:
-            w.use_wino, g.cfg = seen[w.key]
-            if w.use_wino and a is not None:
-                a.use_chain = False
-            continue
-        if t.only_untuned and wino_lookup(w.key) is not None:
-            continue
+    plan, seen, seen4 = t.plan, {}, {}
+    steps = plan.wino_steps + [w for w in plan.wino4_steps if w.wino is None]
+    for w in steps:
+        a = w.alt
         if a is not None and os.environ.get("PTX_CHAIN_FORCE") == "1":
             continue                         # the chained launch is pinned: nothing to decide for the pair's first conv
-        gkey = json.dumps(g.d.key())
-        if not (t.only_untuned and tuned_lookup(gkey, "") is not None):
-            best = _best_conv_tile(t, g, gkey, "", split_k=False)
-            g.cfg, g.split, g.from_table = best[1], 1, False
-            tuned_store(gkey, best[1], 1)
         run = _launch(a if a is not None else w)
         n = max(t.iters, 3)
-        keep_chain = a.use_chain if a is not None else False
-        w.use_wino = False
-        ms_direct = _time_ms(run, n)
-        w.use_wino = True
+
+        def time_form(four, g):
+            """ms of the step with the F(2x2) / F(4x4) launches selected, after sweeping the grouped conv's tile."""
+            gkey = json.dumps(g.d.key())
+            if not (t.only_untuned and tuned_lookup(gkey, "") is not None):
+                best = _best_conv_tile(t, g, gkey, "", split_k=False)
+                g.cfg, g.split, g.from_table = best[1], 1, False
+                tuned_store(gkey, best[1], 1)
+            w.use_wino, w.use_wino4 = not four, four
+            if a is not None:
+                a.use_chain = False
+            return _time_ms(run, n)
+
+        # ---- F(2x2) against the direct execution
+        ms_best, best_name, keep_chain = None, "direct", a.use_chain if a is not None else False
+        if w.wino is not None:
+            g = w.gemm
+            if w.key in seen:
+                w.use_wino, g.cfg = seen[w.key]
+            elif not (t.only_untuned and wino_lookup(w.key) is not None):
+                w.use_wino = w.use_wino4 = False
+                ms_direct = _time_ms(run, n)
+                ms_wino = time_form(False, g)
+                w.use_wino = ms_wino < 0.97 * ms_direct
+                ms_best, best_name = (ms_wino, "wino") if w.use_wino else (ms_direct, "direct")
+                seen[w.key] = (w.use_wino, g.cfg)
+                wino_store(w.key, w.use_wino, g.cfg)
+                tile = t.lib.ptx_conv3d_config_name(g.cfg).decode()
+                t.note("%s\tdirect %.4f ms\twino %.4f ms (%s)\t-> %s\n" % (w.label, ms_direct, ms_wino, tile, best_name),
+                       "tune %-34s direct %.4f ms | wino %.4f ms (%s) -> %s" % (w.label, ms_direct, ms_wino, tile, best_name))
+        # ---- F(4x4) against the best of the two
+        if w.wino4 is not None:
+            g4 = w.gemm4
+            if w.key in seen4:
+                w.use_wino4, g4.cfg = seen4[w.key]
+                if w.use_wino4:
+                    plan.wino4_weights(w, now=True)
+            elif not (t.only_untuned and wino4_lookup(w.key) is not None):
+                keep2 = w.use_wino
+                if ms_best is None:          # the F(2x2) verdict came from the table / there is no F(2x2) form: time what runs now
+                    w.use_wino4 = False
+                    if a is not None and not w.use_wino:
+                        a.use_chain = keep_chain
+                    ms_best, best_name = _time_ms(run, n), "wino" if w.use_wino else "direct"
+                plan.wino4_weights(w, now=True)
+                ms_wino4 = time_form(True, g4)
+                w.use_wino4 = ms_wino4 < 0.97 * ms_best
+                w.use_wino = keep2 and not w.use_wino4
+                seen4[w.key] = (w.use_wino4, g4.cfg)
+                wino4_store(w.key, w.use_wino4, g4.cfg)
+                verdict, tile = "wino4" if w.use_wino4 else best_name, t.lib.ptx_conv3d_config_name(g4.cfg).decode()
+                t.note("%s\t%s %.4f ms\twino4 %.4f ms (%s)\t-> %s\n" % (w.label, best_name, ms_best, ms_wino4, tile, verdict),
+                       "tune %-34s %s %.4f ms | wino4 %.4f ms (%s) -> %s" % (w.label, best_name, ms_best, ms_wino4, tile, verdict))
+        if w.use_wino4:
+            w.use_wino = False
         if a is not None:
-            a.use_chain = False
-        ms_wino = _time_ms(run, n)
-        w.use_wino = ms_wino < 0.97 * ms_direct
-        if a is not None and not w.use_wino:
-            a.use_chain = keep_chain
-        seen[w.key] = (w.use_wino, g.cfg)
-        wino_store(w.key, w.use_wino, g.cfg)
-        verdict = "wino" if w.use_wino else "direct"
-        tile = t.lib.ptx_conv3d_config_name(g.cfg).decode()
-        t.note("%s\tdirect %.4f ms\twino %.4f ms (%s)\t-> %s\n" % (w.label, ms_direct, ms_wino, tile, verdict),
-               "tune %-34s direct %.4f ms | wino %.4f ms (%s) -> %s" % (w.label, ms_direct, ms_wino, tile, verdict))
+            a.use_chain = False if (w.use_wino or w.use_wino4) else keep_chain
 
 
 def _tune_program_vs_launches(t):
@@ -455,7 +487,7 @@ def profile_steps(engine, plan, iters=5, isolated=None):
     if isolated is None:
         isolated = os.environ.get("PTX_PROFILE_ISOLATED", "0") == "1"
     st = _stream()
-    flat = [t for s in plan.steps for t in (s.active() if isinstance(s, (AltStep, ProgramStep, WinoStep)) else [s])]
+    flat = [t for s in plan.steps for t in (s.active() if isinstance(s, (AltStep, ProgramStep, _WinoExec)) else [s])]
     engine.last_profile = None
     if isolated:
         ms_of = [_time_ms(lambda stp=stp: stp(st), iters) for stp in flat]

@@ -42,7 +42,7 @@ torch.cuda.synchronize()
 eng = m.engine()
 plan = next(iter(eng._plans.values()))
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-flat = [t for s in plan.steps for t in (s.active() if isinstance(s, (E.AltStep, E.WinoStep)) else [s])]
+flat = [t for s in plan.steps for t in (s.active() if isinstance(s, (E.AltStep, E._WinoExec)) else [s])]
 MAXWG = 1 << 18
 tl = torch.zeros(MAXWG, 8, dtype=torch.int64, device=DEV)
 tick = 0.01

@@ -18,7 +18,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import pretorched_x_amd as ptx                                   # noqa: E402
 from pretorched_x_amd import _lib                                # noqa: E402
-from pretorched_x_amd.engine import AltStep, Engine, Plan, WinoStep        # noqa: E402
+from pretorched_x_amd.engine import AltStep, Engine, Plan, _WinoExec       # noqa: E402
 
 CLIP_FULL, CLIP_SMALL = (8, 3, 16, 224, 224), (1, 3, 8, 64, 64)
 
@@ -72,14 +72,15 @@ def _record(step):
            getattr(step, "macs", None), getattr(step, "hbm_bytes", None)]
     if isinstance(step, AltStep):
         rec += [bool(step.use_chain), _record(step.chain), [_record(s) for s in step.pair]]
-    if isinstance(step, WinoStep):
-        rec += [bool(step.use_wino), [_record(s) for s in step.direct], [_record(s) for s in step.wino]]
+    if isinstance(step, _WinoExec):
+        rec += [bool(step.use_wino), [_record(s) for s in step.direct], [_record(s) for s in step.wino or []],
+                bool(step.use_wino4), [_record(s) for s in step.wino4 or []]]
     return rec
 
 
 def fingerprint(plan):
     blob = json.dumps([_record(s) for s in plan.steps], sort_keys=True).encode()
-    launches = sum(len(s.active()) if isinstance(s, (AltStep, WinoStep)) else 1 for s in plan.steps)
+    launches = sum(len(s.active()) if isinstance(s, (AltStep, _WinoExec)) else 1 for s in plan.steps)
     return len(plan.steps), launches, int(plan.ws_bytes), hashlib.sha256(blob).hexdigest()[:16]
 
 
