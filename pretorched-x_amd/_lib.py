@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libptx_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd.h")
 WINO4_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_wino4.h")      # the F(4x4) Winograd calls
+TFIR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_tfir.h")        # the stem's temporal fast-FIR calls
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -325,6 +326,20 @@ SIGNATURES_WINO4 = {
 }
 
 
+# include/ptx_amd_tfir.h: the fp32 stem as a fast FIR along time (csrc/conv_stem_tfir_f32.hip), bound the same way
+# (tests/test_stem_tfir_host.py)
+_F = C.POINTER(C.c_float)
+SIGNATURES_TFIR = {
+    "ptx_stem_tfir_scheme": (C.c_int, [_I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, _F, _F]),
+    "ptx_conv_stem_tfir_f32_supported": (C.c_int, [C.POINTER(ConvDesc), _L, _L, _L, _I]),
+    "ptx_stem_tfir_f32_weight_elems": (C.c_size_t, [C.POINTER(ConvDesc), _I]),
+    "ptx_stem_tfir_f32_workspace_bytes": (C.c_size_t, [C.POINTER(ConvDesc), _I]),
+    "ptx_pack_stem_tfir_f32_weight": (C.c_int, [C.POINTER(ConvDesc), _I, _P, _P, _P]),
+    "ptx_stem_tfir_in_f32": (C.c_int, [C.POINTER(ConvDesc), _I, _P, _L, _L, _L, _P, _P]),
+    "ptx_conv_stem_tfir_f32_fwd": (C.c_int, [C.POINTER(ConvDesc), _I, _P, _P, _P, _P, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -358,7 +373,7 @@ def lib():
                 "`python pretorched-x_amd/csrc/build.py` (or __graft_entry__.build()); "
                 "this package has no CPU / eager fallback" % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

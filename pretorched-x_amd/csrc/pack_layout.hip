@@ -1305,3 +1305,7 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 
 // So are the Winograd F(2x2, 3x3) transforms around the grouped implicit GEMM (two memory-bound passes and a filter transform).
 #include "conv_wino_f32.hip"
+
+// So is the fp32 stem as a fast FIR along time (a filter transform, a memory-bound input transform and the stem's step loop over
+// the transformed frames).
+#include "conv_stem_tfir_f32.hip"

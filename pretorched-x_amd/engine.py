@@ -32,7 +32,7 @@ from ._lib import NormDesc, PtxError, check
 from .heads import check_views, linear, relation_mlp, relation_scale, run_views, views_chunk, views_mean  # noqa: F401
 from .plan import BF16_FAMILIES, BF16_GEN_KINDS, BF16_NL_KINDS, Plan, _foldable, model_precision  # noqa: F401
 from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, Wino4Step, WinoStep, _WinoExec,  # noqa: F401
-                    StemBf16Step, StemF32Step, StemStep, _ConcatRowsPack, _Ref, _dense16, _device_ctx, _geom, _ptr, _r4, _r8, _r128,
+                    StemBf16Step, StemF32Step, StemStep, StemTfirStep, _ConcatRowsPack, _Ref, _dense16, _device_ctx, _geom, _ptr, _r4, _r8, _r128,
                     _same_geometry, _stem_ld, _stream, _t3, _tag, _tile_dims, issued_conv_flop)
 from .tuned import (BODY_FILTERS, BODY_SHAPES, _TUNED_PATH, _chain_config_index, _config_index, _flags_kind,  # noqa: F401
                     _tile_kind, _tuned_table, alt_lookup, alt_store, body_lookup, body_store, chain_key, chain_lookup,

@@ -21,11 +21,11 @@ from ._lib import (ConvDesc, ConvFusedExt, ConvProgramInfo, ConvStage, NonlocalD
                    PTX_F16_OPERANDS, PTX_F16X3_OPERANDS, PTX_NL_BF16, PTX_NL_F16, PTX_NL_OUT_F16, PTX_NL_RELU, PTX_NL_SCALE,
                    PTX_NL_SOFTMAX, PTX_NL_X3, PTX_POOL_BF16, PTX_POOL_PAD_ZERO, PTX_POOL_SAME, PTX_PRO_UP2, PTX_RES_F16,
                    PTX_SPLITK_FUSED, PTX_STEM_SRC_BF16_NCDHW, PTX_STEM_SRC_U8_NTHWC, PtxError, check)
-from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step, Wino4Step, WinoStep, _WinoExec,
+from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step, StemTfirStep, TFIR_SCHEMES, Wino4Step, WinoStep, _WinoExec,
                     StemStep, _ConcatRowsPack, _Ref, _device_ctx, _geom, _ptr, _r4, _r8, _r128, _same_geometry, _stem_ld, _stream,
                     _t3, _tag)
 from .tuned import (BODY_FILTERS, BODY_SHAPES, _flags_kind, alt_lookup, body_lookup, chain_key, chain_lookup, prog_lookup,
-                    tuned_lookup, wino4_lookup, wino_lookup)
+                    tfir_lookup, tuned_lookup, wino4_lookup, wino_lookup)
 
 # bf16 inference (a model whose floating-point parameters are torch.bfloat16): the families whose plans run end to end on the
 # bf16 kernels.  Everything else raises at plan build time.
@@ -97,6 +97,7 @@ class Plan:
         self.wino_steps = []     # WinoStep: direct launch | Winograd transforms around a grouped conv, chosen by measurement
         self.wino4_steps = []    # every step with a Winograd F(4x4) form: those of wino_steps, then the F(4x4)-only Wino4Steps
         self.wino_bytes, self.wino_arena = 0, None       # V / M arena of the Winograd steps (the largest need of either form)
+        self.stem_tfir_steps = []        # StemF32Steps with temporal fast-FIR executions (V in the Winograd arena)
         self.stem_bf16_step = None       # the bf16 stem's ConvStep (the tuner bounds its issued work)
         self.bf16_stem = getattr(engine, "bf16_stem", "fold")            # "fold" | "direct" (ptx_conv_stem_bf16_fwd)
         self.stem_steps = self.patch_steps = self.attn_steps = 0         # launches outside conv_steps, by kind
@@ -465,6 +466,9 @@ class Plan:
             if w.use_wino4:
                 self.wino4_weights(w)
         self.wino_arena = torch.empty(self.wino_bytes // 4, device=self.dev, dtype=torch.float32)
+        for st in self.stem_tfir_steps:  # the stem's transformed input: the arena is free while the stem runs
+            for form in st.tfir.values():
+                form[1].v = _ptr(self.wino_arena)
         for w in set(self.wino_steps + self.wino4_steps):
             w.v_ptr = _ptr(self.wino_arena)
             if w.gemm is not None:
@@ -828,9 +832,56 @@ class Plan:
         st.src = src
         st.macs = raw.N * To * Ho * Wo * conv.out_channels * raw.C * kT * kH * kW
         st.hbm_bytes = 0
+        self._stem_tfir(st, raw, w2p)
         self.steps.append(st)
         self.stem_steps += 1
         return y
+
+    def _stem_tfir(self, st, raw, w_stem):
+        """Temporal fast-FIR executions of a 7x7x7 stride-1-in-time fp32 stem (csrc/conv_stem_tfir_f32.hip): per scheme two
+        launches, the temporal input transform into V and the forward over V, chosen against the direct launch by the tuner
+        ("tfir:" keys; default direct).  PTX_STEM_TFIR=0 compiles none, =1|2|3 forces a scheme where the library takes the
+        problem, auto compiles the schemes the tuner may time (TFIR_SCHEMES).  Decoded uint8 frames and padded-pitch clips run the same
+        forms from the plan-owned fp32 buffer, under the same key, so frames and clips keep producing identical bits.  V lives
+        in the Winograd arena; the transformed filters (about 1 MB each) are packed with the plan."""
+        mode = os.environ.get("PTX_STEM_TFIR", "auto")
+        if mode == "0":
+            return
+        d, lib_ = st.d, self.lib
+        schemes = (int(mode),) if mode in ("1", "2", "3") else TFIR_SCHEMES
+        forms = {}
+        for sid in schemes:
+            if not lib_.ptx_conv_stem_tfir_f32_supported(C.byref(d), *st.strides, sid):
+                continue
+            m, P = C.c_int32(), C.c_int32()
+            check(lib_.ptx_stem_tfir_scheme(sid, C.byref(m), C.byref(P), None, None, None), "ptx_stem_tfir_scheme")
+            u = torch.empty(lib_.ptx_stem_tfir_f32_weight_elems(C.byref(d), sid), device=self.dev, dtype=torch.float32)
+            self.keepalive.append(u)
+            up = _ptr(u)
+
+            def repack_tfir(sid=sid, up=up):
+                check(lib_.ptx_pack_stem_tfir_f32_weight(C.byref(d), sid, w_stem, up, _stream()), "ptx_pack_stem_tfir_f32_weight")
+            if torch.device(self.dev).type != "meta":
+                self.refreshers.append(repack_tfir)
+            v_bytes = int(lib_.ptx_stem_tfir_f32_workspace_bytes(C.byref(d), sid))
+            self.wino_bytes = max(self.wino_bytes, v_bytes)
+            f = StemTfirStep()
+            f.d, f.scheme, f.m, f.P, f.w, f.b, f.y, f.macs = d, sid, m.value, P.value, up, st.b, st.y, st.macs
+            f.label = "%s.tfir%d" % (st.label, sid)
+
+            def tfir_in(stream, f=f, sid=sid, st=st):
+                x = st.src if st.src is not None else self.in_ptr
+                check(lib_.ptx_stem_tfir_in_f32(C.byref(d), sid, x, *st.strides, f.v, stream), f.label + "_in")
+            forms[sid] = [_tag(tfir_in, "tfir%d_in" % sid, 4 * raw.N * 3 * raw.T * raw.H * _r4(raw.W) + v_bytes), f]
+        if not forms:
+            return
+        st.tfir, st.key = forms, json.dumps(d.key() + tuple(st.strides))
+        if mode in ("1", "2", "3"):
+            st.use_tfir = int(mode)
+        else:
+            known = tfir_lookup(st.key)
+            st.use_tfir = known if known in forms else 0
+        self.stem_tfir_steps.append(st)
 
     def stem_source(self, raw, pitch):
         """The fp32 NCDHW tensor a direct stem kernel reads, as a device pointer -- or None when that is the caller's own
@@ -1403,8 +1454,8 @@ class Plan:
         autotuner owns) and the direct stem kernels."""
         out = []
         for s in self.steps:
-            for t in (s.active() if isinstance(s, (AltStep, ProgramStep, _WinoExec)) else [s]):
-                if isinstance(t, (ConvStep, ChainStep, StemStep, StemF32Step, StemBf16Step, PatchConvStep, ProgramStep)):
+            for t in (s.active() if isinstance(s, (AltStep, ProgramStep, _WinoExec, StemF32Step)) else [s]):
+                if isinstance(t, (ConvStep, ChainStep, StemStep, StemF32Step, StemTfirStep, StemBf16Step, PatchConvStep, ProgramStep)):
                     out.append(t)
         return out
 

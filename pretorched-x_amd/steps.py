@@ -618,11 +618,19 @@ class PatchConvStep(_Step):
             check(fn(C.byref(self.d), self.x, self.w, self.b, self.y, ext, st), self.label)
 
 
+# temporal fast-FIR schemes of the fp32 stem the tuner times under PTX_STEM_TFIR=auto (include/ptx_amd_tfir.h).  Scheme 3,
+# F(4,7), is the fastest and the least accurate (1.8e-5 of the output scale against 1.9e-6): it runs only when forced.
+TFIR_SCHEMES = (1, 2)
+
+
 class StemF32Step(_Step):
-    """One ptx_conv_stem_f32_fwd launch: the RGB stem on the fp32 matrix cores, read straight from the caller's NCDHW
-    tensor (bound per run: plan.in_ptr) -- no fold, no layout pass."""
-    __slots__ = ("d", "plan", "strides", "w", "b", "y", "label", "macs", "hbm_bytes", "src")
-    _defaults = {"hbm_bytes": 0}
+    """The RGB stem on the fp32 matrix cores, read straight from the caller's NCDHW tensor (bound per run: plan.in_ptr) -- no
+    fold, no layout pass.  One ptx_conv_stem_f32_fwd launch, the default -- or, where the stem is a 7-tap stride-1 FIR along
+    time, `tfir[scheme]` = [temporal input transform, StemTfirStep]: fewer frame-convolutions on the same step loop
+    (csrc/conv_stem_tfir_f32.hip).  `use_tfir`: 0 = direct, else the scheme that runs -- PTX_STEM_TFIR=1|2|3 forces one, else
+    the tuner's "tfir:" verdict; without one the step is the direct launch.  `active()`: the launches that run."""
+    __slots__ = ("d", "plan", "strides", "w", "b", "y", "label", "macs", "hbm_bytes", "src", "tfir", "use_tfir", "key")
+    _defaults = {"hbm_bytes": 0, "use_tfir": 0}
     kernel = "conv_stem_f32"
 
     def issued_flop(self):
@@ -637,11 +645,36 @@ class StemF32Step(_Step):
             steps += max(0, min(d.kT - 1, d.Ti - 1 - t0) - max(0, -t0) + 1) * d.kH
         return float(d.N * tiles * steps * 4 * 44 * 4096)
 
+    def active(self):
+        return list(self.tfir[self.use_tfir]) if self.use_tfir else [self]
+
     def __call__(self, st):
+        if self.use_tfir:
+            for s in self.tfir[self.use_tfir]:
+                s(st)
+            return
         sn, sc, stt = self.strides
         # src: a plan-owned fp32 NCDHW buffer (normalised uint8 frames / pitch-padded rows) or None = the caller's tensor
         x = self.src if self.src is not None else self.plan.in_ptr
         check(_lib.lib().ptx_conv_stem_f32_fwd(C.byref(self.d), x, sn, sc, stt, self.w, self.b, self.y, st), self.label)
+
+
+class StemTfirStep(_Step):
+    """One ptx_conv_stem_tfir_f32_fwd launch: the stem's P frame-convolutions per group of m output frames, read from the
+    transformed input V (the plan's Winograd arena, free while the stem runs) and folded into the m frames."""
+    __slots__ = ("d", "scheme", "m", "P", "v", "w", "b", "y", "label", "macs", "hbm_bytes")
+    _defaults = {"hbm_bytes": 0}
+    kernel = "conv_stem_tfir_f32"
+
+    def issued_flop(self):
+        """FLOP of the MFMAs one launch issues: every group runs all P products (no pruning); per 128-output workgroup and
+        (product, kh) step 4 waves x 22 v_mfma_f32_32x32x2_f32."""
+        d = self.d
+        tiles = -(-(d.Ho * d.Wo) // 128) * -(-_r4(d.Co) // 64)
+        return float(d.N * tiles * -(-d.To // self.m) * self.P * d.kH * 4 * 22 * 4096)
+
+    def __call__(self, st):
+        check(_lib.lib().ptx_conv_stem_tfir_f32_fwd(C.byref(self.d), self.scheme, self.v, self.w, self.b, self.y, st), self.label)
 
 
 def stem_bf16_tiles(d):

@@ -8,6 +8,7 @@ One dict, key -> (name, number), behind one lock.  The entry kinds share it by k
     body:<key>          ("tall" | "square" | "igemm", 1)           body_lookup / body_store
     wino:<key>          (grouped conv's tile NAME, 1 | 2)          wino_lookup / wino_store   (1 Winograd runs, 2 direct stays)
     wino4:<key>         (36-group conv's tile NAME, 1 | 2)         wino4_lookup / wino4_store (1 F(4x4) runs, 2 it does not)
+    tfir:<key>          ("direct" | "fir", 0 | scheme)             tfir_lookup / tfir_store   (the fp32 stem: 0 direct, else the scheme)
     lanes:<model key>   ("lanes", n)                               lanes_lookup / lanes_store
 Tiles are stored by NAME, so inserting / reordering the library's configuration tables cannot remap an entry silently.
 """
@@ -199,6 +200,17 @@ def wino4_lookup(key):
 
 def wino4_store(key, use_wino4, cfg_index):
     _put("wino4:" + key, _lib.lib().ptx_conv3d_config_name(int(cfg_index)).decode(), 1 if use_wino4 else 2)
+
+
+def tfir_lookup(key):
+    """Tuned verdict of an fp32 7x7x7 stem problem on the temporal fast-FIR launches: the scheme that runs (1..3), 0 = the
+    direct launch stays, None = never measured -- which reads as 0."""
+    ent = _get("tfir:" + key)
+    return None if ent is None else int(ent[1])
+
+
+def tfir_store(key, scheme):
+    _put("tfir:" + key, "fir" if scheme else "direct", int(scheme))
 
 
 def lanes_key(model, shape, precision="fp32"):

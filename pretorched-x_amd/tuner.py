@@ -12,11 +12,11 @@ import torch
 
 from . import _lib
 from ._lib import PtxError
-from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemBf16Step, StemF32Step, StemStep, _WinoExec, _dense16,
+from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemBf16Step, StemF32Step, StemStep, StemTfirStep, _WinoExec, _dense16,
                     _r4, _stream, issued_conv_flop)
 from .tuned import (BODY_SHAPES, _flags_kind, _tile_kind, alt_lookup, alt_store, body_lookup, body_store, chain_lookup,
                     chain_store, lanes_key, lanes_lookup, lanes_store, prog_lookup, prog_store, save_tuned_table, tuned_lookup,
-                    tuned_store, wino4_lookup, wino4_store, wino_lookup, wino_store)
+                    tfir_lookup, tfir_store, tuned_store, wino4_lookup, wino4_store, wino_lookup, wino_store)
 
 
 def _time_ms(run, iters):
@@ -94,6 +94,7 @@ def _autotune(engine, model, x, iters=3, verbose=False, persist=False, only_untu
         _tune_chain_tiles(t)
         _tune_chain_vs_pair(t)
         _tune_wino_vs_direct(t)
+        _tune_stem_tfir(t)
         _tune_program_vs_launches(t)
         plan.run_features(_dense16(x))
         plan.tuned = True
@@ -372,6 +373,32 @@ def _tune_wino_vs_direct(t):
             a.use_chain = False if (w.use_wino or w.use_wino4) else keep_chain
 
 
+def _tune_stem_tfir(t):
+    """Phase 4b, the fp32 stem's temporal fast-FIR schemes vs its direct launch: time the direct kernel and the two launches of
+    every compiled scheme on the plan's own buffers, keep the fastest scheme if it beats direct by the 3 % margin of the
+    Winograd phases, else direct."""
+    if os.environ.get("PTX_STEM_TFIR", "auto") != "auto":
+        return
+    for st in t.plan.stem_tfir_steps:
+        if t.only_untuned and tfir_lookup(st.key) is not None:
+            continue
+        run, n = _launch(st), max(t.iters, 5)
+        st.use_tfir = 0
+        ms_direct = _time_ms(run, n)
+        best, ms_best, parts = 0, ms_direct, []
+        for sid in sorted(st.tfir):
+            st.use_tfir = sid
+            ms = _time_ms(run, n)
+            parts.append("fir%d %.4f ms" % (sid, ms))
+            if ms < 0.97 * ms_direct and ms < ms_best:
+                best, ms_best = sid, ms
+        st.use_tfir = best
+        tfir_store(st.key, best)
+        verdict = "fir%d" % best if best else "direct"
+        t.note("%s\tdirect %.4f ms\t%s\t-> %s\n" % (st.label, ms_direct, "\t".join(parts), verdict),
+               "tune %-34s direct %.4f ms | %s -> %s" % (st.label, ms_direct, " | ".join(parts), verdict))
+
+
 def _tune_program_vs_launches(t):
     """Phase 5, conv program vs the launches it replaces (PTX_PROGRAM=auto only): time both executions of every run, keep
     the faster (same margin rule); a program that loses is dissolved into its launches."""
@@ -487,7 +514,7 @@ def profile_steps(engine, plan, iters=5, isolated=None):
     if isolated is None:
         isolated = os.environ.get("PTX_PROFILE_ISOLATED", "0") == "1"
     st = _stream()
-    flat = [t for s in plan.steps for t in (s.active() if isinstance(s, (AltStep, ProgramStep, _WinoExec)) else [s])]
+    flat = [t for s in plan.steps for t in (s.active() if isinstance(s, (AltStep, ProgramStep, _WinoExec, StemF32Step)) else [s])]
     engine.last_profile = None
     if isolated:
         ms_of = [_time_ms(lambda stp=stp: stp(st), iters) for stp in flat]
@@ -499,7 +526,7 @@ def profile_steps(engine, plan, iters=5, isolated=None):
             rows.append((stp.label, "stem", 0, stp.macs, ms, stp.kernel))
         elif isinstance(stp, ConvStep):
             rows.append((stp.label, "conv", 0, stp.macs, ms, _lib.lib().ptx_conv3d_config_name(stp.cfg).decode(), stp))
-        elif isinstance(stp, (StemStep, StemF32Step, StemBf16Step, PatchConvStep)):      # direct (patch) kernels are convs too
+        elif isinstance(stp, (StemStep, StemF32Step, StemTfirStep, StemBf16Step, PatchConvStep)):      # direct (patch) kernels are convs too
             rows.append((stp.label, "stem", 0, stp.macs, ms, stp.kernel))
         elif isinstance(stp, (ChainStep, ProgramStep)):     # several convs in one launch, their own tile tables
             rows.append((stp.label, "chain", 0, stp.macs, ms, stp.kernel))
