@@ -67,17 +67,6 @@ struct BodyF32Args {
 constexpr int kB3ParkStride = 32 * 4 + 4;            // floats between the 4-channel groups of a parked 32-row tile (+4: bank spread)
 constexpr int kB3Park = 16 * kB3ParkStride;          // floats of one parked [32 rows][64 channels] tile: 8.25 KiB
 
-__device__ __forceinline__ unsigned b3_fdiv(unsigned n, const unsigned (&dv)[2]) {
-    return dv[0] ? (__umulhi(n, dv[0]) >> dv[1]) : n;
-}
-static inline void b3_fdiv_make(unsigned d, unsigned (&out)[2]) {
-    if (d <= 1) { out[0] = 0; out[1] = 0; return; }
-    unsigned l = 0;
-    while ((1ull << l) < d) ++l;
-    out[0] = (unsigned)(((1ull << (31 + l)) + d - 1) / d);
-    out[1] = l - 1;
-}
-
 // One tile.  WM x WN waves, each RT x CT MFMA tiles of 32 x 32; NP = 16-byte patch pieces per thread.
 template <int WM, int WN, int RT, int CT, int NP, bool CHAIN>
 __device__ __forceinline__ void conv_body_tile(const BodyF32Args& p, float* smem, const int n, const int to, const int m0, const int nt,
@@ -96,7 +85,7 @@ __device__ __forceinline__ void conv_body_tile(const BodyF32Args& p, float* smem
     const int wm = wave / WN, wn = wave % WN;
     const int g = lane >> 5, l32 = lane & 31;
     const int frame = p.H * p.W;
-    const int ho_a = (int)b3_fdiv((unsigned)m0, p.dv_w);
+    const int ho_a = (int)fdiv((unsigned)m0, p.dv_w);
     const int h_base = ho_a - 1;                        // input row of patch row 0
 
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
@@ -108,9 +97,9 @@ __device__ __forceinline__ void conv_body_tile(const BodyF32Args& p, float* smem
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const int q = tid + kB3NT * i;
-        const int grp = (int)b3_fdiv((unsigned)q, dv_npos);
+        const int grp = (int)fdiv((unsigned)q, dv_npos);
         const int pos = q - grp * NPOS;
-        const int pr = (int)b3_fdiv((unsigned)pos, p.dv_pc);
+        const int pr = (int)fdiv((unsigned)pos, p.dv_pc);
         const int h = h_base + pr, w = pos - pr * p.PC - 1;
         const bool ok = grp < 4 && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
         a_src[i] = ok ? (unsigned)(((h * p.W + w) * p.ldx + grp * 4) * 4) : kOOB;
@@ -147,7 +136,7 @@ __device__ __forceinline__ void conv_body_tile(const BodyF32Args& p, float* smem
     for (int i = 0; i < RT; ++i) {
         const int ml = m0 + (wm * RT + i) * 32 + l32;
         const int mm = ml < frame ? ml : m0;
-        const int ho = (int)b3_fdiv((unsigned)mm, p.dv_w);
+        const int ho = (int)fdiv((unsigned)mm, p.dv_w);
         const int wo = mm - ho * p.W;
         a_row[i] = (g * NPOS + (ho - ho_a) * p.PC + wo) * 4;
         any_valid |= (m0 + (wm * RT + i) * 32) < frame;
@@ -463,7 +452,7 @@ __device__ __forceinline__ void conv_tstack_tile(const BodyF32Args& p, float* sm
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const int q = tid + kB3NT * i;
-        const int grp = (int)b3_fdiv((unsigned)q, p.dv_npos_tall);
+        const int grp = (int)fdiv((unsigned)q, p.dv_npos_tall);
         const int pos = q - grp * NPOS;
         const int t = t0 - p.pT + (pos >> 5), s = s0 + (pos & 31);
         const bool ok = grp < 4 && (unsigned)t < (unsigned)p.T && s < p.HW;
@@ -769,10 +758,10 @@ static size_t body_make_args(const ptx_conv3d_desc* d, int shape, BodyF32Args& a
     const uint64_t M = (uint64_t)d->N * d->Ti * d->Hi * d->Wi;
     a.x_bytes = (unsigned)(M * d->ldx * 4ull);
     a.w_bytes = (unsigned)(ptx_conv_body_f32_weight_elems(d) * 4ull);
-    b3_fdiv_make((unsigned)d->Wi, a.dv_w);
-    b3_fdiv_make((unsigned)a.PC, a.dv_pc);
-    b3_fdiv_make((unsigned)(a.PR_tall * a.PC), a.dv_npos_tall);
-    b3_fdiv_make((unsigned)(a.PR_sq * a.PC), a.dv_npos_sq);
+    fdiv_make((unsigned)d->Wi, a.dv_w);
+    fdiv_make((unsigned)a.PC, a.dv_pc);
+    fdiv_make((unsigned)(a.PR_tall * a.PC), a.dv_npos_tall);
+    fdiv_make((unsigned)(a.PR_sq * a.PC), a.dv_npos_sq);
     const int npos = std::max(g.tall_per_frame ? a.PR_tall * a.PC : 0, a.PR_sq * a.PC);
     return (size_t)(16 * npos + 3 * kB3Slot) * sizeof(float);
 }
@@ -798,7 +787,7 @@ static int launch_tstack(const ptx_conv3d_desc* d, const float* x, const float* 
     a.y_bytes = (unsigned)(M * d->ldy * 4ull);
     a.r_bytes = (unsigned)(M * a.ldr * 4ull);
     const int npos = (kTsF + d->kT - 1) * kTsS;
-    b3_fdiv_make((unsigned)npos, a.dv_npos_tall);
+    fdiv_make((unsigned)npos, a.dv_npos_tall);
     const size_t lds = (size_t)(16 * npos + 3 * kB3Slot) * sizeof(float);     // 40 KiB at kT = 7: three / four workgroups per CU
     static bool attr_set[64] = {};
     int dev = 0;

@@ -63,17 +63,6 @@ struct StemBf16Args {
     unsigned dv_wo[2], dv_pc2[2];
 };
 
-__device__ __forceinline__ unsigned sb_fdiv(unsigned n, const unsigned (&dv)[2]) {
-    return dv[0] ? (__umulhi(n, dv[0]) >> dv[1]) : n;
-}
-static inline void sb_fdiv_make(unsigned d, unsigned (&out)[2]) {
-    if (d <= 1) { out[0] = 0; out[1] = 0; return; }
-    unsigned l = 0;
-    while ((1ull << l) < d) ++l;
-    out[0] = (unsigned)(((1ull << (31 + l)) + d - 1) / d);
-    out[1] = l - 1;
-}
-
 __device__ __forceinline__ unsigned short sb_bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
 
 template <int SRC>
@@ -102,7 +91,7 @@ __global__ void __launch_bounds__(kSbNT, 2) conv_stem_bf16_kernel(const StemBf16
         wo_a = (band - ho_a * p.segs) * kSbRows;
     } else {
         m0 = band * kSbRows;
-        ho_a = (int)sb_fdiv((unsigned)m0, p.dv_wo);
+        ho_a = (int)fdiv((unsigned)m0, p.dv_wo);
         wo_a = 0;
     }
 
@@ -126,7 +115,7 @@ __global__ void __launch_bounds__(kSbNT, 2) conv_stem_bf16_kernel(const StemBf16
         } else {
             pos_ok[j] = m0 + idx < frame_out;
             const int mm = pos_ok[j] ? m0 + idx : m0;
-            ho = (int)sb_fdiv((unsigned)mm, p.dv_wo);
+            ho = (int)fdiv((unsigned)mm, p.dv_wo);
             wo = mm - ho * p.Wo;
         }
         boff[j] = (ho - ho_a) * p.sH * p.PC + (wo - wo_a) * p.sW + 2 * g;
@@ -149,7 +138,7 @@ __global__ void __launch_bounds__(kSbNT, 2) conv_stem_bf16_kernel(const StemBf16
         const unsigned char* fb = static_cast<const unsigned char*>(p.x) + ((size_t)n * p.Ti + t) * HW * 3;
         const size_t cs = (size_t)p.Ti * HW;
         for (int u = tid; u < npairs; u += kSbNT) {
-            const int pr = (int)sb_fdiv((unsigned)u, p.dv_pc2);
+            const int pr = (int)fdiv((unsigned)u, p.dv_pc2);
             const int hh = h0 + pr, ww = w0 + 2 * (u - pr * pc2);
             const bool hok = (unsigned)hh < (unsigned)p.Hi;
             const bool ok0 = hok && (unsigned)ww < (unsigned)p.Wi, ok1 = hok && (unsigned)(ww + 1) < (unsigned)p.Wi;
@@ -356,8 +345,8 @@ extern "C" int ptx_conv_stem_bf16_fwd(const ptx_conv3d_desc* d, const void* x, i
     a.n_tiles = d->N * d->To * g.tiles_per_frame;
     a.w_tiles = d->Co_pad / kSbBN;
     a.flags = d->flags;
-    sb_fdiv_make((unsigned)d->Wo, a.dv_wo);
-    sb_fdiv_make((unsigned)(g.PC / 2), a.dv_pc2);
+    fdiv_make((unsigned)d->Wo, a.dv_wo);
+    fdiv_make((unsigned)(g.PC / 2), a.dv_pc2);
     const size_t lds = (size_t)g.PR * g.PC * 8 + 2 * kSbWSlot * 2 + 3 * 256 * 2;
     const dim3 grid((unsigned)a.n_tiles, (unsigned)cdiv(d->ldy, kSbBN));
     if (src == PTX_STEM_SRC_U8_NTHWC)

@@ -52,4 +52,18 @@ int linear_gemm(const float* x, const float* w, const float* b, float* y, int M,
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// n / d for n < 2^31 by multiply and shift (a kernel argument made once on the host): d == 1 -> mul == 0; else l = ceil(log2 d),
+// mul = ceil(2^(31+l) / d) (< 2^32), q = umulhi(n, mul) >> (l - 1).  Exact: the rounding error of mul adds less than 2^-l <= 1/d
+// to n / d.
+inline void fdiv_make(unsigned d, unsigned (&out)[2]) {
+    if (d <= 1) { out[0] = 0; out[1] = 0; return; }
+    unsigned l = 0;
+    while ((1ull << l) < d) ++l;
+    out[0] = (unsigned)(((1ull << (31 + l)) + d - 1) / d);
+    out[1] = l - 1;
+}
+__device__ __forceinline__ unsigned fdiv(unsigned n, const unsigned (&dv)[2]) {
+    return dv[0] ? (__umulhi(n, dv[0]) >> dv[1]) : n;
+}
+
 }  // namespace ptx

@@ -52,17 +52,6 @@ struct StemArgs {
     unsigned dv_cw[2];    // fast division by CW
 };
 
-__device__ __forceinline__ unsigned fdiv(unsigned n, const unsigned (&dv)[2]) {
-    return dv[0] ? (__umulhi(n, dv[0]) >> dv[1]) : n;
-}
-static inline void fdiv_make(unsigned d, unsigned (&out)[2]) {
-    if (d <= 1) { out[0] = 0; out[1] = 0; return; }
-    unsigned l = 0;
-    while ((1ull << l) < d) ++l;
-    out[0] = (unsigned)(((1ull << (31 + l)) + d - 1) / d);
-    out[1] = l - 1;
-}
-
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 

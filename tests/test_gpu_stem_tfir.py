@@ -26,6 +26,7 @@ CASES = {
     "pitch_stride1": (1, 5, 18, 22, 40, 1, 1),       # W % 4 != 0 (pitch 24), stride 1, ragged channels inside the first tile
     "one_frame": (1, 1, 16, 16, 64, 2, 1),           # To == 1
     "frame_stride": (1, 4, 16, 16, 64, 2, 2),        # short_clip read as x[:, :, ::2] of an 8-frame tensor
+    "wide_patch": (1, 2, 8, 248, 64, 2, 1),          # 11 x 256 patch = 2112 pieces: the 12-pieces-per-thread kernels
 }
 
 
