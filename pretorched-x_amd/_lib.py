@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libptx_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd.h")
 WINO4_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_wino4.h")      # the F(4x4) Winograd calls
 TFIR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_tfir.h")        # the stem's temporal fast-FIR calls
+YUV16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_yuv16.h")      # 10- / 12-bit YUV 4:2:0 sources
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -143,6 +144,16 @@ class ClipSrc(C.Structure):
 class ClipSrcYuv420(C.Structure):
     """ptx_clip_src_yuv420: the same for ptx_resize_clips_yuv420 (the planes at frame 0 of the clip's video)."""
     _fields_ = [("planes", Yuv420Src), ("H", C.c_int32), ("W", C.c_int32), ("Tv", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Yuv420P16Src(C.Structure):
+    """ptx_yuv420p16_src (ptx_amd_yuv16.h): ptx_yuv420_src with 16-bit words of `bits` significant bits, `shift` bits up."""
+    _fields_ = Yuv420Src._fields_ + [("bits", C.c_int32), ("shift", C.c_int32)]
+
+
+class ClipSrcYuv420P16(C.Structure):
+    """ptx_clip_src_yuv420p16: the per-clip row of ptx_resize_clips_yuv420p16."""
+    _fields_ = [("planes", Yuv420P16Src), ("H", C.c_int32), ("W", C.c_int32), ("Tv", C.c_int32), ("reserved", C.c_int32)]
 
 
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
@@ -340,6 +351,14 @@ SIGNATURES_TFIR = {
 }
 
 
+# include/ptx_amd_yuv16.h: the resize entry points on 10- / 12-bit YUV 4:2:0 sources, bound the same way
+# (tests/test_yuv16_frames_host.py); every signature is its _yuv420 twin's with the 16-bit descriptor
+SIGNATURES_YUV16 = {
+    name.replace("_yuv420", "_yuv420p16"): (res, [C.POINTER(Yuv420P16Src) if a == C.POINTER(Yuv420Src) else a for a in args])
+    for name, (res, args) in SIGNATURES.items() if "_yuv420" in name
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -373,7 +392,8 @@ def lib():
                 "`python pretorched-x_amd/csrc/build.py` (or __graft_entry__.build()); "
                 "this package has no CPU / eager fallback" % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
+                list(SIGNATURES_YUV16.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

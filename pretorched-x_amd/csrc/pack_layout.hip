@@ -280,8 +280,9 @@ __global__ void __launch_bounds__(256) fold_kw_frames_u8_kernel(const unsigned c
 // Table entries are clamped to the frame: a wrong table gives wrong pixels, never a stray access.
 // ---------------------------------------------------------------------------------------------
 
-// YUV: the frames are the planes of `ys` (f is unused) and a row is converted to RGB while it is staged (resize_common.h);
-// everything from the staged row on is the same code.
+// SRC is the source flavour: kSrcRgb (interleaved uint8 frames f), kSrcYuv8 or kSrcYuv16 (YUV below: the frames are the
+// planes of `ys`, 8-bit or 10- / 12-bit in 16-bit words, f is unused, and a row is converted to RGB while it is staged,
+// resize_common.h); everything from the staged row on is the same code.
 // WIN (ptx_resize_frames_*_windows): the tables cover the whole resized frame (win.h rows, win.w columns) and every clip
 // has a window of its own: output pixel (r, c) of clip n takes table row top_n + (vflip_n ? Ho-1-r : r) and table column
 // left_n + (hflip_n ? Wo-1-c : c).  Only the table INDEX changes: the workgroup copies those entries to LDS where the
@@ -304,17 +305,19 @@ struct ResizeWindows {
 // sized the row stages from, and H, W are clamped into them.
 struct ResizeClips {
     const ptx_clip_src* srcs;              // device, [N] (RGB)
-    const ptx_clip_src_yuv420* ysrcs;      // device, [N] (YUV)
+    const void* ysrcs;                     // device, [N] (YUV: ptx_clip_src_yuv420 or ptx_clip_src_yuv420p16 rows)
     const int* frame_idx;                  // device, [N][T]
 };
 
-template <int C, bool YUV = false, bool WIN = false, bool TAB = false, bool CLIPS = false>
+template <int C, int SRC = kSrcRgb, bool WIN = false, bool TAB = false, bool CLIPS = false>
 __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d, const unsigned char* __restrict__ f,
                                                                const int* __restrict__ row_lo, const int* __restrict__ row_n,
                                                                const int* __restrict__ row_k, const int* __restrict__ col_lo,
                                                                const int* __restrict__ col_n, const int* __restrict__ col_k,
                                                                void* __restrict__ y, ptx_norm_desc nd, ResizePlan pl,
-                                                               ptx_yuv420_src ys, ResizeWindows win, ResizeClips clips) {
+                                                               typename YuvSource<SRC>::Desc ys, ResizeWindows win,
+                                                               ResizeClips clips) {
+    constexpr bool YUV = SRC != kSrcRgb;
     extern __shared__ __attribute__((aligned(16))) unsigned char resize_smem[];
     int* hdr = reinterpret_cast<int*>(resize_smem);                 // [0] first, [1] one-past-last referenced column
     int* t_clo = hdr + 4;                                           // clamped table entries: columns [Wo], [Wo] ...
@@ -339,7 +342,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
         int64_t stride_t = 0;
         const unsigned char* base = nullptr;
         if constexpr (YUV) {
-            const ptx_clip_src_yuv420 cs = clips.ysrcs[frame / d.T];
+            const auto cs = static_cast<const typename YuvSource<SRC>::Clip*>(clips.ysrcs)[frame / d.T];
             ys = cs.planes;
             H = cs.H, W = cs.W, Tv = cs.Tv;
         } else {
@@ -450,7 +453,7 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
         // row is resampled, so the HBM latency hides under the LDS work instead of adding to every row.
         unsigned char* sw = stage + wave * pl.stage_stride;
         ResizeRow pre = {};
-        YuvRow ypre = {};
+        typename YuvSource<SRC>::Row ypre = {};
         if constexpr (YUV) yuv_fetch_row(ypre, 0 + wave, nrows, ys, yf, lo0, cmin, px_end, lane);
         else resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, W, cmin, C, span_bytes, lane);
         for (int i0 = 0; i0 < nrows; i0 += 4) {
@@ -1044,19 +1047,20 @@ static int resize_norm(const ptx_resize_desc* desc, const ptx_norm_desc* norm, p
     return PTX_OK;
 }
 
-// Both sources: `frames` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.  All three
+// All sources: `frames` (interleaved uint8) or, when src / src16 is not null, the planes of a YUV 4:2:0 source.  All three
 // table modes: the fixed window (win == nullptr: the tables hold the window's entries), one window per clip (win->wins,
 // tables of win->h x win->w entries) or tables per clip (per_clip: every table has a leading [N]).
 static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames, const ptx_yuv420_src* src, const int32_t* row_lo,
                              const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo, const int32_t* col_n,
                              const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream, const char* who,
-                             const ResizeWindows* win = nullptr, bool per_clip = false) {
+                             const ResizeWindows* win = nullptr, bool per_clip = false, const ptx_yuv420p16_src* src16 = nullptr) {
     ResizePlan p;
     int s = resize_plan(desc, y, &p, who);
     if (s) return s;
     if (src && (s = yuv_check(src, desc->C, desc->H, desc->W, who))) return s;
+    if (src16 && (s = yuv_check(src16, desc->C, desc->H, desc->W, who))) return s;
     if (win && (s = resize_windows_check(desc, win->h, win->w, who))) return s;
-    if ((!frames && !src) || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k || (win && !win->wins))
+    if ((!frames && !src && !src16) || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k || (win && !win->wins))
         return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     ptx_norm_desc nd = {};
     if ((s = resize_norm(desc, norm, &nd, who))) return s;
@@ -1065,15 +1069,28 @@ static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames,
     const ResizeWindows rw = win ? *win : ResizeWindows{};
     const unsigned char* none = nullptr;
 #define PTX_RESIZE_LAUNCH(CH, YUV, WIN, TAB)                                                                          \
-    hipLaunchKernelGGL((resize_frames_u8_kernel<CH, YUV, WIN, TAB>), grid, dim3(256), p.lds_bytes, st, *desc,           \
+    hipLaunchKernelGGL((resize_frames_u8_kernel<CH, YUV ? kSrcYuv8 : kSrcRgb, WIN, TAB>), grid, dim3(256), p.lds_bytes, st, *desc, \
                        YUV ? none : frames, row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, YUV ? *src : ptx_yuv420_src{}, \
                        rw, ResizeClips{})
+#define PTX_RESIZE_LAUNCH16(WIN, TAB)                                                                                 \
+    hipLaunchKernelGGL((resize_frames_u8_kernel<3, kSrcYuv16, WIN, TAB>), grid, dim3(256), p.lds_bytes, st, *desc, none, \
+                       row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, *src16, rw, ResizeClips{})
 #define PTX_RESIZE_LAUNCH_C(WIN, TAB)                          \
     switch (desc->C) {                                         \
         case 1: PTX_RESIZE_LAUNCH(1, false, WIN, TAB); break;  \
         case 2: PTX_RESIZE_LAUNCH(2, false, WIN, TAB); break;  \
         case 3: PTX_RESIZE_LAUNCH(3, false, WIN, TAB); break;  \
         default: PTX_RESIZE_LAUNCH(4, false, WIN, TAB); break; \
+    }
+    if (src16) {
+        if (per_clip) {
+            PTX_RESIZE_LAUNCH16(false, true);
+        } else if (win) {
+            PTX_RESIZE_LAUNCH16(true, false);
+        } else {
+            PTX_RESIZE_LAUNCH16(false, false);
+        }
+        return hip_check(hipGetLastError(), who);
     }
     if (src) {
         if (per_clip) {
@@ -1095,6 +1112,7 @@ static int resize_frames_run(const ptx_resize_desc* desc, const uint8_t* frames,
     }
     PTX_RESIZE_LAUNCH_C(false, false)
 #undef PTX_RESIZE_LAUNCH_C
+#undef PTX_RESIZE_LAUNCH16
 #undef PTX_RESIZE_LAUNCH
     return hip_check(hipGetLastError(), "ptx_resize_frames_u8 launch");
 }
@@ -1181,6 +1199,59 @@ extern "C" int ptx_resize_frames_yuv420_tables(const ptx_resize_desc* desc, cons
     const char* who = "ptx_resize_frames_yuv420_tables";
     if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
     return resize_frames_run(desc, nullptr, src, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, nullptr, true);
+}
+
+// The same three launches on a 10- / 12-bit source (include/ptx_amd_yuv16.h).
+extern "C" int ptx_resize_frames_yuv420p16_supported(const ptx_resize_desc* desc, const ptx_yuv420p16_src* src) {
+    const char* who = "ptx_resize_frames_yuv420p16_supported";
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, who) == PTX_OK && yuv_check(src, desc->C, desc->H, desc->W, who) == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_yuv420p16(const ptx_resize_desc* desc, const ptx_yuv420p16_src* src, const int32_t* row_lo,
+                                           const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                                           const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm,
+                                           ptx_stream_t stream) {
+    const char* who = "ptx_resize_frames_yuv420p16";
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    return resize_frames_run(desc, nullptr, nullptr, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, nullptr,
+                             false, src);
+}
+
+extern "C" int ptx_resize_frames_yuv420p16_windows_supported(const ptx_resize_desc* desc, const ptx_yuv420p16_src* src, int32_t h,
+                                                             int32_t w) {
+    const char* who = "ptx_resize_frames_yuv420p16_windows_supported";
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, who) == PTX_OK && yuv_check(src, desc->C, desc->H, desc->W, who) == PTX_OK &&
+           resize_windows_check(desc, h, w, who) == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_yuv420p16_windows(const ptx_resize_desc* desc, const ptx_yuv420p16_src* src,
+                                                   const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
+                                                   const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, int32_t h,
+                                                   int32_t w, const ptx_resize_window* windows, void* y,
+                                                   const ptx_norm_desc* norm, ptx_stream_t stream) {
+    const char* who = "ptx_resize_frames_yuv420p16_windows";
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    const ResizeWindows win = {windows, h, w};
+    return resize_frames_run(desc, nullptr, nullptr, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, &win,
+                             false, src);
+}
+
+extern "C" int ptx_resize_frames_yuv420p16_tables_supported(const ptx_resize_desc* desc, const ptx_yuv420p16_src* src) {
+    const char* who = "ptx_resize_frames_yuv420p16_tables_supported";
+    ResizePlan p;
+    return resize_plan(desc, nullptr, &p, who) == PTX_OK && yuv_check(src, desc->C, desc->H, desc->W, who) == PTX_OK;
+}
+
+extern "C" int ptx_resize_frames_yuv420p16_tables(const ptx_resize_desc* desc, const ptx_yuv420p16_src* src, const int32_t* row_lo,
+                                                  const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
+                                                  const int32_t* col_n, const int32_t* col_k, void* y,
+                                                  const ptx_norm_desc* norm, ptx_stream_t stream) {
+    const char* who = "ptx_resize_frames_yuv420p16_tables";
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    return resize_frames_run(desc, nullptr, nullptr, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, nullptr,
+                             true, src);
 }
 
 extern "C" int ptx_resize_build_tables(const ptx_resize_desc* desc, const ptx_resize_geom* geoms, int32_t* row_lo,

@@ -24,10 +24,11 @@ __global__ void __launch_bounds__(256) resize_build_tables_clips_kernel(ptx_resi
 
 }  // namespace ptx
 
-static int resize_clips_run(const ptx_resize_desc* desc, const ptx_clip_src* srcs, const ptx_clip_src_yuv420* ysrcs,
+// ysrcs: rows of ptx_clip_src_yuv420, or of ptx_clip_src_yuv420p16 when p16 is set
+static int resize_clips_run(const ptx_resize_desc* desc, const ptx_clip_src* srcs, const void* ysrcs,
                             const int32_t* frame_idx, const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
                             const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm,
-                            ptx_stream_t stream, const char* who) {
+                            ptx_stream_t stream, const char* who, bool p16 = false) {
     ResizePlan p;
     int s = resize_plan(desc, y, &p, who);
     if (s) return s;
@@ -40,17 +41,19 @@ static int resize_clips_run(const ptx_resize_desc* desc, const ptx_clip_src* src
     const hipStream_t st = (hipStream_t)stream;
     const ResizeClips rc = {srcs, ysrcs, frame_idx};
     const unsigned char* none = nullptr;
-#define PTX_CLIPS_LAUNCH(CH, YUV)                                                                                          \
-    hipLaunchKernelGGL((resize_frames_u8_kernel<CH, YUV, false, false, true>), grid, dim3(256), p.lds_bytes, st, *desc, none, \
-                       row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, ptx_yuv420_src{}, ResizeWindows{}, rc)
-    if (ysrcs) {
-        PTX_CLIPS_LAUNCH(3, true);
+#define PTX_CLIPS_LAUNCH(CH, SRC)                                                                                          \
+    hipLaunchKernelGGL((resize_frames_u8_kernel<CH, SRC, false, false, true>), grid, dim3(256), p.lds_bytes, st, *desc, none, \
+                       row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, YuvSource<SRC>::Desc{}, ResizeWindows{}, rc)
+    if (ysrcs && p16) {
+        PTX_CLIPS_LAUNCH(3, kSrcYuv16);
+    } else if (ysrcs) {
+        PTX_CLIPS_LAUNCH(3, kSrcYuv8);
     } else {
         switch (desc->C) {
-            case 1: PTX_CLIPS_LAUNCH(1, false); break;
-            case 2: PTX_CLIPS_LAUNCH(2, false); break;
-            case 3: PTX_CLIPS_LAUNCH(3, false); break;
-            default: PTX_CLIPS_LAUNCH(4, false); break;
+            case 1: PTX_CLIPS_LAUNCH(1, kSrcRgb); break;
+            case 2: PTX_CLIPS_LAUNCH(2, kSrcRgb); break;
+            case 3: PTX_CLIPS_LAUNCH(3, kSrcRgb); break;
+            default: PTX_CLIPS_LAUNCH(4, kSrcRgb); break;
         }
     }
 #undef PTX_CLIPS_LAUNCH
@@ -85,6 +88,22 @@ extern "C" int ptx_resize_clips_yuv420(const ptx_resize_desc* desc, const ptx_cl
     const char* who = "ptx_resize_clips_yuv420";
     if (!srcs) return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     return resize_clips_run(desc, nullptr, srcs, frame_idx, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who);
+}
+
+extern "C" int ptx_resize_clips_yuv420p16_supported(const ptx_resize_desc* desc) {
+    const char* who = "ptx_resize_clips_yuv420p16_supported";
+    ResizePlan p;
+    if (resize_plan(desc, nullptr, &p, who) != PTX_OK) return 0;
+    return desc->C == 3 || fail(PTX_ERR_INVALID, "%s: C=%d, a YUV source converts to 3 channels", who, desc->C) == PTX_OK;
+}
+
+extern "C" int ptx_resize_clips_yuv420p16(const ptx_resize_desc* desc, const ptx_clip_src_yuv420p16* srcs, const int32_t* frame_idx,
+                                          const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
+                                          const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, void* y,
+                                          const ptx_norm_desc* norm, ptx_stream_t stream) {
+    const char* who = "ptx_resize_clips_yuv420p16";
+    if (!srcs) return fail(PTX_ERR_INVALID, "%s: null pointer", who);
+    return resize_clips_run(desc, nullptr, srcs, frame_idx, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, true);
 }
 
 extern "C" int ptx_resize_build_tables_clips(const ptx_resize_desc* desc, const ptx_clip_src* srcs, const ptx_resize_geom* geoms,

@@ -2,6 +2,7 @@
 // frame) and resize_views_u8_kernel (resize_views.hip: clips x crops of a video, sampled through an index table).
 #pragma once
 #include "ptx_common.h"
+#include "../../include/ptx_amd_yuv16.h"
 #include <algorithm>
 
 namespace ptx {
@@ -208,6 +209,176 @@ inline int yuv_check(const ptx_yuv420_src* s, int C, int H, int W, const char* w
     if (s->pitch_y < W || s->pitch_c < Wc * s->step_c)
         return fail(PTX_ERR_INVALID, "%s: pitch_y=%d / pitch_c=%d are shorter than a row (%d luma, %lld chroma bytes)", who,
                     s->pitch_y, s->pitch_c, W, (long long)(Wc * s->step_c));
+    if ((int64_t)H * s->pitch_y > INT32_MAX || Hc * s->pitch_c > INT32_MAX)
+        return fail(PTX_ERR_UNSUPPORTED, "%s: a plane of a frame exceeds 32-bit indexing", who);
+    return PTX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// 10- / 12-bit YUV 4:2:0 sources (ptx_yuv420p16_src: P010 / P012 / P016 surfaces, yuv420p10le / p12le planes): the
+// same five pieces on 16-bit words.  A group is still 16 pixels that start at an even pixel, now 32 luma bytes and 32
+// chroma bytes: four 16-byte loads (interleaved chroma is de-interleaved with v_perm on 16-bit lanes, planar chroma is
+// one 16-byte load per plane), and the partial last group of a row is fetched sample by sample.  A sample is
+// (word >> shift) & (2^bits - 1), and with d = bits - 8
+//   R = clip8((ky y' + krv cr + 2^(15+d)) >> (16+d))   G = clip8((ky y' - kgu cb - kgv cr + 2^(15+d)) >> (16+d))
+//   B = clip8((ky y' + kbu cb + 2^(15+d)) >> (16+d))   y' = Y - y_off, cb = Cb - (128 << d), cr = Cr - (128 << d)
+// Products stay below 2^30 and sums below 2^31 (coefficients < 2^18, samples < 2^12), so __mul24 serves as it does
+// for bytes.  The group is staged as the same 48 RGB bytes at the same place, so everything behind the row stage is
+// shared with the other two flavours.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSrcRgb = 0, kSrcYuv8 = 1, kSrcYuv16 = 2;     // the kernels' source flavour (template parameter SRC)
+constexpr int kYuv16Prefetch = 2;                           // groups per lane a 16-bit row keeps in registers (of 1024 pixels each)
+
+struct Yuv16Group {              // 16 pixels: 16 luma words (y0, y1), then 8 U words (u) and 8 V words (v)
+    u32x4 y0, y1, u, v;
+};
+struct Yuv16Row {                // one lane's share of the first kYuv16Prefetch * 1024 pixels of a row
+    Yuv16Group g[kYuv16Prefetch];
+};
+
+__device__ __forceinline__ YuvFrame yuv_frame(const ptx_yuv420p16_src& s, int n, int t) {
+    YuvFrame f;                  // byte pointers: strides and pitches are in bytes
+    f.y = reinterpret_cast<const unsigned char*>(s.y) + (int64_t)n * s.stride_n_y + (int64_t)t * s.stride_t_y;
+    f.u = reinterpret_cast<const unsigned char*>(s.u) + (int64_t)n * s.stride_n_c + (int64_t)t * s.stride_t_c;
+    f.v = reinterpret_cast<const unsigned char*>(s.v) + (int64_t)n * s.stride_n_c + (int64_t)t * s.stride_t_c;
+    return f;
+}
+
+// Pixels [p0, min(p0 + 16, px_end)) of input row `row`; p0 is even and below px_end.
+__device__ __forceinline__ void yuv_load_group(Yuv16Group& g, const ptx_yuv420p16_src& s, const YuvFrame& f, int row, int p0,
+                                               int px_end) {
+    const unsigned char* yp = f.y + (size_t)row * s.pitch_y + (size_t)p0 * 2;
+    const size_t co = (size_t)(row >> 1) * s.pitch_c + (size_t)(p0 >> 1) * s.step_c;
+    const int rem = px_end - p0;
+    if (rem >= 16) {
+        g.y0 = *reinterpret_cast<const u32x4_any*>(yp);
+        g.y1 = *reinterpret_cast<const u32x4_any*>(yp + 16);
+        if (s.step_c == 4) {
+            const bool vu = f.v < f.u;                               // V first (P010 with swapped chroma)
+            const unsigned char* cp = (vu ? f.v : f.u) + co;
+            const u32x4 a = *reinterpret_cast<const u32x4_any*>(cp), b = *reinterpret_cast<const u32x4_any*>(cp + 16);
+            const u32x4 e = {__builtin_amdgcn_perm(a.y, a.x, 0x05040100u), __builtin_amdgcn_perm(a.w, a.z, 0x05040100u),
+                             __builtin_amdgcn_perm(b.y, b.x, 0x05040100u), __builtin_amdgcn_perm(b.w, b.z, 0x05040100u)};
+            const u32x4 o = {__builtin_amdgcn_perm(a.y, a.x, 0x07060302u), __builtin_amdgcn_perm(a.w, a.z, 0x07060302u),
+                             __builtin_amdgcn_perm(b.y, b.x, 0x07060302u), __builtin_amdgcn_perm(b.w, b.z, 0x07060302u)};
+            g.u = vu ? o : e;
+            g.v = vu ? e : o;
+        } else {
+            g.u = *reinterpret_cast<const u32x4_any*>(f.u + co);
+            g.v = *reinterpret_cast<const u32x4_any*>(f.v + co);
+        }
+    } else {
+        unsigned yy[8] = {0, 0, 0, 0, 0, 0, 0, 0}, uu[4] = {0, 0, 0, 0}, vv[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < rem) yy[k >> 1] |= (unsigned)*reinterpret_cast<const unsigned short*>(yp + 2 * k) << (16 * (k & 1));
+        const int nc = (rem + 1) >> 1;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k < nc) {
+                uu[k >> 1] |= (unsigned)*reinterpret_cast<const unsigned short*>(f.u + co + (size_t)k * s.step_c) << (16 * (k & 1));
+                vv[k >> 1] |= (unsigned)*reinterpret_cast<const unsigned short*>(f.v + co + (size_t)k * s.step_c) << (16 * (k & 1));
+            }
+        g.y0 = u32x4{yy[0], yy[1], yy[2], yy[3]};
+        g.y1 = u32x4{yy[4], yy[5], yy[6], yy[7]};
+        g.u = u32x4{uu[0], uu[1], uu[2], uu[3]};
+        g.v = u32x4{vv[0], vv[1], vv[2], vv[3]};
+    }
+}
+
+// Converts the group and writes its RGB bytes to dst exactly as the 8-bit yuv_stage_group does.
+__device__ __forceinline__ void yuv_stage_group(unsigned char* dst, const Yuv16Group& g, const ptx_yuv420p16_src& s, int rem) {
+    const unsigned yw[8] = {g.y0.x, g.y0.y, g.y0.z, g.y0.w, g.y1.x, g.y1.y, g.y1.z, g.y1.w};
+    const unsigned uw[4] = {g.u.x, g.u.y, g.u.z, g.u.w}, vw[4] = {g.v.x, g.v.y, g.v.z, g.v.w};
+    const unsigned mask = (1u << s.bits) - 1u;
+    const int d = s.bits - 8, mid = 128 << d, half = 1 << (15 + d), sh = 16 + d;
+    // a negative sum gives 0, as in yuv_clip8: clamp below, unsigned shift, min
+    auto clip = [&](int sum) { return min((unsigned)max(sum, 0) >> sh, 255u); };
+    unsigned o[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};          // 16 x RGB, byte 3 p + c of the group in word (3 p + c) / 4
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int cb = (int)((uw[k >> 1] >> (16 * (k & 1) + s.shift)) & mask) - mid;
+        const int cr = (int)((vw[k >> 1] >> (16 * (k & 1) + s.shift)) & mask) - mid;
+        const int rv = __mul24(s.krv, cr) + half;
+        const int gv = half - __mul24(s.kgu, cb) - __mul24(s.kgv, cr);
+        const int bv = __mul24(s.kbu, cb) + half;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int p = 2 * k + h;
+            const int yy = __mul24(s.ky, (int)((yw[k] >> (16 * h + s.shift)) & mask) - s.y_off);
+            o[(3 * p) >> 2] |= clip(yy + rv) << (8 * ((3 * p) & 3));
+            o[(3 * p + 1) >> 2] |= clip(yy + gv) << (8 * ((3 * p + 1) & 3));
+            o[(3 * p + 2) >> 2] |= clip(yy + bv) << (8 * ((3 * p + 2) & 3));
+        }
+    }
+    if (rem >= 16) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) *reinterpret_cast<u32x4*>(dst + 16 * q) = u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j)
+            if (4 * j < 3 * rem) *reinterpret_cast<unsigned*>(dst + 4 * j) = o[j];
+    }
+}
+
+// Lane l owns groups l, 64 + l, ... as in the 8-bit form; the first kYuv16Prefetch of them are prefetched.
+__device__ __forceinline__ void yuv_fetch_row(Yuv16Row& r, int i, int nrows, const ptx_yuv420p16_src& s, const YuvFrame& f,
+                                              int lo0, int cmin, int px_end, int lane) {
+    if (i >= nrows) return;
+    const int e0 = cmin & ~1;
+#pragma unroll
+    for (int k = 0; k < kYuv16Prefetch; ++k)
+        if (e0 + (64 * k + lane) * 16 < px_end) yuv_load_group(r.g[k], s, f, lo0 + i, e0 + (64 * k + lane) * 16, px_end);
+}
+
+__device__ __forceinline__ int yuv_stage_row(unsigned char* sw, const Yuv16Row& r, const ptx_yuv420p16_src& s, const YuvFrame& f,
+                                             int row, int cmin, int px_end, int lane) {
+    const int e0 = cmin & ~1;
+    int p0 = e0 + lane * 16;
+#pragma unroll
+    for (int k = 0; k < kYuv16Prefetch; ++k, p0 += 64 * 16)
+        if (p0 < px_end) yuv_stage_group(sw + (p0 - e0) * 3, r.g[k], s, px_end - p0);
+    for (; p0 < px_end; p0 += 64 * 16) {
+        Yuv16Group g;
+        yuv_load_group(g, s, f, row, p0, px_end);
+        yuv_stage_group(sw + (p0 - e0) * 3, g, s, px_end - p0);
+    }
+    return (cmin - e0) * 3;
+}
+
+// What a kernel of source flavour SRC takes: the descriptor, the per-clip row of the clips launch, the prefetched row.
+template <int SRC> struct YuvSource {
+    typedef ptx_yuv420_src Desc;
+    typedef ptx_clip_src_yuv420 Clip;
+    typedef YuvRow Row;
+};
+template <> struct YuvSource<kSrcYuv16> {
+    typedef ptx_yuv420p16_src Desc;
+    typedef ptx_clip_src_yuv420p16 Clip;
+    typedef Yuv16Row Row;
+};
+
+// Host-side checks of a ptx_yuv420p16_src for N x T frames of H x W pixels (no device needed): yuv_check's, in bytes.
+inline int yuv_check(const ptx_yuv420p16_src* s, int C, int H, int W, const char* who) {
+    if (!s) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    if (C != 3) return fail(PTX_ERR_INVALID, "%s: C=%d, a YUV source converts to 3 channels", who, C);
+    if (!s->y || !s->u || !s->v) return fail(PTX_ERR_INVALID, "%s: null plane pointer", who);
+    if (s->bits != 10 && s->bits != 12) return fail(PTX_ERR_INVALID, "%s: bits=%d must be 10 or 12", who, s->bits);
+    if (s->shift != 0 && s->shift != 16 - s->bits)
+        return fail(PTX_ERR_INVALID, "%s: shift=%d must be 0 (LSB-aligned) or %d (MSB-aligned %d-bit samples)", who, s->shift,
+                    16 - s->bits, s->bits);
+    if (s->pitch_y <= 0 || s->pitch_c <= 0)
+        return fail(PTX_ERR_INVALID, "%s: pitch_y=%d / pitch_c=%d must be positive", who, s->pitch_y, s->pitch_c);
+    if (s->step_c != 2 && s->step_c != 4) return fail(PTX_ERR_INVALID, "%s: step_c=%d must be 2 (planar) or 4 (interleaved)", who, s->step_c);
+    if (s->step_c == 4 && s->v != s->u + 1 && s->u != s->v + 1)
+        return fail(PTX_ERR_INVALID, "%s: interleaved chroma (step_c=4) needs v == u + 1 (or u == v + 1)", who);
+    if (((reinterpret_cast<uintptr_t>(s->y) | reinterpret_cast<uintptr_t>(s->u) | reinterpret_cast<uintptr_t>(s->v)) & 1) ||
+        ((s->pitch_y | s->pitch_c) & 1) || ((s->stride_n_y | s->stride_t_y | s->stride_n_c | s->stride_t_c) & 1))
+        return fail(PTX_ERR_INVALID, "%s: plane pointers, pitches and strides of 16-bit samples must be even", who);
+    const int64_t Hc = ((int64_t)H + 1) / 2, Wc = ((int64_t)W + 1) / 2;
+    if (s->pitch_y < (int64_t)W * 2 || s->pitch_c < Wc * s->step_c)
+        return fail(PTX_ERR_INVALID, "%s: pitch_y=%d / pitch_c=%d are shorter than a row (%lld luma, %lld chroma bytes)", who,
+                    s->pitch_y, s->pitch_c, (long long)W * 2, (long long)(Wc * s->step_c));
     if ((int64_t)H * s->pitch_y > INT32_MAX || Hc * s->pitch_c > INT32_MAX)
         return fail(PTX_ERR_UNSUPPORTED, "%s: a plane of a frame exceeds 32-bit indexing", who);
     return PTX_OK;

@@ -21,14 +21,15 @@ namespace ptx {
 
 constexpr int kViewsMinSharedBand = 4;      // below this the shared pass re-reads too many halo rows: one window per workgroup
 
-template <int C, bool YUV = false>
+template <int C, int SRC = kSrcRgb>
 __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, const unsigned char* __restrict__ f,
                                                               const int* __restrict__ frame_idx,
                                                               const int* __restrict__ row_lo, const int* __restrict__ row_n,
                                                               const int* __restrict__ row_k, const int* __restrict__ col_lo,
                                                               const int* __restrict__ col_n, const int* __restrict__ col_k,
                                                               void* __restrict__ y, ptx_norm_desc nd, ResizePlan pl, int shared,
-                                                              int clip0, int nclips, ptx_yuv420_src ys) {
+                                                              int clip0, int nclips, typename YuvSource<SRC>::Desc ys) {
+    constexpr bool YUV = SRC != kSrcRgb;         // the source flavour, as in resize_frames_u8_kernel
     extern __shared__ __attribute__((aligned(16))) unsigned char views_smem[];
     int* hdr = reinterpret_cast<int*>(views_smem);                  // [0] first, [1] one-past-last referenced column
     const int Rn = shared ? d.Ur : d.S, Cn = shared ? d.Uc : d.S;   // rows / columns this launch shape resamples per frame
@@ -133,7 +134,7 @@ __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, 
         // row's bytes already on their way in registers
         unsigned char* sw = stage + wave * pl.stage_stride;
         ResizeRow pre = {};
-        YuvRow ypre = {};
+        typename YuvSource<SRC>::Row ypre = {};
         if constexpr (YUV) yuv_fetch_row(ypre, 0 + wave, nrows, ys, yf, lo0, cmin, px_end, lane);
         else resize_fetch_row(pre, 0 + wave, nrows, fin, lo0, d.W, cmin, C, span_bytes, lane);
         for (int i0 = 0; i0 < nrows; i0 += 4) {
@@ -271,7 +272,7 @@ __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, 
 
 // Launch shape, or the reason there is none.  *shared: 1 = one workgroup per (frame, band of union rows), 0 = per window.
 static int views_plan(const ptx_views_desc* d, const void* y, ResizePlan* p, int* shared, const char* who,
-                      const ptx_yuv420_src* src = nullptr) {
+                      const ptx_yuv420_src* src = nullptr, const ptx_yuv420p16_src* src16 = nullptr) {
     if (!d) return fail(PTX_ERR_INVALID, "%s: null descriptor", who);
     if (d->N <= 0 || d->Tv <= 0 || d->H <= 0 || d->W <= 0 || d->S <= 0 || d->clips <= 0 || d->T <= 0)
         return fail(PTX_ERR_INVALID, "%s: non-positive extent (N=%d Tv=%d H=%d W=%d S=%d clips=%d T=%d)", who, d->N, d->Tv, d->H,
@@ -284,6 +285,8 @@ static int views_plan(const ptx_views_desc* d, const void* y, ResizePlan* p, int
     const int64_t frame_bytes = (int64_t)d->H * d->W * d->C;
     if (src) {                                                       // the source addresses its frames itself: d's strides are not read
         if (int s = yuv_check(src, d->C, d->H, d->W, who)) return s;
+    } else if (src16) {
+        if (int s = yuv_check(src16, d->C, d->H, d->W, who)) return s;
     } else if (d->stride_t < frame_bytes || d->stride_n < frame_bytes)
         return fail(PTX_ERR_INVALID, "%s: stride_t=%lld / stride_n=%lld are smaller than a frame (%lld bytes)", who,
                     (long long)d->stride_t, (long long)d->stride_n, (long long)frame_bytes);
@@ -339,16 +342,16 @@ extern "C" int ptx_resize_views_u8_supported(const ptx_views_desc* desc) {
     return shared ? 2 : 1;
 }
 
-// Both sources: `video` (interleaved uint8) or, when src is not null, the planes of a YUV 4:2:0 source.
+// All sources: `video` (interleaved uint8) or, when src / src16 is not null, the planes of a YUV 4:2:0 source.
 static int resize_views_run(const ptx_views_desc* desc, const uint8_t* video, const ptx_yuv420_src* src, const int32_t* frame_idx,
                             const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k, const int32_t* col_lo,
                             const int32_t* col_n, const int32_t* col_k, void* y, const ptx_norm_desc* norm, ptx_stream_t stream,
-                            const char* who) {
+                            const char* who, const ptx_yuv420p16_src* src16 = nullptr) {
     ResizePlan p;
     int shared;
-    int s = views_plan(desc, y, &p, &shared, who, src);
+    int s = views_plan(desc, y, &p, &shared, who, src, src16);
     if (s) return s;
-    if ((!video && !src) || !frame_idx || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k)
+    if ((!video && !src && !src16) || !frame_idx || !y || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k)
         return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     ptx_norm_desc nd = {};
     if (desc->out_mode != PTX_RESIZE_OUT_U8) {
@@ -365,8 +368,13 @@ static int resize_views_run(const ptx_views_desc* desc, const uint8_t* video, co
 #define PTX_VIEWS_LAUNCH(CH)                                                                                                \
     hipLaunchKernelGGL(resize_views_u8_kernel<CH>, grid, dim3(256), p.lds_bytes, st, *desc, video, frame_idx, row_lo, row_n, \
                        row_k, col_lo, col_n, col_k, y, nd, p, shared, clip0, nclips, ptx_yuv420_src{})
+    if (src16) {
+        hipLaunchKernelGGL((resize_views_u8_kernel<3, kSrcYuv16>), grid, dim3(256), p.lds_bytes, st, *desc, (const unsigned char*)nullptr,
+                           frame_idx, row_lo, row_n, row_k, col_lo, col_n, col_k, y, nd, p, shared, clip0, nclips, *src16);
+        return hip_check(hipGetLastError(), who);
+    }
     if (src) {
-        hipLaunchKernelGGL((resize_views_u8_kernel<3, true>), grid, dim3(256), p.lds_bytes, st, *desc, (const unsigned char*)nullptr, frame_idx, row_lo,
+        hipLaunchKernelGGL((resize_views_u8_kernel<3, kSrcYuv8>), grid, dim3(256), p.lds_bytes, st, *desc, (const unsigned char*)nullptr, frame_idx, row_lo,
                            row_n, row_k, col_lo, col_n, col_k, y, nd, p, shared, clip0, nclips, *src);
         return hip_check(hipGetLastError(), who);
     }
@@ -404,4 +412,23 @@ extern "C" int ptx_resize_views_yuv420(const ptx_views_desc* desc, const ptx_yuv
     const char* who = "ptx_resize_views_yuv420";
     if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
     return resize_views_run(desc, nullptr, src, frame_idx, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who);
+}
+
+// The same on a 10- / 12-bit source (include/ptx_amd_yuv16.h).
+extern "C" int ptx_resize_views_yuv420p16_supported(const ptx_views_desc* desc, const ptx_yuv420p16_src* src) {
+    const char* who = "ptx_resize_views_yuv420p16_supported";
+    ResizePlan p;
+    int shared;
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who), 0;
+    if (views_plan(desc, nullptr, &p, &shared, who, nullptr, src) != PTX_OK) return 0;
+    return shared ? 2 : 1;
+}
+
+extern "C" int ptx_resize_views_yuv420p16(const ptx_views_desc* desc, const ptx_yuv420p16_src* src, const int32_t* frame_idx,
+                                          const int32_t* row_lo, const int32_t* row_n, const int32_t* row_k,
+                                          const int32_t* col_lo, const int32_t* col_n, const int32_t* col_k, void* y,
+                                          const ptx_norm_desc* norm, ptx_stream_t stream) {
+    const char* who = "ptx_resize_views_yuv420p16";
+    if (!src) return fail(PTX_ERR_INVALID, "%s: null source descriptor", who);
+    return resize_views_run(desc, nullptr, nullptr, frame_idx, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, src);
 }

@@ -190,6 +190,70 @@ def yuv420_source(planes, layout, device, matrix="bt709", color_range="limited",
     raise ValueError("yuv420_source: unknown layout %r" % (layout,))
 
 
+def synth_yuv420p16(count, height, width, seed, bits=10, align="msb", content="noise"):
+    """Synthetic 10- / 12-bit decoder output: uint16 numpy planes shaped as `synth_yuv420`'s, the sample MSB- or
+    LSB-aligned in its word and seeded garbage in the bits the contract ignores (the low 16 - bits of an "msb" word, the
+    high ones of an "lsb" word).  "noise": seeded samples over the whole range in all three planes; "extremes": constant
+    frames cycling through (Y, Cb, Cr) = all ones, all zeros and limited-range (16, 240, 16) << (bits - 8)."""
+    import numpy as np
+    hc, wc = (height + 1) // 2, (width + 1) // 2
+    top, d = (1 << bits) - 1, bits - 8
+    shapes = ((count, height, width), (count, hc, wc), (count, hc, wc))
+    rs = np.random.RandomState(int(seed))
+    if content == "extremes":
+        triples = [(top, top, top), (0, 0, 0), (16 << d, 240 << d, 16 << d)]
+        planes = [np.stack([np.full(shape[1:], triples[i % 3][k], np.int64) for i in range(count)]) for k, shape in enumerate(shapes)]
+    elif content == "noise":
+        planes = [rs.randint(0, top + 1, shape).astype(np.int64) for shape in shapes]
+    else:
+        raise ValueError("synth_yuv420p16: content must be 'noise' or 'extremes'")
+    out = []
+    for p in planes:
+        junk = rs.randint(0, 1 << (16 - bits), p.shape).astype(np.int64)
+        out.append(((p << (16 - bits)) | junk if align == "msb" else p | (junk << bits)).astype(np.uint16))
+    return tuple(out)
+
+
+def yuv420p16_source(planes, layout, device, bits=10, align="msb", matrix="bt709", color_range="limited", lead_shape=None):
+    """A `transforms.YUV420P16` over numpy planes (as `synth_yuv420p16` returns them) in one of the memory layouts a
+    decoder produces: "p010" (packed, interleaved chroma, MSB-aligned words, even sizes), "i420p16" (packed planar,
+    LSB-aligned words, even sizes), "planes" (y, u, v tensors), "planes_uv" (y and an interleaved uv plane), "p010_pitched"
+    (y and uv are views into wider buffers: row pitch 2 * (W + 7) / 2 * (2 * ceil(W/2) + 3) bytes, base pointers 2 and 6
+    bytes past the allocation).  align must be what the packed layouts imply; lead_shape: reshape the leading [count] to it."""
+    import numpy as np
+    import torch
+    from .transforms import YUV420P16
+    y, u, v = (np.ascontiguousarray(a).view(np.int16) for a in planes)
+    count, H, W = y.shape
+    hc, wc = u.shape[1:]
+    lead = (count,) if lead_shape is None else tuple(lead_shape)
+    kw = dict(matrix=matrix, color_range=color_range)
+    uv = np.stack([u, v], -1)                                       # [count, hc, wc, 2]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    implied = {"p010": "msb", "p010_pitched": "msb", "i420p16": "lsb"}.get(layout, align)
+    if implied != align:
+        raise ValueError("yuv420p16_source: layout %r holds %s-aligned samples" % (layout, implied))
+    if layout == "p010":
+        return YUV420P16.from_p010(dev(np.concatenate([y, uv.reshape(count, hc, W)], 1)).view(lead + (H * 3 // 2, W)), bits, **kw)
+    if layout == "i420p16":
+        packed = np.concatenate([y.reshape(count, -1), u.reshape(count, -1), v.reshape(count, -1)], 1)
+        return YUV420P16.from_i420p16(dev(packed).view(lead + (H * 3 // 2, W)), bits, **kw)
+    if layout == "planes":
+        return YUV420P16(dev(y).view(lead + (H, W)), dev(u).view(lead + (hc, wc)), dev(v).view(lead + (hc, wc)), bits, align, **kw)
+    if layout == "planes_uv":
+        return YUV420P16(dev(y).view(lead + (H, W)), dev(uv).view(lead + (hc, wc, 2)), None, bits, align, **kw)
+    if layout == "p010_pitched":
+        py, pc = W + 7, 2 * wc + 3                                   # words: 2 W + 14 and 4 wc + 6 bytes, no multiple of 16
+        by = torch.zeros(count * H * py + 1, dtype=torch.int16, device=device)
+        bc = torch.zeros(count * hc * pc + 3, dtype=torch.int16, device=device)
+        ty = by[1:].view(lead + (H, py))[..., :W]
+        tc = bc[3:].view(lead + (hc, pc))[..., :2 * wc].unflatten(-1, (wc, 2))
+        ty.copy_(dev(y).view(lead + (H, W)))
+        tc.copy_(dev(uv).view(lead + (hc, wc, 2)))
+        return YUV420P16(ty, tc, None, bits, "msb", **kw)
+    raise ValueError("yuv420p16_source: unknown layout %r" % (layout,))
+
+
 def synth_frames(count, height, width, seed, content="noise"):
     """Synthetic decoded frames, uint8 numpy [count, height, width, 3]: seeded noise from numpy's legacy generator (its
     stream is stable across numpy versions, so fixtures store outputs only) or a smooth integer gradient."""

@@ -33,7 +33,8 @@ uint8 frames:
 * `YUV420` describes decoder output (NV12 / I420 planes, any row pitch) and is accepted wherever RGB frames are:
   the two resize kernels convert to RGB while they stage an input row on chip (`yuv_coefficients` is the integer
   contract, `yuv420_to_rgb_numpy` its numpy statement), so the RGB frame never exists in HBM and every output bit
-  is that of the RGB path on the converted frames.
+  is that of the RGB path on the converted frames.  `YUV420P16` is the same for 10- and 12-bit streams (P010 / P012 /
+  P016 surfaces, yuv420p10le / yuv420p12le planes; `yuv_coefficients_p16`, `yuv420p16_to_rgb_numpy`).
 
 Image loading and video decoding stay host work and are not on this path.
 """
@@ -45,7 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ClipSrc, ClipSrcYuv420, NormDesc, PtxError, ResizeDesc, ViewsDesc, Yuv420Src, check
+from ._lib import ClipSrc, ClipSrcYuv420, ClipSrcYuv420P16, NormDesc, PtxError, ResizeDesc, ViewsDesc, Yuv420P16Src, Yuv420Src, check
 
 PRECISION_BITS = 22       # PIL's fixed-point coefficient precision for 8-bit channels (32 - 8 - 2)
 
@@ -138,24 +139,36 @@ class YUV420:
     their rows are contiguous runs (a uv plane: last strides (2, 1)) -- row pitch, frame and video strides and base
     alignment are arbitrary --, anything else costs one `.contiguous()` copy of that plane at the call."""
 
+    # what YUV420P16 (16-bit words) replaces: the name in messages, the entry points' infix, the descriptors, bytes per sample
+    _NAME = "YUV420"
+    _ABI = "yuv420"
+    _SRC, _CLIP_SRC = Yuv420Src, ClipSrcYuv420
+    _ITEM = 1
+
     def __init__(self, y, u, v=None, matrix="bt709", color_range="limited"):
-        self.coefficients = yuv_coefficients(matrix, color_range)
-        self.matrix, self.color_range = matrix, color_range
-        planes = (y, u) if v is None else (y, u, v)
-        for p in planes:
+        coefficients = yuv_coefficients(matrix, color_range)
+        for p in (y, u) if v is None else (y, u, v):
             if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8:
                 raise PtxError("YUV420: planes must be uint8 tensors, got %s" % (
                     p.dtype if isinstance(p, torch.Tensor) else type(p).__name__,))
+        self._init_planes(y, u, v, matrix, color_range, coefficients)
+
+    def _init_planes(self, y, u, v, matrix, color_range, coefficients):
+        """The checks and attributes that do not depend on the sample type."""
+        name = self._NAME
+        self.coefficients = coefficients
+        self.matrix, self.color_range = matrix, color_range
+        planes = (y, u) if v is None else (y, u, v)
         if len({p.device for p in planes}) != 1:
-            raise PtxError("YUV420: planes are on different devices (%s)" % ", ".join(str(p.device) for p in planes))
+            raise PtxError("%s: planes are on different devices (%s)" % (name, ", ".join(str(p.device) for p in planes)))
         if y.dim() not in (2, 3, 4):
-            raise PtxError("YUV420: expected a luma plane [N,T,H,W], [T,H,W] or [H,W], got shape %s" % (tuple(y.shape),))
+            raise PtxError("%s: expected a luma plane [N,T,H,W], [T,H,W] or [H,W], got shape %s" % (name, tuple(y.shape)))
         H, W = int(y.shape[-2]), int(y.shape[-1])
         want = tuple(y.shape[:-2]) + ((H + 1) // 2, (W + 1) // 2)
-        for name, p in (("uv", u),) if v is None else (("u", u), ("v", v)):
+        for pname, p in (("uv", u),) if v is None else (("u", u), ("v", v)):
             if tuple(p.shape) != want + ((2,) if v is None else ()):
-                raise PtxError("YUV420: the %s plane has shape %s, a %dx%d luma plane of shape %s needs %s (ceil(H/2) x "
-                               "ceil(W/2) samples)" % (name, tuple(p.shape), H, W, tuple(y.shape),
+                raise PtxError("%s: the %s plane has shape %s, a %dx%d luma plane of shape %s needs %s (ceil(H/2) x "
+                               "ceil(W/2) samples)" % (name, pname, tuple(p.shape), H, W, tuple(y.shape),
                                                        want + ((2,) if v is None else ())))
         self.y, self.u, self.v = y, u, v                            # v is None: u holds the interleaved pairs
         self.H, self.W, self.lead, self.device = H, W, y.dim() - 1, y.device
@@ -163,17 +176,18 @@ class YUV420:
         self.T = int(y.shape[-3]) if y.dim() >= 3 else 1
         self.lead_shape = tuple(y.shape[:-2])
 
-    @staticmethod
-    def _packed(packed, who):
-        if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
-            raise PtxError("YUV420.%s: packed frames must be a uint8 tensor" % who)
+    @classmethod
+    def _packed(cls, packed, who):
+        name, wide = cls._NAME, cls._ITEM == 2
+        if not isinstance(packed, torch.Tensor) or packed.dtype not in ((torch.int16, torch.uint16) if wide else (torch.uint8,)):
+            raise PtxError("%s.%s: packed frames must be %s tensor" % (name, who, "an int16 / uint16" if wide else "a uint8"))
         if packed.dim() not in (2, 3, 4):
-            raise PtxError("YUV420.%s: expected [N,T,H*3/2,W], [T,H*3/2,W] or [H*3/2,W], got shape %s" % (who, tuple(packed.shape)))
+            raise PtxError("%s.%s: expected [N,T,H*3/2,W], [T,H*3/2,W] or [H*3/2,W], got shape %s" % (name, who, tuple(packed.shape)))
         rows, W = int(packed.shape[-2]), int(packed.shape[-1])
         H = rows * 2 // 3
         if rows % 3 or H % 2 or W % 2 or H == 0 or W == 0:
-            raise PtxError("YUV420.%s: a packed frame is H*3/2 rows of W bytes with even H and W, got %d rows of %d (pass "
-                           "planes for odd sizes)" % (who, rows, W))
+            raise PtxError("%s.%s: a packed frame is H*3/2 rows of W %s with even H and W, got %d rows of %d (pass "
+                           "planes for odd sizes)" % (name, who, "words" if wide else "bytes", rows, W))
         return H, W
 
     @classmethod
@@ -204,10 +218,16 @@ class YUV420:
             return False
         return p.shape[-1 - k] == 1 or p.stride(-1 - k) >= run
 
+    def _like(self, y, u, v):
+        """A source over other planes with this one's colour parameters."""
+        return YUV420(y, u, v, self.matrix, self.color_range)
+
     def source(self, who="YUV420"):
-        """(Yuv420Src, tensors to keep alive): the kernels' descriptor of the planes, checked and copied where needed."""
+        """(Yuv420Src, tensors to keep alive): the kernels' descriptor of the planes, checked and copied where needed.
+        Pointers, strides and pitches are in bytes (`_ITEM` per sample)."""
         if self.device.type != "cuda":
-            raise PtxError("%s: the planes of a YUV420 source must be uint8 CUDA tensors (no CPU fallback)" % who)
+            raise PtxError("%s: the planes of a %s source must be %s CUDA tensors (no CPU fallback)" % (
+                who, self._NAME, "uint8" if self._ITEM == 1 else "int16 / uint16"))
         if self.N * self.T == 0 or self.H * self.W == 0:
             raise PtxError("%s: empty batch" % who)
         Hc, Wc = (self.H + 1) // 2, (self.W + 1) // 2
@@ -215,7 +235,7 @@ class YUV420:
         if self.v is None:
             u = self.u if self._rows_in_place(self.u, (Wc, 2)) else self.u.contiguous()
             c, keep = u.select(-1, 0), (y, u)
-            pu, pv, step, pitch_c = u.data_ptr(), u.data_ptr() + 1, 2, (u.stride(-3) if Hc > 1 else 2 * Wc)
+            pu, pv, step, pitch_c = u.data_ptr(), u.data_ptr() + self._ITEM, 2, (u.stride(-3) if Hc > 1 else 2 * Wc)
         else:
             u, v = self.u, self.v
             if not (self._rows_in_place(u, (Wc,)) and self._rows_in_place(v, (Wc,)) and
@@ -230,11 +250,12 @@ class YUV420:
             sn = p.stride(lead - 2) if lead >= 2 and p.shape[lead - 2] > 1 else 0
             return sn, st
 
-        s = Yuv420Src()
+        b = self._ITEM                                              # element strides -> bytes
+        s = self._SRC()
         s.y, s.u, s.v = y.data_ptr(), pu, pv
-        s.stride_n_y, s.stride_t_y = strides(y, 2)
-        s.stride_n_c, s.stride_t_c = strides(c, 2)
-        s.pitch_y, s.pitch_c, s.step_c = (y.stride(-2) if self.H > 1 else self.W), pitch_c, step
+        s.stride_n_y, s.stride_t_y = (b * n for n in strides(y, 2))
+        s.stride_n_c, s.stride_t_c = (b * n for n in strides(c, 2))
+        s.pitch_y, s.pitch_c, s.step_c = b * (y.stride(-2) if self.H > 1 else self.W), b * pitch_c, b * step
         s.y_off, s.ky, s.krv, s.kgu, s.kgv, s.kbu = self.coefficients
         return s, keep
 
@@ -245,6 +266,141 @@ class YUV420:
         else:
             u, v = self.u, self.v
         return yuv420_to_rgb_numpy(self.y.cpu().numpy(), u.cpu().numpy(), v.cpu().numpy(), self.matrix, self.color_range)
+
+
+# ---------------------------------------------------------------------------------------------
+# 10- and 12-bit YUV 4:2:0 sources: 16-bit words, the sample MSB-aligned (P010 / P012 / P016 surfaces of the hardware
+# decoders) or LSB-aligned (yuv420p10le / yuv420p12le of the software decoders).  The contract is the 8-bit one with
+# d = bits - 8 more bits in the samples and in the final shift, and the H.273 scales of the depth.
+# ---------------------------------------------------------------------------------------------
+_YUV_MATRICES_P16 = dict(_YUV_MATRICES, bt2020=(0.2627, 0.0593))                  # + BT.2020 non-constant luminance
+
+
+def _yuv16_args(who, bits, align=None):
+    if bits not in (10, 12):
+        raise PtxError("%s: bits must be 10 or 12, got %r" % (who, bits))
+    if align not in (None, "msb", "lsb"):
+        raise PtxError("%s: align must be 'msb' (P010 / P012 / P016) or 'lsb' (yuv420p10le / yuv420p12le), got %r" % (who, align))
+    return 0 if align == "lsb" else 16 - bits
+
+
+def yuv_coefficients_p16(matrix="bt709", color_range="limited", bits=10):
+    """(y_off, ky, krv, kgu, kgv, kbu) for `bits`-bit samples (10 or 12; d = bits - 8): 2**16 fixed point, rounded once
+    from float64 as `yuv_coefficients` does, for
+        R = clip8((ky*y' + krv*cr + 2**(15+d)) >> (16+d))     G = clip8((ky*y' - kgu*cb - kgv*cr + 2**(15+d)) >> (16+d))
+        B = clip8((ky*y' + kbu*cb + 2**(15+d)) >> (16+d))     y' = Y - y_off, cb = Cb - (128 << d), cr = Cr - (128 << d).
+    Scales of H.273: limited range luma 255/219, chroma 255/224, y_off = 16 << d (the 8-bit coefficients); full range
+    both 255 * 2**d / (2**bits - 1), y_off = 0.  matrix: "bt601" | "bt709" | "bt2020" (non-constant luminance)."""
+    if matrix not in _YUV_MATRICES_P16:
+        raise PtxError("YUV420P16: matrix must be 'bt601', 'bt709' or 'bt2020', got %r" % (matrix,))
+    if color_range not in _YUV_RANGES:
+        raise PtxError("YUV420P16: color_range must be 'limited' or 'full', got %r" % (color_range,))
+    _yuv16_args("YUV420P16", bits)
+    d = bits - 8
+    kr, kb = _YUV_MATRICES_P16[matrix]
+    kg = 1.0 - kr - kb
+    if color_range == "limited":
+        sy, sc, y_off = 255.0 / 219.0, 255.0 / 224.0, 16 << d
+    else:
+        sy = sc = 255.0 * float(1 << d) / float((1 << bits) - 1)
+        y_off = 0
+    q = lambda v: int(round(v * float(1 << YUV_BITS)))
+    return (y_off, q(sy), q(2.0 * (1.0 - kr) * sc), q(2.0 * kb * (1.0 - kb) / kg * sc), q(2.0 * kr * (1.0 - kr) / kg * sc),
+            q(2.0 * (1.0 - kb) * sc))
+
+
+def yuv420p16_to_rgb_numpy(y, u, v, bits=10, align="msb", matrix="bt709", color_range="limited"):
+    """The kernels' colour conversion of 10- / 12-bit samples in numpy: 16-bit planes (uint16, or int16 read unsigned)
+    y [..,H,W], u, v [..,ceil(H/2),ceil(W/2)] -> uint8 [..,H,W,3].  A sample is (word >> shift) & (2**bits - 1) with
+    shift = 16 - bits for align="msb" and 0 for "lsb"; the chroma sample of pixel (r, c) is (r >> 1, c >> 1).  The
+    host-side model the tests compare with; not a fallback."""
+    shift = _yuv16_args("yuv420p16_to_rgb_numpy", bits, align)
+    y_off, ky, krv, kgu, kgv, kbu = yuv_coefficients_p16(matrix, color_range, bits)
+    y, u, v = (np.asarray(a) for a in (y, u, v))
+    for a in (y, u, v):
+        if a.dtype not in (np.uint16, np.int16):
+            raise PtxError("yuv420p16_to_rgb_numpy: planes must be uint16 (or int16) arrays, got %s" % a.dtype)
+    H, W = y.shape[-2:]
+    if u.shape != v.shape or u.shape[-2:] != ((H + 1) // 2, (W + 1) // 2) or u.shape[:-2] != y.shape[:-2]:
+        raise PtxError("yuv420p16_to_rgb_numpy: chroma planes %s / %s do not match the %dx%d luma plane" % (u.shape, v.shape, H, W))
+    d, mask = bits - 8, (1 << bits) - 1
+    sample = lambda a: (a.view(np.uint16).astype(np.int64) >> shift) & mask
+    rows, cols = np.arange(H) >> 1, np.arange(W) >> 1
+    yy = ky * (sample(y) - y_off)
+    cb = sample(u)[..., rows, :][..., cols] - (128 << d)
+    cr = sample(v)[..., rows, :][..., cols] - (128 << d)
+    half, sh = 1 << (YUV_BITS - 1 + d), YUV_BITS + d
+    rgb = np.stack([(yy + krv * cr + half) >> sh, (yy - kgu * cb - kgv * cr + half) >> sh, (yy + kbu * cb + half) >> sh], -1)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+class YUV420P16(YUV420):
+    """Decoded 10- or 12-bit YUV 4:2:0 frames in 16-bit words, accepted wherever `YUV420` is:
+
+        YUV420P16(y, uv, ...)     y [..,H,W], uv [..,ceil(H/2),ceil(W/2),2]       (P010 / P016 surfaces, any row pitch)
+        YUV420P16(y, u, v, ...)   u, v [..,ceil(H/2),ceil(W/2)]                    (planar)
+        YUV420P16.from_p010(packed, bits=10, ...)       packed [..,H*3/2,W] words, MSB-aligned (bits=12: P012 / P016)
+        YUV420P16.from_i420p16(packed, bits, ...)       packed [..,H*3/2,W] words, planar, LSB-aligned (yuv420p10le / p12le)
+
+    Planes are `torch.int16` or `torch.uint16` tensors (the same bits, read unsigned) with 0, 1 or 2 leading dimensions.
+    bits: 10 | 12; align: "msb" (the sample in the high bits, the low 16 - bits ignored whatever they hold) | "lsb" (the
+    sample in the low bits, the high bits masked); matrix: "bt709" | "bt601" | "bt2020"; color_range: "limited" | "full"
+    (see `yuv_coefficients_p16`).  The output is 8-bit RGB; transfer functions are not touched, so PQ / HLG content
+    comes out as PQ / HLG-coded RGB.  Planes are read in place when their rows are contiguous runs, as `YUV420`'s."""
+
+    _NAME = "YUV420P16"
+    _ABI = "yuv420p16"
+    _SRC, _CLIP_SRC = Yuv420P16Src, ClipSrcYuv420P16
+    _ITEM = 2
+
+    def __init__(self, y, u, v=None, bits=10, align="msb", matrix="bt709", color_range="limited"):
+        coefficients = yuv_coefficients_p16(matrix, color_range, bits)
+        self.bits, self.align, self.shift = bits, align, _yuv16_args("YUV420P16", bits, align)
+        planes = (y, u) if v is None else (y, u, v)
+        for p in planes:
+            if isinstance(p, torch.Tensor) and p.dtype == torch.uint8:
+                raise PtxError("YUV420P16: planes must be int16 / uint16 tensors of 10- or 12-bit samples, got torch.uint8 "
+                               "(8-bit planes are a YUV420 source)")
+            if not isinstance(p, torch.Tensor) or p.dtype not in (torch.int16, torch.uint16):
+                raise PtxError("YUV420P16: planes must be int16 / uint16 tensors, got %s" % (
+                    p.dtype if isinstance(p, torch.Tensor) else type(p).__name__,))
+        y, u, v = (p if p is None or p.dtype == torch.int16 else p.view(torch.int16) for p in (y, u, v))   # the same bits
+        self._init_planes(y, u, v, matrix, color_range, coefficients)
+
+    @classmethod
+    def from_p010(cls, packed, bits=10, matrix="bt709", color_range="limited"):
+        """Packed P010 (bits=12: P012 / P016) [..,H*3/2,W] words: H rows of luma, then H/2 rows of interleaved Cb Cr
+        pairs, samples MSB-aligned.  Views, no copy."""
+        H, W = cls._packed(packed, "from_p010")
+        return cls(packed[..., :H, :], packed[..., H:, :].unflatten(-1, (W // 2, 2)), None, bits, "msb", matrix, color_range)
+
+    @classmethod
+    def from_i420p16(cls, packed, bits, matrix="bt709", color_range="limited"):
+        """Packed yuv420p10le / yuv420p12le [..,H*3/2,W] words: the luma plane, then the Cb plane, then the Cr plane (H/2 x
+        W/2 each, as flat runs), samples LSB-aligned.  Views when each packed frame is contiguous."""
+        H, W = cls._packed(packed, "from_i420p16")
+        flat = packed.reshape(tuple(packed.shape[:-2]) + (H * 3 // 2 * W,))
+        q = (H // 2) * (W // 2)
+        return cls(flat[..., :H * W].unflatten(-1, (H, W)), flat[..., H * W:H * W + q].unflatten(-1, (H // 2, W // 2)),
+                   flat[..., H * W + q:].unflatten(-1, (H // 2, W // 2)), bits, "lsb", matrix, color_range)
+
+    def _like(self, y, u, v):
+        return YUV420P16(y, u, v, self.bits, self.align, self.matrix, self.color_range)
+
+    def source(self, who="YUV420P16"):
+        """(Yuv420P16Src, tensors to keep alive): the kernels' descriptor of the planes, checked and copied where needed."""
+        s, keep = super().source(who)
+        s.bits, s.shift = self.bits, self.shift
+        return s, keep
+
+    def to_rgb_numpy(self):
+        """uint8 [..,H,W,3] through `yuv420p16_to_rgb_numpy` (host; tests and examples)."""
+        if self.v is None:
+            u, v = self.u[..., 0], self.u[..., 1]
+        else:
+            u, v = self.u, self.v
+        return yuv420p16_to_rgb_numpy(self.y.cpu().numpy(), u.cpu().numpy(), v.cpu().numpy(), self.bits, self.align,
+                                      self.matrix, self.color_range)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -795,7 +951,7 @@ class TransformFrames:
                 y = torch.empty((N, 3, T, S, S), device=device, dtype=self.dtype)
             desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
             base = buf.data_ptr()
-            name = "ptx_resize_frames_u8_windows" if ysrc is None else "ptx_resize_frames_yuv420_windows"
+            name = "ptx_resize_frames_%s_windows" % ("u8" if ysrc is None else _abi_of(ysrc))
             source = C.c_void_p(f5.data_ptr()) if ysrc is None else C.byref(ysrc)
             check(getattr(_lib.lib(), name)(C.byref(desc), source, *[C.c_void_p(base + o) for o in offs], h, w,
                                             C.c_void_p(wins.data_ptr()), C.c_void_p(y.data_ptr()), C.byref(self.norm),
@@ -825,7 +981,7 @@ class TransformFrames:
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             check(_lib.lib().ptx_resize_build_tables(C.byref(desc), C.c_void_p(geo.data_ptr()), *tabs, stream),
                   "ptx_resize_build_tables")
-            name = "ptx_resize_frames_u8_tables" if ysrc is None else "ptx_resize_frames_yuv420_tables"
+            name = "ptx_resize_frames_%s_tables" % ("u8" if ysrc is None else _abi_of(ysrc))
             source = C.c_void_p(f5.data_ptr()) if ysrc is None else C.byref(ysrc)
             check(getattr(_lib.lib(), name)(C.byref(desc), source, *tabs, C.c_void_p(y.data_ptr()), C.byref(self.norm), stream),
                   name)
@@ -856,10 +1012,10 @@ class TransformFrames:
                 y = torch.empty((N, 3, T, S, S), device=src.device, dtype=self.dtype)
             desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
             base = buf.data_ptr()
-            check(_lib.lib().ptx_resize_frames_yuv420(C.byref(desc), C.byref(ysrc), *[C.c_void_p(base + o) for o in offs],
-                                                      C.c_void_p(y.data_ptr()), C.byref(self.norm),
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                  "ptx_resize_frames_yuv420")
+            name = "ptx_resize_frames_" + src._ABI
+            check(getattr(_lib.lib(), name)(C.byref(desc), C.byref(ysrc), *[C.c_void_p(base + o) for o in offs],
+                                            C.c_void_p(y.data_ptr()), C.byref(self.norm),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
             del keep                                                 # planes (copies included) stayed alive up to the launch
         if self.out == "frames":
             return y.view(src.lead_shape + (S, S, 3))
@@ -868,14 +1024,20 @@ class TransformFrames:
         return y[0] if src.lead == 2 else y[0, :, 0]
 
 
+def _abi_of(ysrc):
+    """The entry points' infix for a source descriptor: "yuv420" or "yuv420p16"."""
+    return YUV420P16._ABI if isinstance(ysrc, Yuv420P16Src) else YUV420._ABI
+
+
 def apply_frames_transform(transform, frames, who="forward_frames"):
     """The `transform=` hook of forward_frames: a TransformFrames with out="frames", applied to the raw frames, or a
     SampleClips with out="frames", applied to the raw videos (a list of any sizes and lengths).  A `YUV420` source has no
     RGB frames to pass on, so it needs one (a crop-only transform serves frames of the input size)."""
     if transform is None:
         if isinstance(frames, YUV420):
-            raise PtxError("%s: a YUV420 source needs transform=TransformFrames(.., out='frames') (the colour conversion "
-                           "runs in its row staging; a crop-only transform serves frames that have the input size)" % who)
+            raise PtxError("%s: a %s source needs transform=TransformFrames(.., out='frames') (the colour conversion "
+                           "runs in its row staging; a crop-only transform serves frames that have the input size)" % (
+                               who, frames._NAME))
         return frames
     if not isinstance(transform, (TransformFrames, SampleClips)) or transform.out != "frames":
         raise PtxError("%s: transform must be a pretorched.transforms.TransformFrames with out='frames', got %r" % (
@@ -1111,7 +1273,7 @@ class SampleViews:
 
     def _sample_yuv(self, src, v0, nv):
         if src.lead not in (2, 3):
-            raise PtxError("SampleViews: expected a YUV420 video with planes [N,Tv,H,W] or [Tv,H,W], got one frame")
+            raise PtxError("SampleViews: expected a %s video with planes [N,Tv,H,W] or [Tv,H,W], got one frame" % src._NAME)
         ysrc, keep = src.source("SampleViews")
         N, Tv, H, W = src.N, src.T, src.H, src.W
         V = self.num_views
@@ -1128,11 +1290,11 @@ class SampleViews:
                 y = torch.empty((N, nv, 3, T, S, S), device=src.device, dtype=self.dtype)
             desc = self._desc(N, Tv, H, W, 3, 0, 0, t, v0, nv)         # the source carries the frame strides
             base = buf.data_ptr()
-            check(_lib.lib().ptx_resize_views_yuv420(C.byref(desc), C.byref(ysrc), C.c_void_p(idx.data_ptr()),
-                                                     *[C.c_void_p(base + o) for o in offs],
-                                                     C.c_void_p(y.data_ptr()), C.byref(self.norm),
-                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                  "ptx_resize_views_yuv420")
+            name = "ptx_resize_views_" + src._ABI
+            check(getattr(_lib.lib(), name)(C.byref(desc), C.byref(ysrc), C.c_void_p(idx.data_ptr()),
+                                            *[C.c_void_p(base + o) for o in offs],
+                                            C.c_void_p(y.data_ptr()), C.byref(self.norm),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
             del keep
         return y if src.lead == 3 else y[0]
 
@@ -1282,11 +1444,10 @@ class SampleClips:
         the host."""
         if isinstance(videos, YUV420):
             if videos.lead == 3:
-                return [YUV420(videos.y[n], videos.u[n], None if videos.v is None else videos.v[n], videos.matrix,
-                               videos.color_range) for n in range(videos.N)]
+                return [videos._like(videos.y[n], videos.u[n], None if videos.v is None else videos.v[n]) for n in range(videos.N)]
             if videos.lead != 2:
-                raise PtxError("SampleClips: expected a YUV420 source with planes [N,Tv,H,W] or [Tv,H,W], got %d leading "
-                               "dimension(s)" % (videos.lead - 1))
+                raise PtxError("SampleClips: expected a %s source with planes [N,Tv,H,W] or [Tv,H,W], got %d leading "
+                               "dimension(s)" % (videos._NAME, videos.lead - 1))
             return [videos]
         if isinstance(videos, torch.Tensor):
             if videos.dim() not in (4, 5):
@@ -1305,9 +1466,12 @@ class SampleClips:
             if yuv != isinstance(v, YUV420):
                 raise PtxError("SampleClips: videos[%d]: a batch is all tensors or all YUV420 sources" % i)
             if yuv:
+                if type(v) is not type(videos[0]):
+                    raise PtxError("SampleClips: videos[%d] is a %s source, videos[0] a %s: a batch is all of one source kind" % (
+                        i, v._NAME, videos[0]._NAME))
                 if v.lead != 2:
-                    raise PtxError("SampleClips: videos[%d]: expected a YUV420 source with planes [Tv,H,W], got %d leading "
-                                   "dimension(s)" % (i, v.lead - 1))
+                    raise PtxError("SampleClips: videos[%d]: expected a %s source with planes [Tv,H,W], got %d leading "
+                                   "dimension(s)" % (i, v._NAME, v.lead - 1))
                 continue
             if not isinstance(v, torch.Tensor):
                 raise PtxError("SampleClips: videos[%d] must be a uint8 CUDA tensor [Tv,H,W,3], got %s" % (i, type(v).__name__))
@@ -1346,7 +1510,7 @@ class SampleClips:
         NC = len(vids) * K
         keep = []
         src = np.zeros(len(vids), _CLIP_SRC)
-        ysrc = (ClipSrcYuv420 * len(vids))() if yuv else None
+        ysrc = (vids[0]._CLIP_SRC * len(vids))() if yuv else None
         for i, (v, (Tv, H, W)) in enumerate(zip(vids, shapes)):
             src[i]["H"], src[i]["W"], src[i]["Tv"] = H, W, Tv
             if yuv:
@@ -1386,7 +1550,7 @@ class SampleClips:
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             check(_lib.lib().ptx_resize_build_tables_clips(C.byref(desc), at[0], at[-1], *tabs, stream),
                   "ptx_resize_build_tables_clips")
-            name = "ptx_resize_clips_yuv420" if yuv else "ptx_resize_clips_u8"
+            name = "ptx_resize_clips_" + (vids[0]._ABI if yuv else "u8")
             check(getattr(_lib.lib(), name)(C.byref(desc), at[1] if yuv else at[0], at[-2], *tabs, C.c_void_p(y.data_ptr()),
                                             C.byref(self.norm), stream), name)
             del keep                                                 # videos (copies included) stayed alive up to the launch
