@@ -14,6 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd.h")
 WINO4_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_wino4.h")      # the F(4x4) Winograd calls
 TFIR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_tfir.h")        # the stem's temporal fast-FIR calls
 YUV16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_yuv16.h")      # 10- / 12-bit YUV 4:2:0 sources
+COLOR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_color.h")      # ColorJitter / RandomGrayscale on uint8 frames
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -155,6 +156,14 @@ class ClipSrcYuv420P16(C.Structure):
     """ptx_clip_src_yuv420p16: the per-clip row of ptx_resize_clips_yuv420p16."""
     _fields_ = [("planes", Yuv420P16Src), ("H", C.c_int32), ("W", C.c_int32), ("Tv", C.c_int32), ("reserved", C.c_int32)]
 
+
+class ColorDesc(C.Structure):
+    """ptx_color_desc (ptx_amd_color.h): the frames of a ColorJitter launch, its output mode, whether a list holds contrast."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "H", "W", "out_mode", "contrast")]
+
+
+PTX_COLOR_NONE, PTX_COLOR_BRIGHTNESS, PTX_COLOR_CONTRAST, PTX_COLOR_SATURATION, PTX_COLOR_HUE, PTX_COLOR_GRAYSCALE = range(6)
+PTX_COLOR_MAX_OPS = 5
 
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
@@ -359,6 +368,15 @@ SIGNATURES_YUV16 = {
 }
 
 
+# include/ptx_amd_color.h: per-clip ColorJitter / RandomGrayscale on uint8 frames (csrc/color_jitter.h), bound the same way
+# (tests/test_color_jitter_host.py)
+SIGNATURES_COLOR = {
+    "ptx_color_jitter_supported": (C.c_int, [C.POINTER(ColorDesc), _P, _P]),
+    "ptx_color_jitter_stats": (C.c_int, [C.POINTER(ColorDesc), _P, _P, _P, _P, _P]),
+    "ptx_color_jitter_apply": (C.c_int, [C.POINTER(ColorDesc), _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -393,7 +411,7 @@ def lib():
                 "this package has no CPU / eager fallback" % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
-                list(SIGNATURES_YUV16.items()):
+                list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -1380,3 +1380,7 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 // So is the fp32 stem as a fast FIR along time (a filter transform, a memory-bound input transform and the stem's step loop over
 // the transformed frames).
 #include "conv_stem_tfir_f32.hip"
+
+// So are the per-clip ColorJitter / RandomGrayscale launches on uint8 frames (include/ptx_amd_color.h): the statistics and
+// the apply kernel, whose plane output is ptx_frames_u8_to_ncdhw's value of the jittered byte.
+#include "color_jitter.h"

@@ -267,3 +267,22 @@ def synth_frames(count, height, width, seed, content="noise"):
     if content != "noise":
         raise ValueError("synth_frames: content must be 'noise' or 'gradient'")
     return np.random.RandomState(int(seed)).randint(0, 256, (count, height, width, 3)).astype(np.uint8)
+
+
+def synth_color_frames(clips, frames, height, width, seed):
+    """Synthetic decoded clips for the colour transforms, uint8 numpy [clips, frames, height, width, 3]: colour ramps plus
+    seeded noise (numpy's legacy generator), with grey, black, white and saturated pixels sprinkled in, so every branch of the
+    HSV conversions and both ends of the blend's clamp are met.  Every frame differs."""
+    import numpy as np
+    rng = np.random.RandomState(int(seed))
+    yy, xx = np.mgrid[0:height, 0:width]
+    out = np.empty((clips, frames, height, width, 3), np.uint8)
+    for n in range(clips):
+        for t in range(frames):
+            base = np.stack([(xx * 255) // max(width - 1, 1), (yy * 255) // max(height - 1, 1), ((xx + yy) * 13 + 40 * t) % 256], -1)
+            img = np.clip(base + rng.randint(-60, 61, base.shape), 0, 255)
+            img[rng.rand(height, width) < 0.05] = rng.randint(0, 256)        # grey pixels (max == min)
+            for colour in ((255, 0, 0), (0, 0, 0), (255, 255, 255)):
+                img[rng.rand(height, width) < 0.03] = colour
+            out[n, t] = img
+    return out

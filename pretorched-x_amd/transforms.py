@@ -36,9 +36,15 @@ uint8 frames:
   is that of the RGB path on the converted frames.  `YUV420P16` is the same for 10- and 12-bit streams (P010 / P012 /
   P016 surfaces, yuv420p10le / yuv420p12le planes; `yuv_coefficients_p16`, `yuv420p16_to_rgb_numpy`).
 
+* `ColorJitter` is torchvision's ColorJitter (+ RandomGrayscale) on uint8 frames, one draw per clip, equal to the PIL-image
+  code path bit for bit (`color_jitter_numpy` is the numpy statement of the contract).  Alone it maps uint8 frames to uint8
+  frames; as `TransformFrames(.., color=cj)` / `SampleClips(.., color=cj)` it runs behind the resize, which then writes uint8
+  frames into scratch, and the colour launch writes the requested output (uint8 frames or the normalised fp32 / bf16 clip).
+
 Image loading and video decoding stay host work and are not on this path.
 """
 import collections
+import copy
 import ctypes as C
 import math
 
@@ -606,6 +612,287 @@ def apply_tables_numpy(frame, tables):
     return one_pass(mid, (rlo - r0, rn, tables["rows"][2]))
 
 
+# ---------------------------------------------------------------------------------------------
+# ColorJitter / RandomGrayscale per clip (include/ptx_amd_color.h): the arithmetic contract in numpy, the draw, the launches
+# ---------------------------------------------------------------------------------------------
+COLOR_OPS = ("none", "brightness", "contrast", "saturation", "hue", "grayscale")          # the PTX_COLOR_* codes, by index
+COLOR_MAX_OPS = _lib.PTX_COLOR_MAX_OPS
+
+
+def color_luma_numpy(rgb):
+    """PIL's convert("L") of uint8 [..., 3]: (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16, as int32 [...]."""
+    c = np.asarray(rgb).astype(np.int32)
+    return (c[..., 0] * 19595 + c[..., 1] * 38470 + c[..., 2] * 7471 + 0x8000) >> 16
+
+
+def color_blend_numpy(d, x, f):
+    """PIL's Image.blend(degenerate, image, f) on integer arrays (ImageEnhance's one operation): t = fp32(d) + fp32(f *
+    fp32(x - d)), every operation rounded to fp32; 0 if t <= 0, 255 if t >= 255, else trunc(t).  int32 result."""
+    d, x = np.asarray(d).astype(np.int32), np.asarray(x).astype(np.int32)
+    t = d.astype(np.float32) + np.float32(f) * (x - d).astype(np.float32)
+    return np.where(t <= 0, 0, np.where(t >= 255, 255, np.trunc(t))).astype(np.int32)
+
+
+def color_rgb_to_hsv_numpy(rgb):
+    """PIL's convert("HSV") of uint8 [..., 3] (the contract in include/ptx_amd_color.h): fp32 divisions, the hue assembled in
+    fp64 from the widened floats and rounded back to fp32.  uint8 [..., 3]."""
+    c = np.asarray(rgb).astype(np.int32)
+    r, g, b = c[..., 0], c[..., 1], c[..., 2]
+    maxc, minc = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    grey = maxc == minc
+    cr = np.where(grey, 1, maxc - minc).astype(np.float32)
+    s = cr / np.where(grey, 1, maxc).astype(np.float32)
+    rc, gc, bc = ((maxc - v).astype(np.float32) / cr for v in (r, g, b))
+    rc, gc, bc = rc.astype(np.float64), gc.astype(np.float64), bc.astype(np.float64)
+    hd = np.where(r == maxc, bc - gc, np.where(g == maxc, 2.0 + rc - bc, 4.0 + gc - rc))
+    hf = hd.astype(np.float32)
+    h2 = np.fmod(hf.astype(np.float64) / 6.0 + 1.0, 1.0).astype(np.float32)
+    H = np.clip((h2.astype(np.float64) * 255.0).astype(np.int64), 0, 255)
+    S = np.clip((s.astype(np.float64) * 255.0).astype(np.int64), 0, 255)
+    out = np.stack([np.where(grey, 0, H), np.where(grey, 0, S), maxc], axis=-1)
+    return out.astype(np.uint8)
+
+
+def color_hsv_to_rgb_numpy(hsv):
+    """PIL's HSV -> RGB of uint8 [..., 3], all in fp64; round is floor(a + 0.5) clipped to 0..255.  uint8 [..., 3]."""
+    c = np.asarray(hsv).astype(np.int64)
+    H, S, V = c[..., 0], c[..., 1], c[..., 2]
+    x = H * 6.0 / 255.0
+    i = np.floor(x)
+    f = x - i
+    fs = S / 255.0
+    v = V.astype(np.float64)
+
+    def rnd(a):
+        return np.clip(np.floor(a + 0.5), 0, 255).astype(np.int64)
+
+    p, q, t = rnd(v * (1.0 - fs)), rnd(v * (1.0 - fs * f)), rnd(v * (1.0 - fs * (1.0 - f)))
+    k = i.astype(np.int64) % 6
+    pick = lambda a: np.choose(k, a)
+    out = np.stack([pick([V, q, p, p, t, V]), pick([t, V, V, q, p, p]), pick([p, p, t, V, V, q])], axis=-1)
+    return np.where((S == 0)[..., None], V[..., None], out).astype(np.uint8)
+
+
+def hue_shift(hue_factor):
+    """torchvision's uint8 wrap of adjust_hue: trunc(hue_factor * 255) mod 256, from the factor as a Python float."""
+    return int(float(hue_factor) * 255.0) % 256
+
+
+def _color_rows(ops, N=None, who="ColorJitter"):
+    """`ops` = (codes [N, 5] integers, factors [N, 5] floats) -- arrays or CPU tensors -- as contiguous (int32, float32) numpy
+    arrays, or PtxError.  Shapes only; the values are checked by ptx_color_jitter_supported."""
+    try:
+        codes, factors = ops
+    except (TypeError, ValueError):
+        raise PtxError("%s: params must be a pair (codes [N, %d], factors [N, %d]), got %r" % (who, COLOR_MAX_OPS, COLOR_MAX_OPS, type(ops).__name__))
+    arrs = []
+    for name, a, kinds in (("codes", codes, "iu"), ("factors", factors, "fiu")):
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                raise PtxError("%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
+            a = a.numpy()
+        a = np.asarray(a)
+        if a.dtype.kind not in kinds:
+            raise PtxError("%s: params %s must hold %s, got dtype %s" % (who, name, "integers" if kinds == "iu" else "numbers", a.dtype))
+        if a.ndim != 2 or a.shape[1] != COLOR_MAX_OPS:
+            raise PtxError("%s: params %s must be [N, %d], got shape %s" % (who, name, COLOR_MAX_OPS, a.shape))
+        if N is not None and a.shape[0] != N:
+            raise PtxError("%s: params %s hold %d clips, the frames hold N = %d" % (who, name, a.shape[0], N))
+        arrs.append(a)
+    if arrs[0].shape != arrs[1].shape:
+        raise PtxError("%s: params codes and factors differ in shape: %s and %s" % (who, arrs[0].shape, arrs[1].shape))
+    if arrs[0].shape[0] == 0:
+        raise PtxError("%s: empty batch" % who)
+    return np.ascontiguousarray(arrs[0].astype(np.int32)), np.ascontiguousarray(arrs[1].astype(np.float32))
+
+
+def check_color_params(ops, N=None, who="ColorJitter"):
+    """`ops` as (CPU int32 [N, 5], CPU float32 [N, 5]) tensors, or PtxError with the library's reason: a code out of range, a
+    repeated code, a hue shift that is not an integer 0..255, a factor that is negative or not finite.  No device is touched."""
+    codes, factors = _color_rows(ops, N, who)
+    desc = _lib.ColorDesc(codes.shape[0], 1, 1, 1, _lib.PTX_RESIZE_OUT_U8, int((codes == _lib.PTX_COLOR_CONTRAST).any()))
+    if not _lib.lib().ptx_color_jitter_supported(C.byref(desc), C.c_void_p(codes.ctypes.data), C.c_void_p(factors.ctypes.data)):
+        raise PtxError("%s: %s" % (who, _lib.lib().ptx_last_error().decode(errors="replace")))
+    return torch.from_numpy(codes), torch.from_numpy(factors)
+
+
+def color_jitter_numpy(frames, ops):
+    """The kernels' arithmetic in numpy: uint8 frames [N,T,H,W,3] and `ops` = (codes [N, 5], factors [N, 5]) -> uint8
+    [N,T,H,W,3].  Every clip's list runs in order on every frame; contrast takes the mean luma of the FRAME as it stands when
+    contrast is applied.  The host-side model the tests compare with PIL; not a fallback (ColorJitter never calls it)."""
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[-1] != 3:
+        raise PtxError("color_jitter_numpy: frames must be uint8 [N,T,H,W,3], got %s %s" % (frames.dtype, frames.shape))
+    codes, factors = (t.numpy() for t in check_color_params(ops, frames.shape[0], "color_jitter_numpy"))
+    out = np.empty_like(frames)
+    for n in range(frames.shape[0]):
+        for t in range(frames.shape[1]):
+            img = frames[n, t].astype(np.int32)
+            for code, f in zip(codes[n].tolist(), factors[n]):
+                name = COLOR_OPS[code]
+                if name == "brightness":
+                    img = color_blend_numpy(0, img, f)
+                elif name == "contrast":
+                    lum = color_luma_numpy(img)
+                    m = int(int(lum.sum()) / lum.size + 0.5)
+                    img = color_blend_numpy(m, img, f)
+                elif name == "saturation":
+                    img = color_blend_numpy(color_luma_numpy(img)[..., None], img, f)
+                elif name == "hue":
+                    hsv = color_rgb_to_hsv_numpy(img)
+                    hsv[..., 0] += np.uint8(int(f) & 255)                    # uint8 wrap
+                    img = color_hsv_to_rgb_numpy(hsv).astype(np.int32)
+                elif name == "grayscale":
+                    img = np.repeat(color_luma_numpy(img)[..., None], 3, axis=-1)
+            out[n, t] = img.astype(np.uint8)
+    return out
+
+
+class ColorJitter:
+    """torchvision's ColorJitter (+ RandomGrayscale) on decoded uint8 frames on the device, one draw per CLIP, equal to the
+    PIL-image code path (ImageEnhance.Brightness / Contrast / Color, the HSV round trip of adjust_hue, convert("L")) bit for
+    bit.  include/ptx_amd_color.h states the arithmetic, `color_jitter_numpy` restates it.
+
+    brightness / contrast / saturation: a number v gives the range [max(0, 1 - v), 1 + v], a pair (lo, hi) with 0 <= lo <= hi
+    is taken as it is; hue: v in [0, 0.5] gives [-v, v], a pair lies inside [-0.5, 0.5].  A range that is the identity alone
+    (0, or (1, 1); (0, 0) for hue) switches the op off: nothing is drawn for it and it does not run.  grayscale: the
+    probability of RandomGrayscale, applied after the jitter.  generator: a CPU torch.Generator (None: torch's default one).
+
+    `cj(frames)` jitters uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3] (one draw per clip: N, or one) and keeps the draw
+    as `last_params` = (codes CPU int32 [N, 5], factors CPU float32 [N, 5]): per clip the ordered op list, codes indexing
+    `COLOR_OPS`, the factor of hue being the integer shift `hue_shift(h)`.  `cj(frames, params=p)` applies given lists.
+    A call is one small upload and one launch, plus a statistics launch when a list holds contrast (`last_launches`)."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, grayscale=0.0, generator=None):
+        self.brightness = self._range(brightness, "brightness")
+        self.contrast = self._range(contrast, "contrast")
+        self.saturation = self._range(saturation, "saturation")
+        self.hue = self._range(hue, "hue", center=0.0, bound=(-0.5, 0.5), clip=False)
+        if isinstance(grayscale, bool) or not isinstance(grayscale, (int, float)) or not 0.0 <= grayscale <= 1.0:
+            raise PtxError("ColorJitter: grayscale must be a probability in [0, 1], got %r" % (grayscale,))
+        self.grayscale = float(grayscale)
+        if generator is not None and not isinstance(generator, torch.Generator):
+            raise PtxError("ColorJitter: generator must be a torch.Generator or None, got %r" % (generator,))
+        self.generator, self.last_params, self.last_launches = generator, None, ()
+
+    @staticmethod
+    def _range(value, name, center=1.0, bound=(0.0, float("inf")), clip=True):
+        """torchvision's ColorJitter._check_input: the (lo, hi) range of a factor, or None when the op is off."""
+        if isinstance(value, bool):
+            raise PtxError("ColorJitter: %s must be a number or a pair (lo, hi), got %r" % (name, value))
+        if isinstance(value, (int, float)):
+            if not value >= 0 or not math.isfinite(value):
+                raise PtxError("ColorJitter: %s=%r: a single number must be non-negative and finite" % (name, value))
+            lo, hi = center - float(value), center + float(value)
+            if clip:
+                lo = max(lo, 0.0)
+        else:
+            try:
+                lo, hi = (float(v) for v in value)
+            except (TypeError, ValueError):
+                raise PtxError("ColorJitter: %s must be a number or a pair (lo, hi), got %r" % (name, value))
+        if not (bound[0] <= lo <= hi <= bound[1]) or not math.isfinite(hi):
+            raise PtxError("ColorJitter: %s: the range (%r, %r) must be ordered and lie inside [%g, %g]" % (name, lo, hi, bound[0], bound[1]))
+        return None if lo == hi == center else (lo, hi)
+
+    def draw(self, n):
+        """Lists of n clips: (codes CPU int32 [n, 5], factors CPU float32 [n, 5]).  Per clip, in torchvision's order, from
+        `generator`: torch.randperm(4); torch.empty(1).uniform_(lo, hi) for each enabled one of brightness, contrast,
+        saturation, hue, in that order; if grayscale > 0, torch.rand(1) < grayscale.  The enabled ops run in the permutation's
+        order (0 brightness, 1 contrast, 2 saturation, 3 hue), grayscale last; factors stay the fp32 values drawn."""
+        g = self.generator
+        codes = torch.zeros((int(n), COLOR_MAX_OPS), dtype=torch.int32)
+        factors = torch.zeros((int(n), COLOR_MAX_OPS), dtype=torch.float32)
+        ranges = (self.brightness, self.contrast, self.saturation, self.hue)
+        for i in range(int(n)):
+            order = torch.randperm(4, generator=g).tolist()
+            drawn = [None if r is None else torch.empty(1).uniform_(r[0], r[1], generator=g)[0] for r in ranges]
+            gray = self.grayscale > 0 and bool(torch.rand(1, generator=g) < self.grayscale)
+            k = 0
+            for fn in order:
+                if drawn[fn] is None:
+                    continue
+                codes[i, k] = fn + 1
+                factors[i, k] = float(hue_shift(float(drawn[fn]))) if fn == 3 else drawn[fn]
+                k += 1
+            if gray:
+                codes[i, k] = _lib.PTX_COLOR_GRAYSCALE
+        return codes, factors
+
+    def check_params(self, params, N=None):
+        """See `check_color_params`."""
+        return check_color_params(params, N)
+
+    def _launch(self, f5, params, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+        """The launches on contiguous uint8 CUDA frames f5 [N,T,H,W,3] with checked params: uint8 [N,T,H,W,3] or the
+        normalised [N,3,T,H,W] of `dtype`."""
+        codes, factors = params
+        N, T, H, W, _ = f5.shape
+        contrast = bool((codes == _lib.PTX_COLOR_CONTRAST).any())
+        lib = _lib.lib()
+        with torch.cuda.device(f5.device):
+            rows = torch.cat([codes.reshape(-1).view(torch.uint8), factors.reshape(-1).view(torch.uint8)]).to(f5.device)   # one upload
+            ops_p, fac_p = C.c_void_p(rows.data_ptr()), C.c_void_p(rows.data_ptr() + N * COLOR_MAX_OPS * 4)
+            desc = _lib.ColorDesc(N, T, H, W, mode, int(contrast))
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            sums = None
+            if contrast:
+                sums = torch.empty(N * T, device=f5.device, dtype=torch.int64)
+                check(lib.ptx_color_jitter_stats(C.byref(desc), C.c_void_p(f5.data_ptr()), ops_p, fac_p, C.c_void_p(sums.data_ptr()),
+                                                 stream), "ptx_color_jitter_stats")
+            if mode == _lib.PTX_RESIZE_OUT_U8:
+                y = torch.empty((N, T, H, W, 3), device=f5.device, dtype=torch.uint8)
+            else:
+                y = torch.empty((N, 3, T, H, W), device=f5.device, dtype=dtype)
+            check(lib.ptx_color_jitter_apply(C.byref(desc), C.c_void_p(f5.data_ptr()), ops_p, fac_p,
+                                             C.c_void_p(sums.data_ptr()) if contrast else None, C.c_void_p(y.data_ptr()),
+                                             C.byref(norm) if norm is not None else None, stream), "ptx_color_jitter_apply")
+        self.last_launches = ("stats", "apply") if contrast else ("apply",)
+        return y
+
+    def _params_for(self, N, params):
+        if params is None:
+            self.last_params = self.draw(N)
+            return self.check_params(self.last_params, N)
+        return self.check_params(params, N)
+
+    def __call__(self, frames, params=None):
+        if not isinstance(frames, torch.Tensor):
+            raise PtxError("ColorJitter: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
+        if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
+            raise PtxError("ColorJitter: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (tuple(frames.shape),))
+        N = frames.shape[0] if frames.dim() == 5 else 1
+        if params is not None:                                       # validated before a device is touched
+            params = self.check_params(params, N)
+        if not frames.is_cuda or frames.dtype != torch.uint8:
+            raise PtxError("ColorJitter: frames must be a uint8 CUDA tensor (no CPU fallback)")
+        if frames.numel() == 0:
+            raise PtxError("ColorJitter: empty batch")
+        f5 = frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
+        return self._launch(f5, self._params_for(N, params)).view(frames.shape)
+
+
+def _apply_color(color, frames_u8, out, dtype, norm, color_params):
+    """The colour half of TransformFrames / SampleClips with color=: `frames_u8` is the resize's uint8 output ([N,T,S,S,3] or
+    a lower rank, one clip), the result the requested output of the call."""
+    lead = frames_u8.dim()
+    f5 = frames_u8.view((1,) * (5 - lead) + tuple(frames_u8.shape))
+    p = color._params_for(f5.shape[0], color_params)
+    if out == "frames":
+        return color._launch(f5, p).view(frames_u8.shape)
+    mode = _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+    y = color._launch(f5, p, mode, norm, dtype)
+    if lead == 5:
+        return y
+    return y[0] if lead == 4 else y[0, :, 0]
+
+
+def _check_color(color, who):
+    if color is not None and not isinstance(color, ColorJitter):
+        raise PtxError("%s: color must be a pretorched.transforms.ColorJitter or None, got %r" % (who, color))
+    return color
+
+
 class TransformFrames:
     """Resize + crop (+ flip) of decoded uint8 frames on the device, bit-exact with PIL's bilinear resize, then
     TransformImage's tensor half (`out="tensor"`) or nothing more (`out="frames"`).
@@ -628,13 +915,18 @@ class TransformFrames:
     crop="center", and does not use `scale`.  random_resized_crop is torchvision's RandomResizedCrop
     (`random_resized_crop_box` states the algorithm; torchvision is not needed): the drawn box is resized to S x S; it
     excludes random_crop, random_short_side and an explicit crop and ignores scale / preserve_aspect_ratio.  Flips
-    apply as above.  `tf(frames, geometry=g)` applies given rows instead (on any TransformFrames)."""
+    apply as above.  `tf(frames, geometry=g)` applies given rows instead (on any TransformFrames).
+
+    color: a `ColorJitter` (None: off, the code path without it).  The resize then writes uint8 frames into scratch and the
+    colour launch writes the output of `out` / `dtype`; the lists are drawn per clip after every other draw of the call and
+    kept as `color.last_params`; `tf(frames, color_params=p)` applies given lists instead."""
 
     CACHE_SIZE = 8
 
     def __init__(self, opts, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, out="tensor",
                  dtype=torch.float32, *, random_crop=False, random_hflip=False, random_vflip=False, vflip=False,
-                 generator=None, random_short_side=None, random_resized_crop=False):
+                 generator=None, random_short_side=None, random_resized_crop=False, color=None):
+        self.color = _check_color(color, "TransformFrames")
         if out not in ("tensor", "frames"):
             raise PtxError("TransformFrames: out must be 'tensor' or 'frames', got %r" % (out,))
         if dtype not in (torch.float32, torch.bfloat16):
@@ -712,6 +1004,20 @@ class TransformFrames:
                 raise PtxError("TransformFrames: random_resized_crop draws the box; it cannot be combined with crop=%r" % (crop,))
             self.random_resized_crop = rrc
         self.per_clip_geometry = self.random_short_side is not None or self.random_resized_crop is not None
+        self._resize = None
+        if self.color is not None:                                   # the resize half of a call with colour: this transform,
+            self._resize = copy.copy(self)                           # writing uint8 frames (tables cache and generator shared)
+            self._resize.color, self._resize.out, self._resize.dtype = None, "frames", torch.float32
+
+    def _call_color(self, frames, params, geometry, color_params):
+        """A call with color=: the resize writes uint8 frames into scratch (every draw of the plain call, in its order), then the
+        colour lists are drawn clip by clip and the apply launch writes the requested output."""
+        rs = self._resize
+        if color_params is not None:                                 # validated before a device is touched
+            color_params = self.color.check_params(color_params)
+        u8 = rs(frames, params=params, geometry=geometry)
+        self.last_params, self.last_geometry = rs.last_params, rs.last_geometry
+        return _apply_color(self.color, u8, self.out, self.dtype, self.norm, color_params)
 
     def tables(self, H, W):
         """Host tables for H x W frames (numpy; see build_tables)."""
@@ -866,7 +1172,7 @@ class TransformFrames:
             self._cache.popitem(last=False)
         return hit
 
-    def __call__(self, frames, params=None, geometry=None):
+    def __call__(self, frames, params=None, geometry=None, color_params=None):
         """uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3], any H, W  ->
         out="tensor": [N,3,T,S,S] | [3,T,S,S] | [3,S,S] (fp32 or bf16);  out="frames": uint8, same rank, H, W -> S, S.
         A `YUV420` source is taken in place of the frames (converted while the kernel stages its rows: the same bits as
@@ -876,7 +1182,14 @@ class TransformFrames:
         integers, see `check_params`) applies given parameters instead.  Both are one launch.
         With random_short_side / random_resized_crop one geometry row is drawn per clip in the same way and kept as
         `last_geometry`; geometry ([N, 10] integers, see `check_geometry`) applies given rows instead, on any transform.
-        Both are a table-builder launch plus one resize launch."""
+        Both are a table-builder launch plus one resize launch.
+        With color= (a `ColorJitter`) the resize writes uint8 frames into scratch and the colour launch writes the output;
+        the colour lists are drawn after every other draw of the call, clip by clip (a seed gives the same geometry with and
+        without colour), and kept as `color.last_params`; color_params applies given lists instead."""
+        if self.color is not None:
+            return self._call_color(frames, params, geometry, color_params)
+        if color_params is not None:
+            raise PtxError("TransformFrames: color_params= needs a transform built with color=ColorJitter(..)")
         if params is not None and geometry is not None:
             raise PtxError("TransformFrames: params= and geometry= cannot be combined (a geometry row holds the window and flips)")
         if params is not None and self.per_clip_geometry:
@@ -1317,12 +1630,15 @@ class SampleClips:
 
     A call draws one index row and one geometry row per output clip (kept as `last_indices`, CPU int64 [N*clips, T], and
     `last_geometry`, CPU int32 [N*clips, 10]); `sc(videos, indices=.., geometry=..)` applies given rows instead, on any
-    SampleClips.  Output clip j comes from video j // clips."""
+    SampleClips.  Output clip j comes from video j // clips.
+
+    color: a `ColorJitter` applied behind the resize, one list per output clip, as for `TransformFrames(.., color=)`."""
 
     def __init__(self, opts, num_frames=16, frame_stride=4, clips=1, sampling="dense", random_start=True, scale=0.875,
                  preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False, random_crop=False, random_hflip=False,
                  random_vflip=False, random_short_side=None, random_resized_crop=False, out="tensor", dtype=torch.float32,
-                 generator=None):
+                 generator=None, color=None):
+        self.color = _check_color(color, "SampleClips")
         for name, v in (("num_frames", num_frames), ("frame_stride", frame_stride), ("clips", clips)):
             if not isinstance(v, int) or isinstance(v, bool) or v < 1:
                 raise PtxError("SampleClips: %s must be a positive integer, got %r" % (name, v))
@@ -1335,6 +1651,10 @@ class SampleClips:
         self.random_start, self.generator = bool(random_start), generator
         self.out, self.dtype, self.size, self.norm = out, dtype, self.spatial.size, self.spatial.norm
         self.last_indices, self.last_geometry = None, None
+        self._resize = None
+        if self.color is not None:                                   # the resize half of a call with colour (see TransformFrames)
+            self._resize = copy.copy(self)
+            self._resize.color, self._resize.out, self._resize.dtype = None, "frames", torch.float32
 
     # ---- host only: no device is touched -------------------------------------------------------
     @staticmethod
@@ -1485,14 +1805,26 @@ class SampleClips:
             raise PtxError("SampleClips: videos[%d] is on %s, videos[0] on %s: a batch lives on one device" % (i, devs[i], devs[0]))
         return videos
 
-    def __call__(self, videos, indices=None, geometry=None):
+    def __call__(self, videos, indices=None, geometry=None, color_params=None):
         """videos: a list / tuple of uint8 CUDA tensors [Tv_i,H_i,W_i,3] of any sizes and lengths on one device | one
         [N,Tv,H,W,3] tensor (N videos) | one [Tv,H,W,3] tensor | a list of `YUV420` sources with planes [Tv,H,W] | one
         `YUV420` with planes [N,Tv,H,W] or [Tv,H,W]  ->  out="tensor": [N*clips,3,T,S,S] (fp32 or bf16); out="frames": uint8
         [N*clips,T,S,S,3].  A video is read in place when its frames are contiguous [H,W,3] blocks (slices and steps over
         Tv included); any other video costs one `.contiguous()` copy of that video only.  One call is one upload (source,
         index and geometry rows in one buffer), one table-builder launch and one resize launch, whatever the batch holds;
-        the tap pitches are the maxima over the batch."""
+        the tap pitches are the maxima over the batch.
+        With color= (a `ColorJitter`) the resize writes uint8 clips into scratch and the colour launch writes the output: one
+        list per output clip, drawn after every other draw of the call and kept as `color.last_params`; color_params applies
+        given lists instead."""
+        if self.color is not None:
+            if color_params is not None:                             # validated before a device is touched
+                color_params = self.color.check_params(color_params)
+            rs = self._resize
+            u8 = rs(videos, indices=indices, geometry=geometry)
+            self.last_indices, self.last_geometry = rs.last_indices, rs.last_geometry
+            return _apply_color(self.color, u8, self.out, self.dtype, self.norm, color_params)
+        if color_params is not None:
+            raise PtxError("SampleClips: color_params= needs a sampler built with color=ColorJitter(..)")
         if (indices is None) != (geometry is None):
             raise PtxError("SampleClips: indices= and geometry= are given together (a replay) or not at all (a draw)")
         vids = self._videos(videos)
