@@ -15,6 +15,7 @@ WINO4_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_win
 TFIR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_tfir.h")        # the stem's temporal fast-FIR calls
 YUV16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_yuv16.h")      # 10- / 12-bit YUV 4:2:0 sources
 COLOR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_color.h")      # ColorJitter / RandomGrayscale on uint8 frames
+RANDAUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_randaug.h")  # RandAugment on uint8 frames
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -164,6 +165,17 @@ class ColorDesc(C.Structure):
 
 PTX_COLOR_NONE, PTX_COLOR_BRIGHTNESS, PTX_COLOR_CONTRAST, PTX_COLOR_SATURATION, PTX_COLOR_HUE, PTX_COLOR_GRAYSCALE = range(6)
 PTX_COLOR_MAX_OPS = 5
+
+class RandAugDesc(C.Structure):
+    """ptx_randaug_desc (ptx_amd_randaug.h): the frames of one RandAugment position, its output mode, the fill colour."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "H", "W", "out_mode", "num_ops", "position", "stats", "fill_r", "fill_g", "fill_b",
+                                         "reserved")]
+
+
+(PTX_RANDAUG_IDENTITY, PTX_RANDAUG_SHEAR_X, PTX_RANDAUG_SHEAR_Y, PTX_RANDAUG_TRANSLATE_X, PTX_RANDAUG_TRANSLATE_Y, PTX_RANDAUG_ROTATE,
+ PTX_RANDAUG_BRIGHTNESS, PTX_RANDAUG_COLOR, PTX_RANDAUG_CONTRAST, PTX_RANDAUG_SHARPNESS, PTX_RANDAUG_POSTERIZE, PTX_RANDAUG_SOLARIZE,
+ PTX_RANDAUG_AUTOCONTRAST, PTX_RANDAUG_EQUALIZE) = range(14)
+PTX_RANDAUG_NUM_CODES, PTX_RANDAUG_MAX_OPS, PTX_RANDAUG_ROW, PTX_RANDAUG_STATS_WORDS = 14, 4, 8, 770
 
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
@@ -377,6 +389,15 @@ SIGNATURES_COLOR = {
 }
 
 
+# include/ptx_amd_randaug.h: per-clip RandAugment on uint8 frames (csrc/rand_augment.h), bound the same way
+# (tests/test_rand_augment_host.py)
+SIGNATURES_RANDAUG = {
+    "ptx_rand_augment_supported": (C.c_int, [C.POINTER(RandAugDesc), _P]),
+    "ptx_rand_augment_stats": (C.c_int, [C.POINTER(RandAugDesc), _P, _P, _P, _P]),
+    "ptx_rand_augment_apply": (C.c_int, [C.POINTER(RandAugDesc), _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -411,7 +432,7 @@ def lib():
                 "this package has no CPU / eager fallback" % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
-                list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()):
+                list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

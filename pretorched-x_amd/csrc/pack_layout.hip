@@ -1384,3 +1384,7 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 // So are the per-clip ColorJitter / RandomGrayscale launches on uint8 frames (include/ptx_amd_color.h): the statistics and
 // the apply kernel, whose plane output is ptx_frames_u8_to_ncdhw's value of the jittered byte.
 #include "color_jitter.h"
+
+// So are the per-clip RandAugment launches (include/ptx_amd_randaug.h): per op position a statistics kernel (histograms and the
+// luma sum of every frame, when an op needs them) and an apply kernel that shares color_jitter.h's blend, luma and mean.
+#include "rand_augment.h"

@@ -41,6 +41,11 @@ uint8 frames:
   frames; as `TransformFrames(.., color=cj)` / `SampleClips(.., color=cj)` it runs behind the resize, which then writes uint8
   frames into scratch, and the colour launch writes the requested output (uint8 frames or the normalised fp32 / bf16 clip).
 
+* `RandAugment` is torchvision's RandAugment on uint8 frames, one draw per clip, equal to the PIL-image code path (nearest
+  interpolation) bit for bit (`rand_augment_numpy` is the numpy statement of the contract): per op position a statistics launch
+  (only when an op needs a frame's histograms or mean) and an apply launch.  As `TransformFrames(.., augment=ra)` /
+  `SampleClips(.., augment=ra)` it runs behind the resize and behind `color=`, its last position writing the call's output.
+
 Image loading and video decoding stay host work and are not on this path.
 """
 import collections
@@ -893,6 +898,419 @@ def _check_color(color, who):
     return color
 
 
+# ---------------------------------------------------------------------------------------------
+# RandAugment per clip (include/ptx_amd_randaug.h): the op table and the draw, PIL's affine coefficients, the arithmetic contract
+# in numpy, the launches
+# ---------------------------------------------------------------------------------------------
+RANDAUG_OPS = ("identity", "shear_x", "shear_y", "translate_x", "translate_y", "rotate", "brightness", "color", "contrast",
+               "sharpness", "posterize", "solarize", "autocontrast", "equalize")             # the PTX_RANDAUG_* codes, by index
+RANDAUG_SIGNED = (False,) + (True,) * 9 + (False,) * 4
+RANDAUG_MAX_OPS = _lib.PTX_RANDAUG_MAX_OPS
+_RANDAUG_GEOMETRIC = range(_lib.PTX_RANDAUG_SHEAR_X, _lib.PTX_RANDAUG_ROTATE + 1)
+_RANDAUG_ENHANCE = range(_lib.PTX_RANDAUG_BRIGHTNESS, _lib.PTX_RANDAUG_SHARPNESS + 1)
+_RANDAUG_STATS = (_lib.PTX_RANDAUG_CONTRAST, _lib.PTX_RANDAUG_AUTOCONTRAST, _lib.PTX_RANDAUG_EQUALIZE)
+
+
+def rand_augment_space(num_bins, H, W):
+    """torchvision's RandAugment._augmentation_space(num_bins, (H, W)): per op code the float32 magnitude table (None: the op
+    takes no magnitude), in RANDAUG_OPS order."""
+    lin = lambda a, b: torch.linspace(a, b, num_bins)
+    return [None, lin(0.0, 0.3), lin(0.0, 0.3), lin(0.0, 150.0 / 331.0 * W), lin(0.0, 150.0 / 331.0 * H), lin(0.0, 30.0),
+            lin(0.0, 0.9), lin(0.0, 0.9), lin(0.0, 0.9), lin(0.0, 0.9),
+            8 - (torch.arange(num_bins) / ((num_bins - 1) / 4)).round().int(), lin(255.0, 0.0), None, None]
+
+
+def _inverse_affine_matrix(center, angle, translate, shear):
+    """torchvision's _get_inverse_affine_matrix (scale 1): PIL's six coefficients, output pixel -> input position."""
+    rot, sx, sy = math.radians(angle), math.radians(shear[0]), math.radians(shear[1])
+    cx, cy = center
+    tx, ty = translate
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    m = [d, -b, 0.0, -c, a, 0.0]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def rand_augment_matrix(code, magnitude, H, W):
+    """The six coefficients that torchvision's RandAugment hands to Image.transform(AFFINE) for a geometric op (codes 1..5) of
+    `magnitude` on an H x W image: F.affine's inverse matrix for the shears (centre (0, 0)) and translations (centre (W * 0.5,
+    H * 0.5), the offset truncated to an integer), PIL.Image.Image.rotate's own matrix for the rotation."""
+    mag = float(magnitude)
+    if code == _lib.PTX_RANDAUG_SHEAR_X:
+        return _inverse_affine_matrix((0.0, 0.0), 0.0, (0, 0), (math.degrees(math.atan(mag)), 0.0))
+    if code == _lib.PTX_RANDAUG_SHEAR_Y:
+        return _inverse_affine_matrix((0.0, 0.0), 0.0, (0, 0), (0.0, math.degrees(math.atan(mag))))
+    if code == _lib.PTX_RANDAUG_TRANSLATE_X:
+        return _inverse_affine_matrix((W * 0.5, H * 0.5), 0.0, (int(mag), 0), (0.0, 0.0))
+    if code == _lib.PTX_RANDAUG_TRANSLATE_Y:
+        return _inverse_affine_matrix((W * 0.5, H * 0.5), 0.0, (0, int(mag)), (0.0, 0.0))
+    if code != _lib.PTX_RANDAUG_ROTATE:
+        raise PtxError("rand_augment_matrix: op code %r is not geometric (1..5)" % (code,))
+    angle = -math.radians(mag % 360.0)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    cx, cy = W / 2, H / 2
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def affine_fixed(m, H, W, who="RandAugment"):
+    """PIL's 16.16 fixed-point form (a0 .. a5) of the affine coefficients m for an H x W image (Geometry.c, affine_fixed), or
+    PtxError when PIL itself would leave the fixed-point walk: a source coordinate of a frame corner at or beyond +-32768."""
+    for x, y in ((0, 0), (W, 0), (0, H), (W, H)):
+        if not (abs(x * m[0] + y * m[1] + m[2]) < 32768.0 and abs(x * m[3] + y * m[4] + m[5]) < 32768.0):
+            raise PtxError("%s: the affine coefficients leave PIL's fixed-point range on a %dx%d frame (a source coordinate beyond "
+                           "+-32768); such frames are not offered" % (who, H, W))
+    fix = lambda v: int(math.floor(v * 65536.0 + 0.5))
+    a = [fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5), fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in a):
+        raise PtxError("%s: the affine coefficients leave PIL's fixed-point range on a %dx%d frame (a source coordinate beyond "
+                       "+-32768); such frames are not offered" % (who, H, W))
+    return a
+
+
+def _randaug_params(params, N=None, who="RandAugment"):
+    """`params` = (codes [N, K] integers, magnitudes [N, K] numbers) -- arrays or CPU tensors -- as contiguous (int32, float64)
+    numpy arrays, or PtxError: shapes, K outside 1..PTX_RANDAUG_MAX_OPS, a code out of range, a magnitude that an op cannot take."""
+    try:
+        codes, mags = params
+    except (TypeError, ValueError):
+        raise PtxError("%s: params must be a pair (codes [N, num_ops], magnitudes [N, num_ops]), got %r" % (who, type(params).__name__))
+    arrs = []
+    for name, a, kinds in (("codes", codes, "iu"), ("magnitudes", mags, "fiu")):
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                raise PtxError("%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
+            a = a.numpy()
+        a = np.asarray(a)
+        if a.dtype.kind not in kinds:
+            raise PtxError("%s: params %s must hold %s, got dtype %s" % (who, name, "integers" if kinds == "iu" else "numbers", a.dtype))
+        if a.ndim != 2 or not 1 <= a.shape[1] <= RANDAUG_MAX_OPS:
+            raise PtxError("%s: params %s must be [N, num_ops] with num_ops 1..%d, got shape %s" % (who, name, RANDAUG_MAX_OPS, a.shape))
+        if N is not None and a.shape[0] != N:
+            raise PtxError("%s: params %s hold %d clips, the frames hold N = %d" % (who, name, a.shape[0], N))
+        arrs.append(a)
+    if arrs[0].shape != arrs[1].shape:
+        raise PtxError("%s: params codes and magnitudes differ in shape: %s and %s" % (who, arrs[0].shape, arrs[1].shape))
+    if arrs[0].shape[0] == 0:
+        raise PtxError("%s: empty batch" % who)
+    codes, mags = np.ascontiguousarray(arrs[0].astype(np.int64)), np.ascontiguousarray(arrs[1].astype(np.float64))
+    for (n, k), code in np.ndenumerate(codes):
+        mag = float(mags[n, k])
+        if not 0 <= code < len(RANDAUG_OPS):
+            raise PtxError("%s: clip %d position %d: op code %d out of range 0..%d" % (who, n, k, code, len(RANDAUG_OPS) - 1))
+        if not math.isfinite(mag):
+            raise PtxError("%s: clip %d position %d: magnitude %r is not finite" % (who, n, k, mag))
+        if code in _RANDAUG_ENHANCE and mag < -1.0:
+            raise PtxError("%s: clip %d position %d: %s magnitude %r gives a negative factor (1 + magnitude)" % (who, n, k, RANDAUG_OPS[code], mag))
+        if code == _lib.PTX_RANDAUG_POSTERIZE and not 0 <= int(mag) <= 8:
+            raise PtxError("%s: clip %d position %d: posterize keeps int(magnitude) = %d bits, not 0..8" % (who, n, k, int(mag)))
+    return codes.astype(np.int32), mags
+
+
+def rand_augment_rows(params, H, W, N=None, who="RandAugment"):
+    """The kernels' rows of `params` = (codes [N, K], magnitudes [N, K]) for H x W frames: int32 [N, K, PTX_RANDAUG_ROW] -- the
+    code, then a0 .. a5 (geometric ops, `affine_fixed(rand_augment_matrix(..))`), the bits of the fp32 factor 1 + magnitude
+    (brightness, color, contrast, sharpness), the posterize mask ~(2**(8 - int(magnitude)) - 1) & 255, or the bits of the solarize
+    threshold (its ceiling clamped to 0..256: for a byte c, c < thr is c < ceil(thr)).  PtxError when a row is refused."""
+    codes, mags = _randaug_params(params, N, who)
+    rows = np.zeros(codes.shape + (_lib.PTX_RANDAUG_ROW,), np.int32)
+    rows[..., 0] = codes
+    for (n, k), code in np.ndenumerate(codes):
+        mag = float(mags[n, k])
+        if code in _RANDAUG_GEOMETRIC:
+            rows[n, k, 1:7] = affine_fixed(rand_augment_matrix(int(code), mag, H, W), H, W, who)
+        elif code in _RANDAUG_ENHANCE:
+            rows[n, k, 1] = np.float32(1.0 + mag).view(np.int32)
+        elif code == _lib.PTX_RANDAUG_POSTERIZE:
+            rows[n, k, 1] = ~(2 ** (8 - int(mag)) - 1) & 255
+        elif code == _lib.PTX_RANDAUG_SOLARIZE:
+            rows[n, k, 1] = np.float32(math.ceil(min(max(mag, 0.0), 256.0))).view(np.int32)
+    return rows
+
+
+def _randaug_fill(fill, who="RandAugment"):
+    if isinstance(fill, int) and not isinstance(fill, bool):
+        fill = (fill,) * 3
+    try:
+        fill = tuple(fill)
+        ok = len(fill) == 3 and all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 255 for v in fill)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise PtxError("%s: fill must be an integer or an RGB triple of integers in 0..255, got %r" % (who, fill))
+    return fill
+
+
+def _randaug_supported(rows, H, W, fill, who="RandAugment"):
+    """ptx_rand_augment_supported on host rows [N, K, 8], position by position; PtxError with the library's reason."""
+    N, K = rows.shape[:2]
+    rows = np.ascontiguousarray(rows, np.int32)
+    for k in range(K):
+        stats = int(np.isin(rows[:, k, 0], _RANDAUG_STATS).any())
+        desc = _lib.RandAugDesc(N, 1, H, W, _lib.PTX_RESIZE_OUT_U8, K, k, stats, fill[0], fill[1], fill[2], 0)
+        if not _lib.lib().ptx_rand_augment_supported(C.byref(desc), C.c_void_p(rows.ctypes.data)):
+            raise PtxError("%s: %s" % (who, _lib.lib().ptx_last_error().decode(errors="replace")))
+    return rows
+
+
+def randaug_smooth_numpy(img):
+    """PIL's ImageFilter.SMOOTH of uint8 / integer [H, W, 3] (3 x 3 kernel 1 1 1 / 1 5 1 / 1 1 1 over 13): interior pixels are
+    (2 * S + 13) // 26 with S the neighbourhood's sum plus 4 times the centre; border pixels -- all, when H < 3 or W < 3 -- are
+    copied.  int32 [H, W, 3]."""
+    c = np.asarray(img).astype(np.int32)
+    out = c.copy()
+    H, W = c.shape[:2]
+    if H >= 3 and W >= 3:
+        S = 4 * c[1:-1, 1:-1]
+        for dy in range(3):
+            for dx in range(3):
+                S = S + c[dy:H - 2 + dy, dx:W - 2 + dx]
+        out[1:-1, 1:-1] = (2 * S + 13) // 26
+    return out
+
+
+def randaug_autocontrast_lut(h):
+    """ImageOps.autocontrast's LUT (256 ints) of one channel with histogram h (256 counts)."""
+    nz = [i for i in range(256) if h[i]]
+    lo, hi = (nz[0], nz[-1]) if nz else (255, 0)
+    if hi <= lo:
+        return list(range(256))
+    scale = 255.0 / (hi - lo)
+    offset = -lo * scale
+    return [min(max(int(i * scale + offset), 0), 255) for i in range(256)]
+
+
+def randaug_equalize_lut(h):
+    """ImageOps.equalize's LUT (256 ints) of one channel with histogram h (256 counts); an entry above 255 is stored as 255, as
+    Image.point stores it."""
+    histo = [int(v) for v in h if v]
+    if len(histo) <= 1:
+        return list(range(256))
+    step = (sum(histo) - histo[-1]) // 255
+    if not step:
+        return list(range(256))
+    lut, n = [], step // 2
+    for i in range(256):
+        lut.append(min(n // step, 255))
+        n += int(h[i])
+    return lut
+
+
+def rand_augment_op_numpy(img, row, fill=(0, 0, 0)):
+    """One position on one frame: uint8 [H, W, 3] and one row (PTX_RANDAUG_ROW int32 words, see `rand_augment_rows`) -> uint8
+    [H, W, 3], as include/ptx_amd_randaug.h states it."""
+    img = np.asarray(img)
+    H, W = img.shape[:2]
+    row = np.asarray(row, np.int32)
+    code = int(row[0])
+    f = row[1:2].view(np.float32)[0]
+    if code in _RANDAUG_GEOMETRIC:
+        a0, a1, a2, a3, a4, a5 = (int(v) for v in row[1:7])
+        y, x = np.mgrid[0:H, 0:W].astype(np.int64)
+        xin, yin = (a2 + a1 * y + a0 * x) >> 16, (a5 + a4 * y + a3 * x) >> 16
+        inside = (xin >= 0) & (xin < W) & (yin >= 0) & (yin < H)
+        out = np.empty_like(img)
+        out[...] = np.asarray(fill, np.uint8)
+        out[inside] = img[yin[inside], xin[inside]]
+        return out
+    c = img.astype(np.int32)
+    if code == _lib.PTX_RANDAUG_BRIGHTNESS:
+        c = color_blend_numpy(0, c, f)
+    elif code == _lib.PTX_RANDAUG_COLOR:
+        c = color_blend_numpy(color_luma_numpy(c)[..., None], c, f)
+    elif code == _lib.PTX_RANDAUG_CONTRAST:
+        lum = color_luma_numpy(c)
+        c = color_blend_numpy(int(int(lum.sum()) / lum.size + 0.5), c, f)
+    elif code == _lib.PTX_RANDAUG_SHARPNESS:
+        c = color_blend_numpy(randaug_smooth_numpy(c), c, f)
+    elif code == _lib.PTX_RANDAUG_POSTERIZE:
+        c = c & int(row[1])
+    elif code == _lib.PTX_RANDAUG_SOLARIZE:
+        c = np.where(c.astype(np.float32) < f, c, 255 - c)
+    elif code in (_lib.PTX_RANDAUG_AUTOCONTRAST, _lib.PTX_RANDAUG_EQUALIZE):
+        make = randaug_autocontrast_lut if code == _lib.PTX_RANDAUG_AUTOCONTRAST else randaug_equalize_lut
+        c = np.stack([np.asarray(make(np.bincount(c[..., ch].ravel(), minlength=256)), np.int32)[c[..., ch]] for ch in range(3)], -1)
+    return c.astype(np.uint8)
+
+
+def rand_augment_numpy(frames, params, fill=0):
+    """The kernels' arithmetic in numpy: uint8 frames [N,T,H,W,3] and `params` = (codes [N, K], magnitudes [N, K]) -> uint8
+    [N,T,H,W,3].  Every clip's positions run in order on every frame; contrast, autocontrast and equalize take the statistics of
+    the FRAME as it stands at their position.  The host-side model the tests compare with PIL; not a fallback (RandAugment never
+    calls it)."""
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[-1] != 3:
+        raise PtxError("rand_augment_numpy: frames must be uint8 [N,T,H,W,3], got %s %s" % (frames.dtype, frames.shape))
+    fill = _randaug_fill(fill, "rand_augment_numpy")
+    N, T, H, W, _ = frames.shape
+    rows = _randaug_supported(rand_augment_rows(params, H, W, N, "rand_augment_numpy"), H, W, fill, "rand_augment_numpy")
+    out = np.empty_like(frames)
+    for n in range(N):
+        for t in range(T):
+            img = frames[n, t]
+            for row in rows[n]:
+                img = rand_augment_op_numpy(img, row, fill)
+            out[n, t] = img
+    return out
+
+
+class RandAugment:
+    """torchvision's RandAugment on decoded uint8 frames on the device, one draw per CLIP, equal to its PIL-image code path
+    (nearest interpolation: Image.transform / rotate, ImageEnhance, ImageOps) bit for bit.  include/ptx_amd_randaug.h states the
+    arithmetic, `rand_augment_numpy` restates it.
+
+    num_ops: ops per clip, 1..PTX_RANDAUG_MAX_OPS; magnitude: the bin, 0 <= magnitude < num_magnitude_bins; fill: what the
+    geometric ops write where they have no source pixel, an integer or an RGB triple in 0..255; generator: a CPU torch.Generator
+    (None: torch's default one).
+
+    `ra(frames)` augments uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3] (one draw per clip: N, or one; statistics are per
+    frame) and keeps the draw as `last_params` = (codes CPU int32 [N, num_ops], magnitudes CPU float64 [N, num_ops]): per clip
+    the op codes in running order, indexing `RANDAUG_OPS`, and the signed magnitudes.  `ra(frames, params=p)` applies a given
+    draw (on any RandAugment, any num_ops in range).  Per position a call is one apply launch, plus a statistics launch when some
+    clip's op there is contrast, autocontrast or equalize (`last_launches`)."""
+
+    def __init__(self, num_ops=2, magnitude=9, num_magnitude_bins=31, fill=0, generator=None):
+        for name, v in (("num_ops", num_ops), ("magnitude", magnitude), ("num_magnitude_bins", num_magnitude_bins)):
+            if not isinstance(v, int) or isinstance(v, bool):
+                raise PtxError("RandAugment: %s must be an integer, got %r" % (name, v))
+        if not 1 <= num_ops <= RANDAUG_MAX_OPS:
+            raise PtxError("RandAugment: num_ops must be 1..%d (PTX_RANDAUG_MAX_OPS), got %d" % (RANDAUG_MAX_OPS, num_ops))
+        if num_magnitude_bins < 2:
+            raise PtxError("RandAugment: num_magnitude_bins must be at least 2, got %d" % num_magnitude_bins)
+        if not 0 <= magnitude < num_magnitude_bins:
+            raise PtxError("RandAugment: magnitude must be a bin 0..%d, got %d" % (num_magnitude_bins - 1, magnitude))
+        if generator is not None and not isinstance(generator, torch.Generator):
+            raise PtxError("RandAugment: generator must be a torch.Generator or None, got %r" % (generator,))
+        self.num_ops, self.magnitude, self.num_magnitude_bins = num_ops, magnitude, num_magnitude_bins
+        self.fill = _randaug_fill(fill)
+        self.generator, self.last_params, self.last_launches = generator, None, ()
+
+    def draw(self, n, H, W):
+        """The draw of n clips of H x W frames: (codes CPU int32 [n, num_ops], magnitudes CPU float64 [n, num_ops]).  Per clip and
+        position, in torchvision's order, from `generator`: op = int(torch.randint(14, (1,))); the magnitude is
+        float(table[magnitude].item()) of `rand_augment_space(num_magnitude_bins, H, W)` (0.0 for an op without a table); only
+        for a signed op, torch.randint(2, (1,)), a non-zero value negating the magnitude."""
+        g = self.generator
+        space = rand_augment_space(self.num_magnitude_bins, int(H), int(W))
+        codes = torch.zeros((int(n), self.num_ops), dtype=torch.int32)
+        mags = torch.zeros((int(n), self.num_ops), dtype=torch.float64)
+        for i in range(int(n)):
+            for k in range(self.num_ops):
+                op = int(torch.randint(len(RANDAUG_OPS), (1,), generator=g))
+                mag = float(space[op][self.magnitude].item()) if space[op] is not None else 0.0
+                if RANDAUG_SIGNED[op] and torch.randint(2, (1,), generator=g):
+                    mag *= -1.0
+                codes[i, k], mags[i, k] = op, mag
+        return codes, mags
+
+    def check_params(self, params, N=None, H=None, W=None):
+        """`params` as (CPU int32 [N, K], CPU float64 [N, K]) tensors, or PtxError: shapes, N, K outside 1..PTX_RANDAUG_MAX_OPS, a
+        code out of range, a magnitude that is not finite or that its op cannot take; with H and W also the library's own check
+        of the rows (`rand_augment_rows`) for frames of that size.  No device is touched."""
+        codes, mags = _randaug_params(params, N)
+        if H is not None and W is not None:
+            _randaug_supported(rand_augment_rows((codes, mags), int(H), int(W), N), int(H), int(W), self.fill)
+        return torch.from_numpy(codes), torch.from_numpy(mags)
+
+    def _rows_for(self, N, H, W, params):
+        """The checked host rows of a call on N clips of H x W frames: of a new draw (kept as last_params) or of `params`."""
+        if params is None:
+            params = self.last_params = self.draw(N, H, W)
+        return _randaug_supported(rand_augment_rows(params, H, W, N), H, W, self.fill)
+
+    def _launch(self, f5, rows, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+        """The launches on contiguous uint8 CUDA frames f5 [N,T,H,W,3] with checked host rows [N, K, 8]: uint8 [N,T,H,W,3] or the
+        normalised [N,3,T,H,W] of `dtype`.  Positions ping-pong between two uint8 scratch buffers; the last one writes y."""
+        N, T, H, W, _ = f5.shape
+        K = rows.shape[1]
+        lib = _lib.lib()
+        launches = []
+        with torch.cuda.device(f5.device):
+            dev_rows = torch.from_numpy(rows.reshape(-1)).to(f5.device)                  # one upload
+            rows_p = C.c_void_p(dev_rows.data_ptr())
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            scratch = [torch.empty_like(f5) for _ in range(min(K - 1, 2))]
+            if mode == _lib.PTX_RESIZE_OUT_U8:
+                y = torch.empty((N, T, H, W, 3), device=f5.device, dtype=torch.uint8)
+            else:
+                y = torch.empty((N, 3, T, H, W), device=f5.device, dtype=dtype)
+            stats = None
+            cur = f5
+            for k in range(K):
+                last = k == K - 1
+                need = bool(np.isin(rows[:, k, 0], _RANDAUG_STATS).any())
+                desc = _lib.RandAugDesc(N, T, H, W, mode if last else _lib.PTX_RESIZE_OUT_U8, K, k, int(need), self.fill[0],
+                                        self.fill[1], self.fill[2], 0)
+                if need:
+                    if stats is None:
+                        stats = torch.empty(N * T * _lib.PTX_RANDAUG_STATS_WORDS, device=f5.device, dtype=torch.int32)
+                    check(lib.ptx_rand_augment_stats(C.byref(desc), C.c_void_p(cur.data_ptr()), rows_p, C.c_void_p(stats.data_ptr()),
+                                                     stream), "ptx_rand_augment_stats")
+                    launches.append("stats")
+                dst = y if last else scratch[k % 2]
+                check(lib.ptx_rand_augment_apply(C.byref(desc), C.c_void_p(cur.data_ptr()), rows_p,
+                                                 C.c_void_p(stats.data_ptr()) if need else None, C.c_void_p(dst.data_ptr()),
+                                                 C.byref(norm) if (last and norm is not None) else None, stream), "ptx_rand_augment_apply")
+                launches.append("apply")
+                cur = dst
+        self.last_launches = tuple(launches)
+        return y
+
+    def __call__(self, frames, params=None):
+        if not isinstance(frames, torch.Tensor):
+            raise PtxError("RandAugment: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
+        if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
+            raise PtxError("RandAugment: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (tuple(frames.shape),))
+        N = frames.shape[0] if frames.dim() == 5 else 1
+        H, W = int(frames.shape[-3]), int(frames.shape[-2])
+        if frames.numel() == 0:
+            raise PtxError("RandAugment: empty batch")
+        if params is not None:                                       # validated before a device is touched
+            params = self.check_params(params, N, H, W)
+        if not frames.is_cuda or frames.dtype != torch.uint8:
+            raise PtxError("RandAugment: frames must be a uint8 CUDA tensor (no CPU fallback)")
+        f5 = frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
+        return self._launch(f5, self._rows_for(N, H, W, params)).view(frames.shape)
+
+
+def _apply_augment(augment, frames_u8, out, dtype, norm, augment_params):
+    """The RandAugment half of TransformFrames / SampleClips with augment=: `frames_u8` is the uint8 output of the stage in front
+    ([N,T,S,S,3] or a lower rank, one clip), the result the requested output of the call."""
+    lead = frames_u8.dim()
+    f5 = frames_u8.view((1,) * (5 - lead) + tuple(frames_u8.shape))
+    rows = augment._rows_for(f5.shape[0], f5.shape[2], f5.shape[3], augment_params)
+    if out == "frames":
+        return augment._launch(f5, rows).view(frames_u8.shape)
+    mode = _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+    y = augment._launch(f5, rows, mode, norm, dtype)
+    if lead == 5:
+        return y
+    return y[0] if lead == 4 else y[0, :, 0]
+
+
+def _apply_stages(color, augment, u8, out, dtype, norm, color_params, augment_params):
+    """The stages behind the resize of TransformFrames / SampleClips: colour, then augment; the last one writes the call's output."""
+    if augment is None:
+        return _apply_color(color, u8, out, dtype, norm, color_params)
+    if color is not None:
+        u8 = _apply_color(color, u8, "frames", torch.float32, norm, color_params)
+    return _apply_augment(augment, u8, out, dtype, norm, augment_params)
+
+
+def _check_augment(augment, who):
+    if augment is not None and not isinstance(augment, RandAugment):
+        raise PtxError("%s: augment must be a pretorched.transforms.RandAugment or None, got %r" % (who, augment))
+    return augment
+
+
 class TransformFrames:
     """Resize + crop (+ flip) of decoded uint8 frames on the device, bit-exact with PIL's bilinear resize, then
     TransformImage's tensor half (`out="tensor"`) or nothing more (`out="frames"`).
@@ -919,14 +1337,20 @@ class TransformFrames:
 
     color: a `ColorJitter` (None: off, the code path without it).  The resize then writes uint8 frames into scratch and the
     colour launch writes the output of `out` / `dtype`; the lists are drawn per clip after every other draw of the call and
-    kept as `color.last_params`; `tf(frames, color_params=p)` applies given lists instead."""
+    kept as `color.last_params`; `tf(frames, color_params=p)` applies given lists instead.
+
+    augment: a `RandAugment` (None: off, the code path without it), run behind the resize and behind `color`: the stage in front
+    writes uint8 scratch and the augment's last position writes the output of `out` / `dtype`.  Its draw comes after every other
+    draw of the call (a seed gives the same geometry and colour with and without it) and is kept as `augment.last_params`;
+    `tf(frames, augment_params=p)` applies a given draw instead."""
 
     CACHE_SIZE = 8
 
     def __init__(self, opts, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, out="tensor",
                  dtype=torch.float32, *, random_crop=False, random_hflip=False, random_vflip=False, vflip=False,
-                 generator=None, random_short_side=None, random_resized_crop=False, color=None):
+                 generator=None, random_short_side=None, random_resized_crop=False, color=None, augment=None):
         self.color = _check_color(color, "TransformFrames")
+        self.augment = _check_augment(augment, "TransformFrames")
         if out not in ("tensor", "frames"):
             raise PtxError("TransformFrames: out must be 'tensor' or 'frames', got %r" % (out,))
         if dtype not in (torch.float32, torch.bfloat16):
@@ -1005,19 +1429,26 @@ class TransformFrames:
             self.random_resized_crop = rrc
         self.per_clip_geometry = self.random_short_side is not None or self.random_resized_crop is not None
         self._resize = None
-        if self.color is not None:                                   # the resize half of a call with colour: this transform,
-            self._resize = copy.copy(self)                           # writing uint8 frames (tables cache and generator shared)
-            self._resize.color, self._resize.out, self._resize.dtype = None, "frames", torch.float32
+        if self.color is not None or self.augment is not None:       # the resize half of a call with colour / augment: this
+            self._resize = copy.copy(self)                           # transform, writing uint8 frames (tables cache and generator shared)
+            self._resize.color, self._resize.augment, self._resize.out, self._resize.dtype = None, None, "frames", torch.float32
 
-    def _call_color(self, frames, params, geometry, color_params):
-        """A call with color=: the resize writes uint8 frames into scratch (every draw of the plain call, in its order), then the
-        colour lists are drawn clip by clip and the apply launch writes the requested output."""
+    def _call_color(self, frames, params, geometry, color_params, augment_params=None):
+        """A call with color= and / or augment=: the resize writes uint8 frames into scratch (every draw of the plain call, in its
+        order), then the colour lists are drawn clip by clip and applied, then the augment's draw; the last stage writes the
+        requested output, the stages in front of it uint8 scratch."""
         rs = self._resize
         if color_params is not None:                                 # validated before a device is touched
+            if self.color is None:
+                raise PtxError("TransformFrames: color_params= needs a transform built with color=ColorJitter(..)")
             color_params = self.color.check_params(color_params)
+        if augment_params is not None:
+            if self.augment is None:
+                raise PtxError("TransformFrames: augment_params= needs a transform built with augment=RandAugment(..)")
+            augment_params = self.augment.check_params(augment_params, None, self.size, self.size)
         u8 = rs(frames, params=params, geometry=geometry)
         self.last_params, self.last_geometry = rs.last_params, rs.last_geometry
-        return _apply_color(self.color, u8, self.out, self.dtype, self.norm, color_params)
+        return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params)
 
     def tables(self, H, W):
         """Host tables for H x W frames (numpy; see build_tables)."""
@@ -1172,7 +1603,7 @@ class TransformFrames:
             self._cache.popitem(last=False)
         return hit
 
-    def __call__(self, frames, params=None, geometry=None, color_params=None):
+    def __call__(self, frames, params=None, geometry=None, color_params=None, augment_params=None):
         """uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3], any H, W  ->
         out="tensor": [N,3,T,S,S] | [3,T,S,S] | [3,S,S] (fp32 or bf16);  out="frames": uint8, same rank, H, W -> S, S.
         A `YUV420` source is taken in place of the frames (converted while the kernel stages its rows: the same bits as
@@ -1185,11 +1616,16 @@ class TransformFrames:
         Both are a table-builder launch plus one resize launch.
         With color= (a `ColorJitter`) the resize writes uint8 frames into scratch and the colour launch writes the output;
         the colour lists are drawn after every other draw of the call, clip by clip (a seed gives the same geometry with and
-        without colour), and kept as `color.last_params`; color_params applies given lists instead."""
-        if self.color is not None:
-            return self._call_color(frames, params, geometry, color_params)
+        without colour), and kept as `color.last_params`; color_params applies given lists instead.
+        With augment= (a `RandAugment`) its positions run behind the resize and behind the colour launch, the last one writing
+        the output; its draw comes after every other draw of the call and is kept as `augment.last_params`; augment_params
+        applies a given draw instead."""
+        if self.color is not None or self.augment is not None:
+            return self._call_color(frames, params, geometry, color_params, augment_params)
         if color_params is not None:
             raise PtxError("TransformFrames: color_params= needs a transform built with color=ColorJitter(..)")
+        if augment_params is not None:
+            raise PtxError("TransformFrames: augment_params= needs a transform built with augment=RandAugment(..)")
         if params is not None and geometry is not None:
             raise PtxError("TransformFrames: params= and geometry= cannot be combined (a geometry row holds the window and flips)")
         if params is not None and self.per_clip_geometry:
@@ -1632,13 +2068,15 @@ class SampleClips:
     `last_geometry`, CPU int32 [N*clips, 10]); `sc(videos, indices=.., geometry=..)` applies given rows instead, on any
     SampleClips.  Output clip j comes from video j // clips.
 
-    color: a `ColorJitter` applied behind the resize, one list per output clip, as for `TransformFrames(.., color=)`."""
+    color: a `ColorJitter` applied behind the resize, one list per output clip, as for `TransformFrames(.., color=)`.
+    augment: a `RandAugment` applied behind the resize and the colour, one draw per output clip, as for `TransformFrames(.., augment=)`."""
 
     def __init__(self, opts, num_frames=16, frame_stride=4, clips=1, sampling="dense", random_start=True, scale=0.875,
                  preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False, random_crop=False, random_hflip=False,
                  random_vflip=False, random_short_side=None, random_resized_crop=False, out="tensor", dtype=torch.float32,
-                 generator=None, color=None):
+                 generator=None, color=None, augment=None):
         self.color = _check_color(color, "SampleClips")
+        self.augment = _check_augment(augment, "SampleClips")
         for name, v in (("num_frames", num_frames), ("frame_stride", frame_stride), ("clips", clips)):
             if not isinstance(v, int) or isinstance(v, bool) or v < 1:
                 raise PtxError("SampleClips: %s must be a positive integer, got %r" % (name, v))
@@ -1652,9 +2090,9 @@ class SampleClips:
         self.out, self.dtype, self.size, self.norm = out, dtype, self.spatial.size, self.spatial.norm
         self.last_indices, self.last_geometry = None, None
         self._resize = None
-        if self.color is not None:                                   # the resize half of a call with colour (see TransformFrames)
+        if self.color is not None or self.augment is not None:       # the resize half of a call with colour / augment (see TransformFrames)
             self._resize = copy.copy(self)
-            self._resize.color, self._resize.out, self._resize.dtype = None, "frames", torch.float32
+            self._resize.color, self._resize.augment, self._resize.out, self._resize.dtype = None, None, "frames", torch.float32
 
     # ---- host only: no device is touched -------------------------------------------------------
     @staticmethod
@@ -1805,7 +2243,7 @@ class SampleClips:
             raise PtxError("SampleClips: videos[%d] is on %s, videos[0] on %s: a batch lives on one device" % (i, devs[i], devs[0]))
         return videos
 
-    def __call__(self, videos, indices=None, geometry=None, color_params=None):
+    def __call__(self, videos, indices=None, geometry=None, color_params=None, augment_params=None):
         """videos: a list / tuple of uint8 CUDA tensors [Tv_i,H_i,W_i,3] of any sizes and lengths on one device | one
         [N,Tv,H,W,3] tensor (N videos) | one [Tv,H,W,3] tensor | a list of `YUV420` sources with planes [Tv,H,W] | one
         `YUV420` with planes [N,Tv,H,W] or [Tv,H,W]  ->  out="tensor": [N*clips,3,T,S,S] (fp32 or bf16); out="frames": uint8
@@ -1815,16 +2253,21 @@ class SampleClips:
         the tap pitches are the maxima over the batch.
         With color= (a `ColorJitter`) the resize writes uint8 clips into scratch and the colour launch writes the output: one
         list per output clip, drawn after every other draw of the call and kept as `color.last_params`; color_params applies
-        given lists instead."""
-        if self.color is not None:
+        given lists instead.  With augment= (a `RandAugment`) its positions run behind the resize and the colour launch, one draw
+        per output clip after every other draw of the call (`augment.last_params`); augment_params applies a given draw instead."""
+        if color_params is not None and self.color is None:
+            raise PtxError("SampleClips: color_params= needs a sampler built with color=ColorJitter(..)")
+        if augment_params is not None and self.augment is None:
+            raise PtxError("SampleClips: augment_params= needs a sampler built with augment=RandAugment(..)")
+        if self.color is not None or self.augment is not None:
             if color_params is not None:                             # validated before a device is touched
                 color_params = self.color.check_params(color_params)
+            if augment_params is not None:
+                augment_params = self.augment.check_params(augment_params, None, self.size, self.size)
             rs = self._resize
             u8 = rs(videos, indices=indices, geometry=geometry)
             self.last_indices, self.last_geometry = rs.last_indices, rs.last_geometry
-            return _apply_color(self.color, u8, self.out, self.dtype, self.norm, color_params)
-        if color_params is not None:
-            raise PtxError("SampleClips: color_params= needs a sampler built with color=ColorJitter(..)")
+            return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params)
         if (indices is None) != (geometry is None):
             raise PtxError("SampleClips: indices= and geometry= are given together (a replay) or not at all (a draw)")
         vids = self._videos(videos)
