@@ -16,6 +16,7 @@ TFIR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_tfir
 YUV16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_yuv16.h")      # 10- / 12-bit YUV 4:2:0 sources
 COLOR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_color.h")      # ColorJitter / RandomGrayscale on uint8 frames
 RANDAUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_randaug.h")  # RandAugment on uint8 frames
+RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_resample.h")  # PIL's other resize filters
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -116,6 +117,10 @@ class ResizeGeom(C.Structure):
 
 PTX_RESIZE_OUT_U8, PTX_RESIZE_OUT_F32, PTX_RESIZE_OUT_BF16 = 0, 1, 2
 PTX_RESIZE_MAX_TAPS = 64
+# ptx_amd_resample.h: Pillow's filter codes (Image.Resampling), and the longest NEAREST walk of the device builder
+(PTX_RESAMPLE_NEAREST, PTX_RESAMPLE_LANCZOS, PTX_RESAMPLE_BILINEAR, PTX_RESAMPLE_BICUBIC, PTX_RESAMPLE_BOX,
+ PTX_RESAMPLE_HAMMING) = range(6)
+PTX_RESAMPLE_NEAREST_MAX_EXTENT = 65536
 PTX_STEM_SRC_BF16_NCDHW, PTX_STEM_SRC_U8_NTHWC = 0, 1       # ptx_conv_stem_bf16_fwd: where the stem reads its input
 PTX_VIEWS_MAX_CROPS = 4
 PTX_VIEWS_SHARE_AUTO, PTX_VIEWS_SHARE_ALWAYS, PTX_VIEWS_SHARE_NEVER = 0, 1, 2
@@ -398,6 +403,15 @@ SIGNATURES_RANDAUG = {
 }
 
 
+# include/ptx_amd_resample.h: the per-clip table builders for PIL's other resize filters (csrc/pack_layout.hip,
+# csrc/resize_clips.hip), bound the same way (tests/test_resample_frames_host.py): their bilinear twins' signatures with the
+# filter code behind the geometry rows
+SIGNATURES_RESAMPLE = {
+    "ptx_resize_build_tables_filter": (C.c_int, [C.POINTER(ResizeDesc), _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ptx_resize_build_tables_clips_filter": (C.c_int, [C.POINTER(ResizeDesc), _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -432,7 +446,8 @@ def lib():
                 "this package has no CPU / eager fallback" % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
-                list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()):
+                list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
+                list(SIGNATURES_RESAMPLE.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

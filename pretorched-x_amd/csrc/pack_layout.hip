@@ -265,10 +265,13 @@ __global__ void __launch_bounds__(256) fold_kw_frames_u8_kernel(const unsigned c
 }
 
 // ---------------------------------------------------------------------------------------------
-// uint8 frames [N][T][H][W][C] -> bilinear resize + crop (+ flip), bit-exact with PIL's 8-bit resampling
-// (TransformImage's PIL half, utils.py:53-64).  The host builds PIL's fixed-point tables (per output index: first
-// input index, tap count, 2^22-scaled coefficients), with crop and flip folded in; this kernel is integer work only:
+// uint8 frames [N][T][H][W][C] -> resize (bilinear, or any other PIL filter: the filter is in the tables) + crop (+ flip),
+// bit-exact with PIL's 8-bit resampling (TransformImage's PIL half, utils.py:53-64).  The host builds PIL's fixed-point
+// tables (per output index: first input index, tap count, 2^22-scaled coefficients), with crop and flip folded in; this
+// kernel is integer work only:
 //   horizontal pass -> uint8 intermediate -> vertical pass,  out = clip8((2^21 + sum k[j] * in[lo + j]) >> 22).
+// Coefficients may be negative (ptx_amd_resample.h): |k| < 2^23 for __mul24, 255 * sum |k| + 2^21 < 2^31 for the accumulator,
+// and >> is arithmetic, so a negative sum clips to 0.
 // One workgroup per (frame, band of output rows).  It copies the tables it needs to LDS (entries clamped to the frame;
 // the coefficients too when they fit), then each wave stages one referenced input row at a time in LDS (only the
 // column span the column table references; 16-byte loads between a byte head and tail, LDS offset = global address
@@ -513,12 +516,10 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[e] += __mul24(k, (int)((v >> (8 * e)) & 255u));
                 }
-                // coefficients and pixels are >= 0, so the sums are too: clamp with an unsigned shift + min.  (The signed
-                // clamp of two neighbouring sums is selected as one v_ashr_pk_u8_i32, whose result hipcc then ORs with
-                // the other two bytes as if its upper half were zero; on gfx950 that upper half came back non-zero.)
+                // a negative sum (negative coefficients) gives 0, and no packed shift-and-saturate: see resize_clip8
                 unsigned o = 0;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o |= min((unsigned)acc[e] >> kResizeBits, 255u) << (8 * e);
+                for (int e = 0; e < 4; ++e) o |= resize_clip8(acc[e]) << (8 * e);
                 unsigned char* ob = yo + ((size_t)frame * d.Ho + row) * WoC + q * 4;
                 if (pl.vec_store) {
                     *reinterpret_cast<unsigned*>(ob) = o;
@@ -585,20 +586,24 @@ __global__ void __launch_bounds__(256) resize_frames_u8_kernel(ptx_resize_desc d
 
 // ---------------------------------------------------------------------------------------------
 // The per-clip tables of ptx_resize_frames_*_tables, built on the device from one ptx_resize_geom per clip
-// (ptx_resize_build_tables): one thread per (clip, axis, output index) restates PIL's precompute_coeffs +
-// normalize_coeffs_8bpc for its entry in IEEE fp64, in the operation order of transforms.resize_axis_table -- the
-// host builder the fixed-window launch uses -- so the entry has that builder's bits.  Contraction is OFF: hipcc
-// otherwise fuses (i + 0.5) * scale - fs, 1 - |..| * ss and w * 2^22 + 0.5 into FMAs, which moves the last bit of
-// `center` and of the weights and with it a coefficient here and there.  The sum of the weights is taken sequentially.
-// Garbage rows are safe: the box is clamped into the frame, the resized extent to >= 1, the window into the resized
-// frame, the table index into [0, extent), n to the pitch; the resize kernel clamps the entries once more.
+// (ptx_resize_build_tables, ptx_resize_build_tables_filter): one thread per (clip, axis, output index) restates PIL's
+// precompute_coeffs + normalize_coeffs_8bpc for its entry in IEEE fp64, in the operation order of
+// transforms.resize_axis_table -- the host builder the fixed-window launch uses -- so the entry has that builder's bits.
+// Contraction is OFF: hipcc otherwise fuses (i + 0.5) * scale - fs, 1 - |..| * ss, the bicubic polynomial and w * 2^22 + 0.5
+// into FMAs, which moves the last bit of `center` and of the weights and with it a coefficient here and there.  The sum of
+// the weights is taken sequentially.  `filter` is a PTX_RESAMPLE_* code of BOX, BILINEAR, BICUBIC (PIL's filter functions,
+// support 0.5 / 1 / 2) or NEAREST (PIL's affine walk: one tap at (int)(a / 2 + a + a + ...), i sequential additions for index
+// i, because the walk's sum differs from a product in the last bit); the bilinear branch is the code it was.
+// Garbage rows are safe: the box is clamped into the frame, the resized extent to >= 1 (NEAREST: and to the longest walk),
+// the window into the resized frame, the table index into [0, extent), n to the pitch; the resize kernel clamps the entries
+// once more.
 // ---------------------------------------------------------------------------------------------
 // The entry of (clip, axis entry e) for frames of H x W: the body shared by resize_build_tables_kernel (H, W of the
 // descriptor) and resize_build_tables_clips_kernel (resize_clips.hip: H, W of the clip's source row).
 __device__ __forceinline__ void resize_build_entry(const ptx_resize_desc& d, int H, int W, int clip, int e,
-                                                   const ptx_resize_geom* __restrict__ geoms, int* __restrict__ row_lo,
-                                                   int* __restrict__ row_n, int* __restrict__ row_k, int* __restrict__ col_lo,
-                                                   int* __restrict__ col_n, int* __restrict__ col_k) {
+                                                   const ptx_resize_geom* __restrict__ geoms, int filter,
+                                                   int* __restrict__ row_lo, int* __restrict__ row_n, int* __restrict__ row_k,
+                                                   int* __restrict__ col_lo, int* __restrict__ col_n, int* __restrict__ col_k) {
 #pragma clang fp contract(off)
     const bool rows = e < d.Ho;
     const int o = rows ? e : e - d.Ho;                               // output index on this axis
@@ -606,7 +611,8 @@ __device__ __forceinline__ void resize_build_entry(const ptx_resize_desc& d, int
     const ptx_resize_geom g = geoms[clip];
     const int origin = min(max(rows ? g.box_top : g.box_left, 0), extent - 1);
     const int n_in = min(max(rows ? g.box_h : g.box_w, 1), extent - origin);
-    const int n_out = max(rows ? g.h : g.w, 1);
+    int n_out = max(rows ? g.h : g.w, 1);
+    if (filter == PTX_RESAMPLE_NEAREST) n_out = min(n_out, PTX_RESAMPLE_NEAREST_MAX_EXTENT);   // bounds the walk below
     const int start = min(max(rows ? g.top : g.left, 0), max(n_out - S, 0));
     const int flip = (rows ? g.vflip : g.hflip) != 0;
     const int i = min(start + (flip ? S - 1 - o : o), n_out - 1);   // index in the resized box
@@ -614,8 +620,15 @@ __device__ __forceinline__ void resize_build_entry(const ptx_resize_desc& d, int
     int* lo_t = rows ? row_lo : col_lo;
     int* n_t = rows ? row_n : col_n;
     int* k = (rows ? row_k : col_k) + at * taps;
-    if (n_in == n_out) {                                             // not resampled: one tap of 2^22
-        lo_t[at] = origin + i;
+    if (n_in == n_out || filter == PTX_RESAMPLE_NEAREST) {           // one tap of 2^22: not resampled, or PIL's nearest index
+        int idx = i;
+        if (n_in != n_out) {
+            const double a = (double)n_in / (double)n_out;
+            double xo = a * 0.5;
+            for (int t = 0; t < i; ++t) xo = xo + a;
+            idx = min(max((int)fmin(xo, 2147483647.0), 0), n_in - 1);
+        }
+        lo_t[at] = origin + idx;
         n_t[at] = 1;
         k[0] = 1 << kResizeBits;
         for (int j = 1; j < taps; ++j) k[j] = 0;
@@ -623,14 +636,24 @@ __device__ __forceinline__ void resize_build_entry(const ptx_resize_desc& d, int
     }
     const double scale = (double)n_in / (double)n_out;
     const double fs = scale > 1.0 ? scale : 1.0;
+    const double support = (filter == PTX_RESAMPLE_BOX ? 0.5 : filter == PTX_RESAMPLE_BICUBIC ? 2.0 : 1.0) * fs;
     const double ss = 1.0 / fs;
     const double center = ((double)i + 0.5) * scale;
-    // C's (int) truncates; both values are >= -0.5 and, clamped in double first, inside int whatever the row held
-    const int lo = min(max((int)fmin(center - fs + 0.5, 2147483647.0), 0), n_in - 1);   // below n_in for every real row
-    const int hi = min((int)fmin(center + fs + 0.5, 2147483647.0), n_in);
+    // C's (int) truncates (a value in (-1, 0) gives 0, a lower one is clamped to 0 as PIL clamps it); clamped in double
+    // first, both values lie inside int whatever the row held
+    const int lo = min(max((int)fmin(fmax(center - support + 0.5, -2147483648.0), 2147483647.0), 0), n_in - 1);   // below n_in for every real row
+    const int hi = min((int)fmin(center + support + 0.5, 2147483647.0), n_in);
     const int n = min(max(hi - lo, 0), taps);
     auto weight = [&](int j) {
-        const double w = 1.0 - fabs(((double)j + (double)lo - center + 0.5) * ss);
+        double x = ((double)j + (double)lo - center + 0.5) * ss;
+        if (filter == PTX_RESAMPLE_BOX) return x > -0.5 && x <= 0.5 ? 1.0 : 0.0;
+        if (filter == PTX_RESAMPLE_BICUBIC) {                        // PIL's bicubic_filter, a = -0.5: (a + 2) = 1.5, (a + 3) = 2.5
+            if (x < 0.0) x = -x;
+            if (x < 1.0) return (1.5 * x - 2.5) * x * x + 1.0;
+            if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5;
+            return 0.0;
+        }
+        const double w = 1.0 - fabs(x);
         return w > 0.0 ? w : 0.0;
     };
     double ww = 0.0;
@@ -642,21 +665,35 @@ __device__ __forceinline__ void resize_build_entry(const ptx_resize_desc& d, int
         if (j < n) {
             double w = weight(j);
             if (ww != 0.0) w = w / ww;
-            c = (int)(w * 4194304.0 + 0.5);
+            c = w < 0.0 ? (int)(-0.5 + w * 4194304.0) : (int)(w * 4194304.0 + 0.5);
         }
         k[j] = c;
     }
 }
 
 __global__ void __launch_bounds__(256) resize_build_tables_kernel(ptx_resize_desc d, const ptx_resize_geom* __restrict__ geoms,
-                                                                  int* __restrict__ row_lo, int* __restrict__ row_n,
+                                                                  int filter, int* __restrict__ row_lo, int* __restrict__ row_n,
                                                                   int* __restrict__ row_k, int* __restrict__ col_lo,
                                                                   int* __restrict__ col_n, int* __restrict__ col_k) {
     const int per_clip = d.Ho + d.Wo;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)d.N * per_clip) return;
     const int clip = (int)(idx / per_clip), e = (int)(idx - (long long)clip * per_clip);
-    resize_build_entry(d, d.H, d.W, clip, e, geoms, row_lo, row_n, row_k, col_lo, col_n, col_k);
+    resize_build_entry(d, d.H, d.W, clip, e, geoms, filter, row_lo, row_n, row_k, col_lo, col_n, col_k);
+}
+
+// The filters the device builder takes, or the reason it does not (no device needed).
+static int resize_filter_check(int filter, const char* who) {
+    switch (filter) {
+        case PTX_RESAMPLE_NEAREST: case PTX_RESAMPLE_BOX: case PTX_RESAMPLE_BILINEAR: case PTX_RESAMPLE_BICUBIC:
+            return PTX_OK;
+        case PTX_RESAMPLE_HAMMING: case PTX_RESAMPLE_LANCZOS:
+            return fail(PTX_ERR_UNSUPPORTED, "%s: filter=%d (%s): its weights are sin / cos of the host's C library, which the "
+                        "device cannot be promised to equal bit for bit; the device builder takes nearest, box, bilinear and "
+                        "bicubic (build the table on the host)", who, filter, filter == PTX_RESAMPLE_HAMMING ? "hamming" : "lanczos");
+        default:
+            return fail(PTX_ERR_INVALID, "%s: filter=%d is not a PTX_RESAMPLE_* code", who, filter);
+    }
 }
 
 static unsigned grid_for(size_t work_items) {
@@ -1254,19 +1291,33 @@ extern "C" int ptx_resize_frames_yuv420p16_tables(const ptx_resize_desc* desc, c
                              true, src);
 }
 
-extern "C" int ptx_resize_build_tables(const ptx_resize_desc* desc, const ptx_resize_geom* geoms, int32_t* row_lo,
-                                       int32_t* row_n, int32_t* row_k, int32_t* col_lo, int32_t* col_n, int32_t* col_k,
-                                       ptx_stream_t stream) {
-    const char* who = "ptx_resize_build_tables";
+static int resize_build_tables_run(const ptx_resize_desc* desc, const ptx_resize_geom* geoms, int filter, int32_t* row_lo,
+                                   int32_t* row_n, int32_t* row_k, int32_t* col_lo, int32_t* col_n, int32_t* col_k,
+                                   ptx_stream_t stream, const char* who) {
     ResizePlan p;
     int s = resize_plan(desc, nullptr, &p, who);                     // the extents and pitches the launch will be given
     if (s) return s;
+    if ((s = resize_filter_check(filter, who))) return s;
     if (!geoms || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k) return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     const int64_t entries = (int64_t)desc->N * ((int64_t)desc->Ho + desc->Wo);
     if (entries > INT32_MAX) return fail(PTX_ERR_UNSUPPORTED, "%s: N * (Ho + Wo) exceeds 32-bit indexing", who);
     hipLaunchKernelGGL(resize_build_tables_kernel, dim3((unsigned)cdiv64(entries, 256)), dim3(256), 0, (hipStream_t)stream,
-                       *desc, geoms, row_lo, row_n, row_k, col_lo, col_n, col_k);
+                       *desc, geoms, filter, row_lo, row_n, row_k, col_lo, col_n, col_k);
     return hip_check(hipGetLastError(), who);
+}
+
+extern "C" int ptx_resize_build_tables(const ptx_resize_desc* desc, const ptx_resize_geom* geoms, int32_t* row_lo,
+                                       int32_t* row_n, int32_t* row_k, int32_t* col_lo, int32_t* col_n, int32_t* col_k,
+                                       ptx_stream_t stream) {
+    return resize_build_tables_run(desc, geoms, PTX_RESAMPLE_BILINEAR, row_lo, row_n, row_k, col_lo, col_n, col_k, stream,
+                                   "ptx_resize_build_tables");
+}
+
+extern "C" int ptx_resize_build_tables_filter(const ptx_resize_desc* desc, const ptx_resize_geom* geoms, int32_t filter,
+                                              int32_t* row_lo, int32_t* row_n, int32_t* row_k, int32_t* col_lo, int32_t* col_n,
+                                              int32_t* col_k, ptx_stream_t stream) {
+    return resize_build_tables_run(desc, geoms, filter, row_lo, row_n, row_k, col_lo, col_n, col_k, stream,
+                                   "ptx_resize_build_tables_filter");
 }
 
 // y[r][0..W) = x[r][0..W), y[r][W..ld) = 0: gives rows whose length is not a multiple of 4 floats a 16-byte pitch

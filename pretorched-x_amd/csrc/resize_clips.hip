@@ -10,7 +10,7 @@
 namespace ptx {
 
 __global__ void __launch_bounds__(256) resize_build_tables_clips_kernel(ptx_resize_desc d, const ptx_clip_src* __restrict__ srcs,
-                                                                        const ptx_resize_geom* __restrict__ geoms,
+                                                                        const ptx_resize_geom* __restrict__ geoms, int filter,
                                                                         int* __restrict__ row_lo, int* __restrict__ row_n,
                                                                         int* __restrict__ row_k, int* __restrict__ col_lo,
                                                                         int* __restrict__ col_n, int* __restrict__ col_k) {
@@ -19,7 +19,7 @@ __global__ void __launch_bounds__(256) resize_build_tables_clips_kernel(ptx_resi
     if (idx >= (long long)d.N * per_clip) return;
     const int clip = (int)(idx / per_clip), e = (int)(idx - (long long)clip * per_clip);
     const int H = min(max(srcs[clip].H, 1), d.H), W = min(max(srcs[clip].W, 1), d.W);
-    resize_build_entry(d, H, W, clip, e, geoms, row_lo, row_n, row_k, col_lo, col_n, col_k);
+    resize_build_entry(d, H, W, clip, e, geoms, filter, row_lo, row_n, row_k, col_lo, col_n, col_k);
 }
 
 }  // namespace ptx
@@ -106,18 +106,34 @@ extern "C" int ptx_resize_clips_yuv420p16(const ptx_resize_desc* desc, const ptx
     return resize_clips_run(desc, nullptr, srcs, frame_idx, row_lo, row_n, row_k, col_lo, col_n, col_k, y, norm, stream, who, true);
 }
 
-extern "C" int ptx_resize_build_tables_clips(const ptx_resize_desc* desc, const ptx_clip_src* srcs, const ptx_resize_geom* geoms,
-                                             int32_t* row_lo, int32_t* row_n, int32_t* row_k, int32_t* col_lo, int32_t* col_n,
-                                             int32_t* col_k, ptx_stream_t stream) {
-    const char* who = "ptx_resize_build_tables_clips";
+static int resize_build_tables_clips_run(const ptx_resize_desc* desc, const ptx_clip_src* srcs, const ptx_resize_geom* geoms,
+                                         int filter, int32_t* row_lo, int32_t* row_n, int32_t* row_k, int32_t* col_lo,
+                                         int32_t* col_n, int32_t* col_k, ptx_stream_t stream, const char* who) {
     ResizePlan p;
     int s = resize_plan(desc, nullptr, &p, who);                     // the extents and pitches the launch will be given
     if (s) return s;
+    if ((s = resize_filter_check(filter, who))) return s;
     if (!srcs || !geoms || !row_lo || !row_n || !row_k || !col_lo || !col_n || !col_k)
         return fail(PTX_ERR_INVALID, "%s: null pointer", who);
     const int64_t entries = (int64_t)desc->N * ((int64_t)desc->Ho + desc->Wo);
     if (entries > INT32_MAX) return fail(PTX_ERR_UNSUPPORTED, "%s: N * (Ho + Wo) exceeds 32-bit indexing", who);
     hipLaunchKernelGGL(resize_build_tables_clips_kernel, dim3((unsigned)cdiv64(entries, 256)), dim3(256), 0, (hipStream_t)stream,
-                       *desc, srcs, geoms, row_lo, row_n, row_k, col_lo, col_n, col_k);
+                       *desc, srcs, geoms, filter, row_lo, row_n, row_k, col_lo, col_n, col_k);
     return hip_check(hipGetLastError(), who);
+}
+
+extern "C" int ptx_resize_build_tables_clips(const ptx_resize_desc* desc, const ptx_clip_src* srcs, const ptx_resize_geom* geoms,
+                                             int32_t* row_lo, int32_t* row_n, int32_t* row_k, int32_t* col_lo, int32_t* col_n,
+                                             int32_t* col_k, ptx_stream_t stream) {
+    return resize_build_tables_clips_run(desc, srcs, geoms, PTX_RESAMPLE_BILINEAR, row_lo, row_n, row_k, col_lo, col_n, col_k,
+                                         stream, "ptx_resize_build_tables_clips");
+}
+
+// The same for a filter (include/ptx_amd_resample.h).
+extern "C" int ptx_resize_build_tables_clips_filter(const ptx_resize_desc* desc, const ptx_clip_src* srcs,
+                                                    const ptx_resize_geom* geoms, int32_t filter, int32_t* row_lo, int32_t* row_n,
+                                                    int32_t* row_k, int32_t* col_lo, int32_t* col_n, int32_t* col_k,
+                                                    ptx_stream_t stream) {
+    return resize_build_tables_clips_run(desc, srcs, geoms, filter, row_lo, row_n, row_k, col_lo, col_n, col_k, stream,
+                                         "ptx_resize_build_tables_clips_filter");
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "ptx_common.h"
 #include "../../include/ptx_amd_yuv16.h"
+#include "../../include/ptx_amd_resample.h"
 #include <algorithm>
 
 namespace ptx {
@@ -32,6 +33,15 @@ __device__ __forceinline__ void resize_entry(const int* __restrict__ lo_t, const
 }
 
 __device__ __forceinline__ int clip8(int v) { return min(max(v, 0), 255); }
+
+// clip8(sum >> kResizeBits) of a resampling sum as an unsigned byte, for the pass that packs four of them into a word.
+// Coefficients may be negative (bicubic, Lanczos, Hamming: ptx_amd_resample.h), so a sum may be: clamp below, UNSIGNED shift,
+// min -- yuv_clip8's form, one v_max_i32 more per byte than the unsigned shift + min it replaces, and for a sum >= 0 the same
+// bits.  The signed clamp of the SHIFTED value is not used there: of two neighbouring sums it is selected as one
+// v_ashr_pk_u8_i32, whose result hipcc then ORs with the other two bytes as if its upper half were zero; on gfx950 that upper
+// half came back non-zero.  (Clamping into [0, 2^30 - 1] before the shift is one v_med3_i32 and no instruction more than
+// before, but it changed the register allocation of the whole kernel and measured 1 % slower on the fp32 output: DESIGN 3.34.)
+__device__ __forceinline__ unsigned resize_clip8(int sum) { return min((unsigned)max(sum, 0) >> kResizeBits, 255u); }
 
 // The bytes [off, end) of input row `row` that the column table references, relative to the 16-byte aligned address g:
 // a byte head [off, vb), 16-byte pieces [vb, ve), a byte tail [ve, end).  g itself may lie before the row: only
@@ -384,9 +394,17 @@ inline int yuv_check(const ptx_yuv420p16_src* s, int C, int H, int W, const char
     return PTX_OK;
 }
 
-// Launch shape of resize_frames_u8_kernel, or the reason there is none.  taps_h is the widest row's tap count, and a
-// row of support s has more than 2 s - 1 taps, so output rows advance by at most taps_h / 2 input rows: a band of b
-// output rows references at most b * taps_h / 2 + taps_h + 1 input rows (b when taps_h == 1: the axis is not resampled).
+// Launch shape of resize_frames_u8_kernel, or the reason there is none.  taps_h is the widest row's tap count.  For a filter
+// of support >= 1 (bilinear, Hamming, bicubic, Lanczos) a row of support s has more than 2 s - 1 taps, so output rows advance
+// by at most taps_h / 2 input rows: a band of b output rows references at most b * taps_h / 2 + taps_h + 1 input rows (b when
+// taps_h == 1: the axis is not resampled), and rows_of(b) below is that bound: the band is one chunk.
+// It is NOT a bound for the two filters whose taps do not overlap: BOX (support 0.5: rows advance by about taps_h - 1, so a
+// band references about b * (taps_h - 1) rows) and a one-tap NEAREST table of a down-scale (lo jumps by the scale while
+// rows_of(b) = b).  Those stay correct because the kernel never relies on rows_of: its chunk loop (`while (r < y1)`) takes
+// as many output rows as fit lds_rows intermediate rows and starts another chunk for the rest, and one output row always fits
+// (n is clamped to lds_rows >= taps_h).  The cost is more, smaller chunks per band (a barrier pair each), and for NEAREST
+// the horizontal pass also resamples the unreferenced input rows between two referenced ones, because a chunk stages the
+// whole span [lo0, hi0).  Bilinear launch shapes are what they were.
 inline int resize_plan(const ptx_resize_desc* d, const void* y, ResizePlan* p, const char* who) {
     if (!d) return fail(PTX_ERR_INVALID, "%s: null descriptor", who);
     if (d->N <= 0 || d->T <= 0 || d->H <= 0 || d->W <= 0 || d->Ho <= 0 || d->Wo <= 0)

@@ -202,10 +202,10 @@ __global__ void __launch_bounds__(256) resize_views_u8_kernel(ptx_views_desc d, 
 #pragma unroll
                         for (int e = 0; e < 4; ++e) acc[e] += __mul24(kc, (int)((v >> (8 * e)) & 255u));
                     }
-                    // sums of non-negative terms: unsigned shift + min (resize_frames_u8_kernel says why not the signed clamp)
+                    // a negative sum (negative coefficients) gives 0, and no packed shift-and-saturate: see resize_clip8
                     unsigned o = 0;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) o |= min((unsigned)acc[e] >> kResizeBits, 255u) << (8 * e);
+                    for (int e = 0; e < 4; ++e) o |= resize_clip8(acc[e]) << (8 * e);
                     unsigned char* ob = yo + (size_t)(row - wr) * SC + q * 4;
                     if (pl.vec_store) {
                         *reinterpret_cast<unsigned*>(ob) = o;

@@ -8,8 +8,8 @@ uint8 frames:
 * `FramesToTensor` is the tensor half alone (same fp32 operations in the same order: bit-identical), for frames
   that already have the model's input size.  Models go one step further with `model.forward_frames`, which
   fuses it into the stem's fold kernel so the fp32 clip never exists in HBM.
-* `TransformFrames` is both halves in one HIP launch: bilinear resize + crop (+ flips) of frames of
-  any size, then either the normalised clip (`out="tensor"`) or the resized uint8 frames (`out="frames"`, what
+* `TransformFrames` is both halves in one HIP launch: resize (bilinear, or with `interpolation=` any other Pillow filter:
+  nearest, box, hamming, bicubic, lanczos -- the filter lives in the tables) + crop (+ flips) of frames of any size, then either the normalised clip (`out="tensor"`) or the resized uint8 frames (`out="frames"`, what
   `forward_frames(.., transform=tf)` takes).  PIL resamples uint8 images in integer arithmetic (22-bit
   fixed-point coefficients, horizontal pass, uint8 intermediate, vertical pass); the coefficient tables are
   built here on the host in float64 exactly as PIL builds them and the kernel does integer work only, so the
@@ -452,17 +452,144 @@ def crop_window(h, w, S, crop="center"):
     return top, left
 
 
-def resize_axis_table(n_in, n_out):
-    """PIL's bilinear coefficients for one axis (precompute_coeffs + normalize_coeffs_8bpc): for every output index
-    the first input index `lo`, the tap count `n` and `n` int32 coefficients (2**22 fixed point), as
-    (lo[n_out], n[n_out], k[n_out][taps]) with taps = max(n).  An axis that is not resampled is one tap of 2**22."""
+INTERPOLATIONS = ("nearest", "lanczos", "bilinear", "bicubic", "box", "hamming")     # by Pillow's code (the PTX_RESAMPLE_* codes)
+DEVICE_INTERPOLATIONS = ("nearest", "box", "bilinear", "bicubic")                   # what the device table builder takes
+_SUPPORT = {"box": 0.5, "bilinear": 1.0, "hamming": 1.0, "bicubic": 2.0, "lanczos": 3.0}   # Resample.c's filter supports
+
+
+def check_interpolation(interpolation, who="TransformFrames"):
+    """The canonical name of a resize filter: one of INTERPOLATIONS as a string, Pillow's integer code, or any enum whose
+    `.value` is one of those (PIL.Image.Resampling, torchvision's InterpolationMode); anything else raises."""
+    v = interpolation
+    if not isinstance(v, (str, int)) and isinstance(getattr(v, "value", None), (str, int)):
+        v = v.value
+    if isinstance(v, str) and v in INTERPOLATIONS:
+        return v
+    if isinstance(v, int) and not isinstance(v, bool) and 0 <= v < len(INTERPOLATIONS):
+        return INTERPOLATIONS[int(v)]
+    raise PtxError("%s: interpolation must be one of %s, Pillow's code 0..5 or an enum of those, got %r" % (
+        who, ", ".join(repr(n) for n in ("nearest", "box", "bilinear", "hamming", "bicubic", "lanczos")), interpolation))
+
+
+def _filter_weight(name):
+    """Resample.c's filter functions, operation for operation (Python floats are C doubles; math.sin / math.cos are the C
+    library's, as Pillow calls them -- numpy's vector routines may differ in the last bit)."""
+    if name == "box":
+        return lambda x: 1.0 if -0.5 < x <= 0.5 else 0.0
+    if name == "bilinear":
+        def bilinear(x):
+            x = -x if x < 0.0 else x
+            return 1.0 - x if x < 1.0 else 0.0
+        return bilinear
+    if name == "hamming":
+        c54, c46 = float(np.float32(0.54)), float(np.float32(0.46))    # 0.54f, 0.46f in the C source
+        def hamming(x):
+            x = -x if x < 0.0 else x
+            if x == 0.0:
+                return 1.0
+            if x >= 1.0:
+                return 0.0
+            x = x * math.pi
+            return math.sin(x) / x * (c54 + c46 * math.cos(x))
+        return hamming
+    if name == "bicubic":
+        a = -0.5
+        def bicubic(x):
+            x = -x if x < 0.0 else x
+            if x < 1.0:
+                return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+            if x < 2.0:
+                return (((x - 5) * x + 8) * x - 4) * a
+            return 0.0
+        return bicubic
+
+    def sinc(x):
+        if x == 0.0:
+            return 1.0
+        x = x * math.pi
+        return math.sin(x) / x
+    return lambda x: sinc(x) * sinc(x / 3) if -3.0 <= x < 3.0 else 0.0          # lanczos: a truncated sinc
+
+
+_FILTER_TABLES = collections.OrderedDict()                # (n_in, n_out, filter) -> read-only (lo, n, k)
+_FILTER_TABLES_MAX = 256
+
+
+def _filter_axis_table(n_in, n_out, name):
+    """resize_axis_table for the filters other than bilinear: a scalar restatement of precompute_coeffs +
+    normalize_coeffs_8bpc (and of ImagingScaleAffine's index walk for nearest), paid once per (n_in, n_out, filter)."""
+    key = (n_in, n_out, name)
+    hit = _FILTER_TABLES.get(key)
+    if hit is not None:
+        _FILTER_TABLES.move_to_end(key)
+        return hit
+    if name == "nearest":                                  # xo = a * 0.5; idx[x] = (int)xo; xo += a -- sequential in fp64
+        a = n_in / n_out
+        xo, lo = a * 0.5, np.empty(n_out, np.int32)
+        for x in range(n_out):
+            lo[x] = min(int(xo), n_in - 1)
+            xo += a
+        hit = (lo, np.ones(n_out, np.int32), np.full((n_out, 1), 1 << PRECISION_BITS, np.int32))
+    else:
+        weight = _filter_weight(name)
+        scale = n_in / n_out
+        fs = max(scale, 1.0)
+        support = _SUPPORT[name] * fs
+        ksize = int(math.ceil(support)) * 2 + 1
+        ss = 1.0 / fs
+        one = float(1 << PRECISION_BITS)
+        lo, n, k = np.empty(n_out, np.int32), np.empty(n_out, np.int32), np.zeros((n_out, ksize), np.int32)
+        for xx in range(n_out):
+            center = (xx + 0.5) * scale
+            xmin = max(int(center - support + 0.5), 0)     # int() truncates, as C's (int)
+            xmax = min(int(center + support + 0.5), n_in) - xmin
+            w = [weight((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+            ww = 0.0
+            for v in w:
+                ww += v
+            if ww != 0.0:
+                w = [v / ww for v in w]
+            k[xx, :xmax] = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
+            lo[xx], n[xx] = xmin, xmax
+        hit = (lo, n, np.ascontiguousarray(k[:, :int(n.max())]))
+    for a_ in hit:
+        a_.flags.writeable = False
+    _FILTER_TABLES[key] = hit
+    while len(_FILTER_TABLES) > _FILTER_TABLES_MAX:
+        _FILTER_TABLES.popitem(last=False)
+    return hit
+
+
+def check_coefficients(k, who="TransformFrames"):
+    """What the kernels need of a coefficient table k[entries][taps] (ptx_amd_resample.h): every |k| < 2**23 (the 24-bit
+    multiply) and per entry 255 * sum|k| + 2**21 < 2**31 (the 32-bit accumulator), else PtxError.  Pillow's own tables of every
+    filter keep far inside both (the largest sum|k| is about 1.55 * 2**22)."""
+    k = np.abs(np.asarray(k).astype(np.int64))
+    if k.size and int(k.max()) >= 1 << 23:
+        raise PtxError("%s: a resize coefficient of magnitude %d is not below 2**23 (the kernels multiply 24-bit integers)" % (
+            who, int(k.max())))
+    total = k.reshape(k.shape[0], -1).sum(axis=1) if k.ndim > 1 else k
+    if total.size and 255 * int(total.max()) + (1 << (PRECISION_BITS - 1)) >= 1 << 31:
+        raise PtxError("%s: a resize table entry with sum|k| = %d overflows the 32-bit accumulator (255 * sum|k| + 2**21 must "
+                       "stay below 2**31)" % (who, int(total.max())))
+
+
+def resize_axis_table(n_in, n_out, interpolation="bilinear"):
+    """PIL's coefficients of a resize filter for one axis (precompute_coeffs + normalize_coeffs_8bpc): for every output
+    index the first input index `lo`, the tap count `n` and `n` int32 coefficients (2**22 fixed point; negative ones where
+    the filter has negative lobes), as (lo[n_out], n[n_out], k[n_out][taps]) with taps = max(n).  An axis that is not
+    resampled is one tap of 2**22 for every filter (PIL skips that pass).  "nearest" is PIL's affine index walk as one-tap
+    entries.  Tables of the filters other than bilinear are cached and read-only."""
     n_in, n_out = int(n_in), int(n_out)
     if n_in <= 0 or n_out <= 0:
         raise PtxError("TransformFrames: non-positive extent (%d -> %d)" % (n_in, n_out))
     if n_in == n_out:
         return (np.arange(n_out, dtype=np.int32), np.ones(n_out, np.int32),
                 np.full((n_out, 1), 1 << PRECISION_BITS, np.int32))
-    scale = n_in / n_out
+    name = interpolation if interpolation == "bilinear" else check_interpolation(interpolation)
+    if name != "bilinear":
+        return _filter_axis_table(n_in, n_out, name)
+    scale = n_in / n_out                                   # the bilinear branch: vectorised, its bits pinned by the tests
     fs = max(scale, 1.0)
     support = 1.0 * fs
     ksize = int(math.ceil(support)) * 2 + 1
@@ -489,29 +616,34 @@ def _select(table, start, count, reverse=False):
     return np.ascontiguousarray(lo), np.ascontiguousarray(n), np.ascontiguousarray(k[:, :taps])
 
 
-def _check_taps(rows, cols, H, W, h, w):
+def _check_taps(rows, cols, H, W, h, w, interpolation="bilinear", who="TransformFrames"):
+    """The tap cap and the coefficient bounds of a pair of tables (see check_coefficients)."""
     for name, t in (("rows", rows), ("columns", cols)):
         if t[2].shape[1] > _lib.PTX_RESIZE_MAX_TAPS:
-            raise PtxError("TransformFrames: down-scaling the %s of a %dx%d frame to %dx%d needs %d taps, the kernel's cap is "
-                           "PTX_RESIZE_MAX_TAPS = %d" % (name, H, W, h, w, t[2].shape[1], _lib.PTX_RESIZE_MAX_TAPS))
+            raise PtxError("%s: down-scaling the %s of a %dx%d frame to %dx%d%s needs %d taps, the kernel's cap is "
+                           "PTX_RESIZE_MAX_TAPS = %d" % (who, name, H, W, h, w, "" if interpolation == "bilinear" else
+                                                         " with the %s filter" % interpolation, t[2].shape[1],
+                                                         _lib.PTX_RESIZE_MAX_TAPS))
+        check_coefficients(t[2], who)
 
 
-def build_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False):
+def build_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False,
+                 interpolation="bilinear"):
     """Row and column tables of resize + crop (+ flips) for H x W frames: only the S output rows / columns of the
     window get entries (reversed where a flip asks for it).  Returns a dict with `rows`, `cols` ((lo, n, k) each), `S`,
-    `resized`, `window`."""
+    `resized`, `window`.  interpolation: the resize filter (see `check_interpolation`)."""
     S = int(max(input_size))
     h, w = resized_size(H, W, input_size, scale, preserve_aspect_ratio)
     if h <= 0 or w <= 0:
         raise PtxError("TransformFrames: resized frame %dx%d is empty" % (h, w))
     top, left = crop_window(h, w, S, crop)
-    rows = _select(resize_axis_table(H, h), top, S, reverse=bool(vflip))
-    cols = _select(resize_axis_table(W, w), left, S, reverse=bool(hflip))
-    _check_taps(rows, cols, H, W, h, w)
+    rows = _select(resize_axis_table(H, h, interpolation), top, S, reverse=bool(vflip))
+    cols = _select(resize_axis_table(W, w, interpolation), left, S, reverse=bool(hflip))
+    _check_taps(rows, cols, H, W, h, w, interpolation)
     return {"rows": rows, "cols": cols, "S": S, "resized": (h, w), "window": (top, left)}
 
 
-def build_frame_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True):
+def build_frame_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True, interpolation="bilinear"):
     """Row and column tables of the WHOLE resized frame (h rows, w columns): what the per-clip windows launch indexes.
     `build_tables(.., crop=(top, left), hflip=.., vflip=..)` is the slice [top, top + S) x [left, left + S) of these,
     reversed where a flip asks for it.  Returns a dict with `rows`, `cols`, `S`, `resized`."""
@@ -522,8 +654,8 @@ def build_frame_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True
     if h < S or w < S:
         raise PtxError("TransformFrames: a %dx%d crop does not fit the resized %dx%d frame (padding crops are not "
                        "offered)" % (S, S, h, w))
-    rows, cols = resize_axis_table(H, h), resize_axis_table(W, w)
-    _check_taps(rows, cols, H, W, h, w)
+    rows, cols = resize_axis_table(H, h, interpolation), resize_axis_table(W, w, interpolation)
+    _check_taps(rows, cols, H, W, h, w, interpolation)
     return {"rows": rows, "cols": cols, "S": S, "resized": (h, w)}
 
 
@@ -533,9 +665,9 @@ def build_frame_tables(H, W, input_size, scale=0.875, preserve_aspect_ratio=True
 GEOMETRY_FIELDS = ("box_top", "box_left", "box_h", "box_w", "h", "w", "top", "left", "hflip", "vflip")
 
 
-def geometry_tables(row, S):
+def geometry_tables(row, S, interpolation="bilinear"):
     """Row and column tables of ONE clip's geometry, in build_tables' form.  The row means, in PIL terms: crop the box
-    [box_top, +box_h) x [box_left, +box_w) out of the frame, resize it to h x w (Image.BILINEAR; an axis whose extent
+    [box_top, +box_h) x [box_left, +box_w) out of the frame, resize it to h x w (`interpolation`; an axis whose extent
     does not change is not resampled), crop the S x S window at (top, left), mirror if hflip, flip if vflip.  Resizing
     a crop references only the crop's pixels, at positions relative to its origin, so its table is
     `resize_axis_table(box_len, out_len)` with `lo` shifted by the origin; window and flips select and order the
@@ -547,22 +679,53 @@ def geometry_tables(row, S):
     def axis(origin, n_in, n_out, start, flip):
         if start < 0 or start + S > n_out:
             raise PtxError("TransformFrames: geometry: the %d-entry window at %d does not fit the resized extent %d" % (S, start, n_out))
-        lo, n, k = resize_axis_table(n_in, n_out)
+        lo, n, k = resize_axis_table(n_in, n_out, interpolation)
         return _select((lo + np.int32(origin), n, k), start, S, reverse=bool(flip))
 
-    return {"rows": axis(bt, bh, h, top, vf), "cols": axis(bl, bw, w, left, hf), "S": S, "resized": (h, w),
-            "window": (top, left)}
+    t = {"rows": axis(bt, bh, h, top, vf), "cols": axis(bl, bw, w, left, hf), "S": S, "resized": (h, w),
+         "window": (top, left)}
+    for name in ("rows", "cols"):
+        check_coefficients(t[name][2])
+    return t
 
 
-def _axis_taps(n_in, n_out, start, S):
-    """Largest tap count of the entries [start, start + S) of resize_axis_table(n_in, n_out), per clip (int64 arrays
-    [N]): lo / hi of the table alone (the same float64 operations), no weight is computed."""
+def _axis_taps(n_in, n_out, start, S, interpolation="bilinear"):
+    """Largest tap count of the entries [start, start + S) of resize_axis_table(n_in, n_out, interpolation), per clip
+    (int64 arrays [N]): lo / hi of the table alone (the same float64 operations, the filter's support), no weight is
+    computed.  Nearest is one tap."""
+    if interpolation == "nearest":
+        return np.ones(len(n_in), np.int64)
     scale = n_in / n_out                                             # int64 / int64: the float64 quotient, as Python's
     fs = np.maximum(scale, 1.0)[:, None]
+    if interpolation != "bilinear":
+        fs = _SUPPORT[interpolation] * fs                            # the support (bilinear: 1.0 * fs, fs itself)
     center = ((start[:, None] + np.arange(S, dtype=np.int64)[None, :]).astype(np.float64) + 0.5) * scale[:, None]
     lo = np.maximum((center - fs + 0.5).astype(np.int64), 0)
     hi = np.minimum((center + fs + 0.5).astype(np.int64), n_in[:, None])
     return np.where(n_in == n_out, 1, (hi - lo).max(axis=1))
+
+
+def _axis_bicubic_bound(n_in, n_out, start, S):
+    """Per clip (int64 [N]) the largest |k| and the largest sum|k| of the bicubic entries [start, start + S) of every clip's
+    axis, vectorised: the per-clip tables are built on the device, so the host bounds what it will not see.  The weights are
+    PIL's polynomial in numpy (only + - * /: IEEE, no contraction), summed along the taps."""
+    scale = n_in / n_out
+    fs = np.maximum(scale, 1.0)[:, None]
+    support = 2.0 * fs
+    center = ((start[:, None] + np.arange(S, dtype=np.int64)[None, :]).astype(np.float64) + 0.5) * scale[:, None]
+    lo = np.maximum((center - support + 0.5).astype(np.int64), 0)
+    hi = np.minimum((center + support + 0.5).astype(np.int64), n_in[:, None])
+    ksize = int(max((hi - lo).max(), 1))
+    j = np.arange(ksize, dtype=np.float64)[None, None, :]
+    x = np.abs((j + lo[..., None] - center[..., None] + 0.5) * (1.0 / fs)[..., None])
+    a = -0.5
+    w = np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+    w = np.where(j < (hi - lo)[..., None], w, 0.0)
+    ww = np.cumsum(w, axis=2)[..., -1:]
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    k = np.where(j < (hi - lo)[..., None], np.abs(w) * float(1 << PRECISION_BITS) + 0.5, 0.0)   # >= |k| of the table, by less than 1 per tap
+    same, one = n_in == n_out, float(1 << PRECISION_BITS)           # not resampled: one tap of 2**22
+    return np.where(same, one, k.max(axis=(1, 2))), np.where(same, one, k.sum(axis=2).max(axis=1))
 
 
 def random_resized_crop_box(H, W, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), generator=None):
@@ -599,7 +762,8 @@ def random_resized_crop_box(H, W, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0
 
 def apply_tables_numpy(frame, tables):
     """The kernel's arithmetic in numpy (uint8 [H,W,C] -> uint8 [S,S,C]): horizontal pass, uint8 intermediate,
-    vertical pass.  The host-side model the tests compare with PIL; not a fallback (TransformFrames never calls it)."""
+    vertical pass, each `clip((2**21 + sum) >> 22, 0, 255)` with an arithmetic shift (coefficients, and so sums, may be
+    negative).  The host-side model the tests compare with PIL; not a fallback (TransformFrames never calls it)."""
     half = 1 << (PRECISION_BITS - 1)
 
     def one_pass(img, table):                       # resamples axis 0 of img
@@ -1342,13 +1506,21 @@ class TransformFrames:
     augment: a `RandAugment` (None: off, the code path without it), run behind the resize and behind `color`: the stage in front
     writes uint8 scratch and the augment's last position writes the output of `out` / `dtype`.  Its draw comes after every other
     draw of the call (a seed gives the same geometry and colour with and without it) and is kept as `augment.last_params`;
-    `tf(frames, augment_params=p)` applies a given draw instead."""
+    `tf(frames, augment_params=p)` applies a given draw instead.
+
+    interpolation: the resize filter, Pillow's `Image.resize(size, filter)` bit for bit: "nearest" | "box" | "bilinear" (the
+    default) | "hamming" | "bicubic" | "lanczos", Pillow's integer code, or an enum of either (PIL.Image.Resampling,
+    torchvision's InterpolationMode); kept as the canonical string `interpolation`.  The contract stays crop-then-resize
+    (torchvision's resized_crop), not `resize(box=)`.  A per-clip geometry (random_short_side, random_resized_crop,
+    geometry=) supports nearest, box, bilinear and bicubic: its tables are built on the device.  No draw depends on it."""
 
     CACHE_SIZE = 8
 
     def __init__(self, opts, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, out="tensor",
                  dtype=torch.float32, *, random_crop=False, random_hflip=False, random_vflip=False, vflip=False,
-                 generator=None, random_short_side=None, random_resized_crop=False, color=None, augment=None):
+                 generator=None, random_short_side=None, random_resized_crop=False, color=None, augment=None,
+                 interpolation="bilinear"):
+        self.interpolation = check_interpolation(interpolation, "TransformFrames")
         self.color = _check_color(color, "TransformFrames")
         self.augment = _check_augment(augment, "TransformFrames")
         if out not in ("tensor", "frames"):
@@ -1428,6 +1600,8 @@ class TransformFrames:
                 raise PtxError("TransformFrames: random_resized_crop draws the box; it cannot be combined with crop=%r" % (crop,))
             self.random_resized_crop = rrc
         self.per_clip_geometry = self.random_short_side is not None or self.random_resized_crop is not None
+        if self.per_clip_geometry:
+            self._device_filter("random_short_side / random_resized_crop")
         self._resize = None
         if self.color is not None or self.augment is not None:       # the resize half of a call with colour / augment: this
             self._resize = copy.copy(self)                           # transform, writing uint8 frames (tables cache and generator shared)
@@ -1450,13 +1624,24 @@ class TransformFrames:
         self.last_params, self.last_geometry = rs.last_params, rs.last_geometry
         return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params)
 
+    def _device_filter(self, what):
+        """The PTX_RESAMPLE_* code of this transform's filter for the device table builder, or PtxError: a per-clip
+        geometry's tables are built on the device, which takes the filters whose weights are polynomials."""
+        if self.interpolation not in DEVICE_INTERPOLATIONS:
+            raise PtxError("TransformFrames: interpolation=%r cannot be combined with a per-clip geometry (%s): its "
+                           "trigonometric weights are built on the host only; a per-clip geometry supports %s (the %s filter "
+                           "serves every fixed-geometry route: a fixed window, random_crop / flips, SampleViews)" % (
+                               self.interpolation, what, ", ".join(DEVICE_INTERPOLATIONS), self.interpolation))
+        return INTERPOLATIONS.index(self.interpolation)
+
     def tables(self, H, W):
         """Host tables for H x W frames (numpy; see build_tables)."""
-        return build_tables(H, W, self.input_size, self.scale, self.preserve_aspect_ratio, self.crop, self.hflip, self.vflip)
+        return build_tables(H, W, self.input_size, self.scale, self.preserve_aspect_ratio, self.crop, self.hflip, self.vflip,
+                            interpolation=self.interpolation)
 
     def frame_tables(self, H, W):
         """Host tables of the whole resized frame of H x W frames (numpy; see build_frame_tables)."""
-        return build_frame_tables(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
+        return build_frame_tables(H, W, self.input_size, self.scale, self.preserve_aspect_ratio, interpolation=self.interpolation)
 
     def draw(self, N, H, W):
         """Parameters of N clips of H x W frames: a CPU int32 tensor [N, 4] of (top, left, hflip, vflip) in the resized
@@ -1546,6 +1731,7 @@ class TransformFrames:
         return out
 
     def _checked_geometry(self, geometry, N, H, W):
+        self._device_filter("geometry=")
         if isinstance(geometry, torch.Tensor):
             if geometry.is_cuda:
                 raise PtxError("TransformFrames: geometry must be an integer array or a CPU tensor [N, 10], got a CUDA tensor")
@@ -1573,12 +1759,22 @@ class TransformFrames:
                 raise PtxError("TransformFrames: geometry[%d]: a flip must be 0 or 1, got hflip=%d vflip=%d" % (n, hf, vf))
         if N == 0:
             raise PtxError("TransformFrames: empty batch")
-        taps = (_axis_taps(p[:, 2], p[:, 4], p[:, 6], S), _axis_taps(p[:, 3], p[:, 5], p[:, 7], S))
+        f = self.interpolation
+        taps = (_axis_taps(p[:, 2], p[:, 4], p[:, 6], S, f), _axis_taps(p[:, 3], p[:, 5], p[:, 7], S, f))
         for name, t, src, dst in (("rows", taps[0], 2, 4), ("columns", taps[1], 3, 5)):
             n = int(np.argmax(t))
             if t[n] > _lib.PTX_RESIZE_MAX_TAPS:
-                raise PtxError("TransformFrames: geometry[%d]: down-scaling %d %s to %d needs %d taps, the kernel's cap is "
-                               "PTX_RESIZE_MAX_TAPS = %d" % (n, p[n, src], name, p[n, dst], t[n], _lib.PTX_RESIZE_MAX_TAPS))
+                raise PtxError("TransformFrames: geometry[%d]: down-scaling %d %s to %d%s needs %d taps, the kernel's cap is "
+                               "PTX_RESIZE_MAX_TAPS = %d" % (n, p[n, src], name, p[n, dst], "" if f == "bilinear" else
+                                                             " with the %s filter" % f, t[n], _lib.PTX_RESIZE_MAX_TAPS))
+        if f == "nearest" and int(p[:, 4:6].max()) > _lib.PTX_RESAMPLE_NEAREST_MAX_EXTENT:
+            raise PtxError("TransformFrames: geometry: a resized extent of %d exceeds the nearest filter's device walk (%d)" % (
+                int(p[:, 4:6].max()), _lib.PTX_RESAMPLE_NEAREST_MAX_EXTENT))
+        if f == "bicubic":             # the coefficient bounds of tables the host does not build (box / nearest / bilinear: k >= 0, sum 2**22)
+            for n_in, n_out, start in ((p[:, 2], p[:, 4], p[:, 6]), (p[:, 3], p[:, 5], p[:, 7])):
+                kmax, ksum = _axis_bicubic_bound(n_in, n_out, start, S)
+                check_coefficients(np.array([kmax.max()]), "TransformFrames: geometry")
+                check_coefficients(np.array([ksum.max()]), "TransformFrames: geometry")
         return torch.from_numpy(p.astype(np.int32)), int(taps[0].max()), int(taps[1].max())
 
     def check_geometry(self, geometry, N, H, W):
@@ -1712,6 +1908,7 @@ class TransformFrames:
         geometry rows (one upload of N x 40 bytes), ptx_resize_build_tables into a scratch buffer, the tables launch.  The
         host only derives the tap pitch of each axis (from lo / hi of the entries; no weights)."""
         S = self.size
+        code = self._device_filter("geometry=")
         if geometry is None:
             self.last_geometry = self.draw_geometry(N, H, W)
         g, taps_h, taps_w = self._checked_geometry(self.last_geometry if geometry is None else geometry, N, H, W)
@@ -1728,8 +1925,12 @@ class TransformFrames:
                 y = torch.empty((N, 3, T, S, S), device=device, dtype=self.dtype)
             desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            check(_lib.lib().ptx_resize_build_tables(C.byref(desc), C.c_void_p(geo.data_ptr()), *tabs, stream),
-                  "ptx_resize_build_tables")
+            if code == _lib.PTX_RESAMPLE_BILINEAR:                   # the default: the launch it always was
+                check(_lib.lib().ptx_resize_build_tables(C.byref(desc), C.c_void_p(geo.data_ptr()), *tabs, stream),
+                      "ptx_resize_build_tables")
+            else:
+                check(_lib.lib().ptx_resize_build_tables_filter(C.byref(desc), C.c_void_p(geo.data_ptr()), code, *tabs, stream),
+                      "ptx_resize_build_tables_filter")
             name = "ptx_resize_frames_%s_tables" % ("u8" if ysrc is None else _abi_of(ysrc))
             source = C.c_void_p(f5.data_ptr()) if ysrc is None else C.byref(ysrc)
             check(getattr(_lib.lib(), name)(C.byref(desc), source, *tabs, C.c_void_p(y.data_ptr()), C.byref(self.norm), stream),
@@ -1854,13 +2055,15 @@ class SampleViews:
     opts, scale, preserve_aspect_ratio, out, dtype: as for TransformFrames.  num_frames / frame_stride / clips /
     sampling: see `clip_frame_indices`; crops: 1 or 3, see `crop_windows`.  View v = clip * crops + crop.
     share: "auto" (the library picks the workgroup shape), "always" / "never" force the shared horizontal pass on or
-    off (measurements; the results are the same bits)."""
+    off (measurements; the results are the same bits).  interpolation: the resize filter, as for TransformFrames (all six:
+    the tables are built on the host, one per frame size)."""
 
     CACHE_SIZE = 8
     _SHARE = {"auto": _lib.PTX_VIEWS_SHARE_AUTO, "always": _lib.PTX_VIEWS_SHARE_ALWAYS, "never": _lib.PTX_VIEWS_SHARE_NEVER}
 
     def __init__(self, opts, num_frames=16, frame_stride=4, clips=10, crops=3, sampling="dense", scale=0.875,
-                 preserve_aspect_ratio=True, out="frames", dtype=torch.float32, share="auto"):
+                 preserve_aspect_ratio=True, out="frames", dtype=torch.float32, share="auto", interpolation="bilinear"):
+        self.interpolation = check_interpolation(interpolation, "SampleViews")
         if out not in ("tensor", "frames"):
             raise PtxError("SampleViews: out must be 'tensor' or 'frames', got %r" % (out,))
         if dtype not in (torch.float32, torch.bfloat16):
@@ -1907,12 +2110,9 @@ class SampleViews:
         S = self.size
         h, w = resized_size(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
         wins = self.windows(H, W)
-        rows, row_off = _union(resize_axis_table(H, h), [t for t, _ in wins], S)
-        cols, col_off = _union(resize_axis_table(W, w), [l for _, l in wins], S)
-        for name, t in (("rows", rows), ("columns", cols)):
-            if t[2].shape[1] > _lib.PTX_RESIZE_MAX_TAPS:
-                raise PtxError("SampleViews: down-scaling the %s of a %dx%d frame to %dx%d needs %d taps, the kernel's cap is "
-                               "PTX_RESIZE_MAX_TAPS = %d" % (name, H, W, h, w, t[2].shape[1], _lib.PTX_RESIZE_MAX_TAPS))
+        rows, row_off = _union(resize_axis_table(H, h, self.interpolation), [t for t, _ in wins], S)
+        cols, col_off = _union(resize_axis_table(W, w, self.interpolation), [l for _, l in wins], S)
+        _check_taps(rows, cols, H, W, h, w, self.interpolation, "SampleViews")
         return {"rows": rows, "cols": cols, "row_off": row_off, "col_off": col_off, "S": S, "resized": (h, w), "windows": wins}
 
     def view_tables(self, H, W, crop):
@@ -2069,12 +2269,14 @@ class SampleClips:
     SampleClips.  Output clip j comes from video j // clips.
 
     color: a `ColorJitter` applied behind the resize, one list per output clip, as for `TransformFrames(.., color=)`.
-    augment: a `RandAugment` applied behind the resize and the colour, one draw per output clip, as for `TransformFrames(.., augment=)`."""
+    augment: a `RandAugment` applied behind the resize and the colour, one draw per output clip, as for `TransformFrames(.., augment=)`.
+    interpolation: the resize filter, passed to `spatial`; every clip's tables are built on the device, so nearest, box,
+    bilinear and bicubic (see TransformFrames)."""
 
     def __init__(self, opts, num_frames=16, frame_stride=4, clips=1, sampling="dense", random_start=True, scale=0.875,
                  preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False, random_crop=False, random_hflip=False,
                  random_vflip=False, random_short_side=None, random_resized_crop=False, out="tensor", dtype=torch.float32,
-                 generator=None, color=None, augment=None):
+                 generator=None, color=None, augment=None, interpolation="bilinear"):
         self.color = _check_color(color, "SampleClips")
         self.augment = _check_augment(augment, "SampleClips")
         for name, v in (("num_frames", num_frames), ("frame_stride", frame_stride), ("clips", clips)):
@@ -2084,7 +2286,10 @@ class SampleClips:
             raise PtxError("SampleClips: sampling must be 'dense' or 'segments', got %r" % (sampling,))
         self.spatial = TransformFrames(opts, scale, preserve_aspect_ratio, crop, hflip, out, dtype, random_crop=random_crop,
                                        random_hflip=random_hflip, random_vflip=random_vflip, vflip=vflip, generator=generator,
-                                       random_short_side=random_short_side, random_resized_crop=random_resized_crop)
+                                       random_short_side=random_short_side, random_resized_crop=random_resized_crop,
+                                       interpolation=interpolation)
+        self.interpolation = self.spatial.interpolation
+        self._filter = self.spatial._device_filter("SampleClips builds every clip's tables on the device")
         self.num_frames, self.frame_stride, self.clips, self.sampling = num_frames, frame_stride, clips, sampling
         self.random_start, self.generator = bool(random_start), generator
         self.out, self.dtype, self.size, self.norm = out, dtype, self.spatial.size, self.spatial.norm
@@ -2323,8 +2528,12 @@ class SampleClips:
                 y = torch.empty((NC, 3, T, S, S), device=device, dtype=self.dtype)
             desc = ResizeDesc(NC, T, Hm, Wm, 3, S, S, taps_h, taps_w, mode)
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            check(_lib.lib().ptx_resize_build_tables_clips(C.byref(desc), at[0], at[-1], *tabs, stream),
-                  "ptx_resize_build_tables_clips")
+            if self._filter == _lib.PTX_RESAMPLE_BILINEAR:           # the default: the launch it always was
+                check(_lib.lib().ptx_resize_build_tables_clips(C.byref(desc), at[0], at[-1], *tabs, stream),
+                      "ptx_resize_build_tables_clips")
+            else:
+                check(_lib.lib().ptx_resize_build_tables_clips_filter(C.byref(desc), at[0], at[-1], self._filter, *tabs, stream),
+                      "ptx_resize_build_tables_clips_filter")
             name = "ptx_resize_clips_" + (vids[0]._ABI if yuv else "u8")
             check(getattr(_lib.lib(), name)(C.byref(desc), at[1] if yuv else at[0], at[-2], *tabs, C.c_void_p(y.data_ptr()),
                                             C.byref(self.norm), stream), name)
