@@ -17,6 +17,7 @@ YUV16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_yuv
 COLOR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_color.h")      # ColorJitter / RandomGrayscale on uint8 frames
 RANDAUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_randaug.h")  # RandAugment on uint8 frames
 RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_resample.h")  # PIL's other resize filters
+MIX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_mix.h")          # RandomErasing + MixUp / CutMix
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -181,6 +182,18 @@ class RandAugDesc(C.Structure):
  PTX_RANDAUG_BRIGHTNESS, PTX_RANDAUG_COLOR, PTX_RANDAUG_CONTRAST, PTX_RANDAUG_SHARPNESS, PTX_RANDAUG_POSTERIZE, PTX_RANDAUG_SOLARIZE,
  PTX_RANDAUG_AUTOCONTRAST, PTX_RANDAUG_EQUALIZE) = range(14)
 PTX_RANDAUG_NUM_CODES, PTX_RANDAUG_MAX_OPS, PTX_RANDAUG_ROW, PTX_RANDAUG_STATS_WORDS = 14, 4, 8, 770
+
+
+class MixDesc(C.Structure):
+    """ptx_mix_desc (ptx_amd_mix.h): the clips of a BatchMix launch, its source and output modes, the size of the noise buffer."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "H", "W", "src_mode", "out_mode")] + [("noise_elems", C.c_int64)]
+
+
+PTX_MIX_NONE, PTX_MIX_MIXUP, PTX_MIX_CUTMIX = range(3)
+PTX_MIX_ERASE_NONE, PTX_MIX_ERASE_CONST, PTX_MIX_ERASE_NOISE = range(3)
+PTX_MIX_SRC_U8, PTX_MIX_SRC_F32, PTX_MIX_SRC_BF16 = range(3)
+(PTX_MIX_W_PARTNER, PTX_MIX_W_MODE, PTX_MIX_W_A, PTX_MIX_W_B, PTX_MIX_W_BOX, PTX_MIX_W_ERASE, PTX_MIX_W_ERASE_KIND, PTX_MIX_W_CONST,
+ PTX_MIX_W_NOISE, PTX_MIX_ROW) = 0, 1, 2, 3, 4, 8, 12, 13, 16, 20
 
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
@@ -412,6 +425,15 @@ SIGNATURES_RESAMPLE = {
 }
 
 
+# include/ptx_amd_mix.h: RandomErasing + MixUp / CutMix on the normalised clip in one launch (csrc/batch_mix.h), bound the same
+# way (tests/test_batch_mix_host.py)
+SIGNATURES_MIX = {
+    "ptx_batch_mix_supported": (C.c_int, [C.POINTER(MixDesc), _P]),
+    "ptx_batch_mix_apply": (C.c_int, [C.POINTER(MixDesc), _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+    "ptx_batch_mix_targets": (C.c_int, [_P, _P, _P, _I, _I, C.c_float, C.c_float, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -447,7 +469,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
-                list(SIGNATURES_RESAMPLE.items()):
+                list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

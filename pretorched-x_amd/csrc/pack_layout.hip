@@ -1439,3 +1439,7 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 // So are the per-clip RandAugment launches (include/ptx_amd_randaug.h): per op position a statistics kernel (histograms and the
 // luma sum of every frame, when an op needs them) and an apply kernel that shares color_jitter.h's blend, luma and mean.
 #include "rand_augment.h"
+
+// So is the last stage of the training input path (include/ptx_amd_mix.h): RandomErasing per clip and MixUp / CutMix across the
+// clips of the batch on the normalised values, from uint8 frames or a normalised clip, in one launch that writes the NCDHW clip.
+#include "batch_mix.h"

@@ -46,6 +46,11 @@ uint8 frames:
   (only when an op needs a frame's histograms or mean) and an apply launch.  As `TransformFrames(.., augment=ra)` /
   `SampleClips(.., augment=ra)` it runs behind the resize and behind `color=`, its last position writing the call's output.
 
+* `BatchMix` is the recipes' last two steps on the normalised clip: RandomErasing per clip (torchvision's draw) and MixUp /
+  CutMix across the clips of the batch (torchvision v2's draw), in one launch that reads uint8 frames (or a normalised clip) and
+  writes the NCDHW clip once, equal bit for bit to `batch_mix_torch`, the torch statement of the contract.  As
+  `TransformFrames(.., mix=bm)` / `SampleClips(.., mix=bm)` it is the last stage; `bm.targets` gives the soft targets.
+
 Image loading and video decoding stay host work and are not on this path.
 """
 import collections
@@ -1460,8 +1465,413 @@ def _apply_augment(augment, frames_u8, out, dtype, norm, augment_params):
     return y[0] if lead == 4 else y[0, :, 0]
 
 
-def _apply_stages(color, augment, u8, out, dtype, norm, color_params, augment_params):
-    """The stages behind the resize of TransformFrames / SampleClips: colour, then augment; the last one writes the call's output."""
+# ---------------------------------------------------------------------------------------------
+# BatchMix: RandomErasing per clip and MixUp / CutMix across the clips of a batch, on the normalised clip (include/ptx_amd_mix.h)
+# ---------------------------------------------------------------------------------------------
+MIX_MODES = ("none", "mixup", "cutmix")
+MIX_FIELDS = ("partner", "mode", "box_y0", "box_x0", "box_y1", "box_x1", "erase", "erase_top", "erase_left", "erase_h", "erase_w")
+
+
+def _mix_params(params, N=None, who="BatchMix"):
+    """A draw as (int64 numpy [N, 11] of MIX_FIELDS, float64 numpy [N] of lam), or PtxError (shapes and dtypes only)."""
+    try:
+        rows, lam = params
+    except (TypeError, ValueError):
+        raise PtxError("%s: params must be a pair (rows [N, %d], lam [N]), got %r" % (who, len(MIX_FIELDS), params))
+    out = []
+    for name, a, kinds in (("rows", rows, "iu"), ("lam", lam, "f")):
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                raise PtxError("%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
+            a = a.numpy()
+        a = np.asarray(a)
+        if a.dtype.kind not in kinds:
+            raise PtxError("%s: params %s must hold %s, got dtype %s" % (who, name, "integers" if kinds == "iu" else "floats", a.dtype))
+        out.append(a)
+    rows, lam = out[0].astype(np.int64), out[1].astype(np.float64)
+    if rows.ndim != 2 or rows.shape[1] != len(MIX_FIELDS):
+        raise PtxError("%s: params rows must be [N, %d] (%s), got shape %s" % (who, len(MIX_FIELDS), ", ".join(MIX_FIELDS), rows.shape))
+    if lam.shape != (rows.shape[0],):
+        raise PtxError("%s: params lam must be [N] = [%d], got shape %s" % (who, rows.shape[0], lam.shape))
+    if N is not None and rows.shape[0] != N:
+        raise PtxError("%s: params hold %d clips, the batch holds N = %d" % (who, rows.shape[0], N))
+    if rows.shape[0] == 0:
+        raise PtxError("%s: empty batch" % who)
+    if np.abs(rows).max() >= 2 ** 31:
+        raise PtxError("%s: params rows must fit int32" % who)
+    return rows, lam
+
+
+def _mix_erase_value(value, who="BatchMix"):
+    """erase_value as "random" or a tuple of three floats (one per output channel, in the normalised domain)."""
+    if isinstance(value, str):
+        if value != "random":
+            raise PtxError("%s: erase_value must be a number, an RGB triple or 'random', got %r" % (who, value))
+        return value
+    try:
+        v = [float(value)] * 3 if isinstance(value, (int, float)) and not isinstance(value, bool) else [float(c) for c in value]
+    except (TypeError, ValueError):
+        v = None
+    if v is None or len(v) != 3 or not all(math.isfinite(c) for c in v):
+        raise PtxError("%s: erase_value must be a finite number, an RGB triple or 'random', got %r" % (who, value))
+    return tuple(v)
+
+
+def batch_mix_rows(params, T, erase_value=0, N=None, who="BatchMix"):
+    """The int32 rows [N, PTX_MIX_ROW] of a draw for clips of T frames (include/ptx_amd_mix.h) and the number of noise
+    elements they address: a = fp32(lam), b = fp32(1.0 - lam); an erased clip's kind is CONST with the three constants, or NOISE
+    with the offset of its [3, T, h, w] block, the blocks packed in clip order."""
+    rows, lam = _mix_params(params, N, who)
+    value = _mix_erase_value(erase_value, who)
+    out = np.zeros((rows.shape[0], _lib.PTX_MIX_ROW), np.int32)
+    out[:, _lib.PTX_MIX_W_PARTNER], out[:, _lib.PTX_MIX_W_MODE] = rows[:, 0], rows[:, 1]
+    out[:, _lib.PTX_MIX_W_A] = lam.astype(np.float32).view(np.int32)
+    out[:, _lib.PTX_MIX_W_B] = (1.0 - lam).astype(np.float32).view(np.int32)
+    out[:, _lib.PTX_MIX_W_BOX:_lib.PTX_MIX_W_BOX + 4] = rows[:, 2:6]
+    out[:, _lib.PTX_MIX_W_ERASE:_lib.PTX_MIX_W_ERASE + 4] = rows[:, 7:11]
+    noise = 0
+    for n in np.flatnonzero(rows[:, 6]):
+        if value == "random":
+            out[n, _lib.PTX_MIX_W_ERASE_KIND] = _lib.PTX_MIX_ERASE_NOISE
+            out[n, _lib.PTX_MIX_W_NOISE:_lib.PTX_MIX_W_NOISE + 2] = np.array([noise], np.int64).view(np.int32)
+            noise += 3 * int(T) * max(int(rows[n, 9]), 0) * max(int(rows[n, 10]), 0)
+        else:
+            out[n, _lib.PTX_MIX_W_ERASE_KIND] = _lib.PTX_MIX_ERASE_CONST
+            out[n, _lib.PTX_MIX_W_CONST:_lib.PTX_MIX_W_CONST + 3] = np.array(value, np.float32).view(np.int32)
+    return out, noise
+
+
+def _mix_supported(rows, noise_elems, T, H, W, src_mode=_lib.PTX_MIX_SRC_U8, out_mode=_lib.PTX_RESIZE_OUT_F32, who="BatchMix"):
+    """The library's host-side check of the rows (ptx_batch_mix_supported: no device), or PtxError with its message."""
+    desc = _lib.MixDesc(rows.shape[0], int(T), int(H), int(W), src_mode, out_mode, int(noise_elems))
+    rows = np.ascontiguousarray(rows, np.int32)
+    if not _lib.lib().ptx_batch_mix_supported(C.byref(desc), C.c_void_p(rows.ctypes.data)):
+        raise PtxError("%s: %s" % (who, _lib.lib().ptx_last_error().decode(errors="replace")))
+    return rows
+
+
+def batch_mix_torch(clips, params, erase_value=0, noise=None):
+    """torch-on-CPU statement of the contract (the tests' reference).  clips: a CPU tensor [N,3,T,H,W], fp32 or bf16; params: a
+    draw (rows [N, 11] of MIX_FIELDS, lam [N]); noise: for erase_value="random" the list of [3,T,h,w] tensors of the erased
+    clips in clip order.  E_i is clip i with its rectangle replaced on every frame (constants and noise cast to the clips'
+    dtype); then MixUp is  E_p.mul(1.0 - lam).add_(E_i.mul(lam)),  CutMix E_p inside the box and E_i outside it, no mix E_i."""
+    rows, lam = _mix_params(params, clips.shape[0], "batch_mix_torch")
+    value = _mix_erase_value(erase_value, "batch_mix_torch")
+    if clips.dim() != 5 or clips.shape[1] != 3 or clips.is_cuda:
+        raise PtxError("batch_mix_torch: clips must be a CPU tensor [N,3,T,H,W], got %s" % (tuple(clips.shape),))
+    erased, k = [], 0
+    for i, r in enumerate(rows.tolist()):
+        e = clips[i].clone()
+        if r[6]:
+            top, left, h, w = r[7:11]
+            if value == "random":
+                fill = noise[k].to("cpu").to(clips.dtype)
+                k += 1
+            else:
+                fill = torch.tensor(value, dtype=torch.float32).to(clips.dtype).view(3, 1, 1, 1)
+            if h > 0 and w > 0:
+                e[:, :, top:top + h, left:left + w] = fill
+        erased.append(e)
+    out = torch.empty_like(clips)
+    for i, r in enumerate(rows.tolist()):
+        p, mode, (y0, x0, y1, x1) = r[0], r[1], r[2:6]
+        if mode == _lib.PTX_MIX_MIXUP:
+            out[i] = erased[p].mul(1.0 - float(lam[i])).add_(erased[i].mul(float(lam[i])))
+        elif mode == _lib.PTX_MIX_CUTMIX:
+            out[i] = erased[i]
+            out[i][:, :, y0:y1, x0:x1] = erased[p][:, :, y0:y1, x0:x1]
+        else:
+            out[i] = erased[i]
+    return out
+
+
+def batch_mix_targets_torch(labels, num_classes, params, smoothing=0.0):
+    """torch-on-CPU statement of `BatchMix.targets`: fp32 [N, num_classes].  One-hot rows with off = smoothing / K and
+    on = 1 - smoothing + off; a mixed clip's row is  row_p.mul(1.0 - lam).add_(row_i.mul(lam)),  an unmixed clip keeps its own."""
+    rows, lam = _mix_params(params, len(labels), "batch_mix_targets_torch")
+    off = float(smoothing) / int(num_classes)
+    on = 1.0 - float(smoothing) + off
+    onehot = torch.full((len(labels), int(num_classes)), off, dtype=torch.float32)
+    onehot.scatter_(1, torch.as_tensor(labels, dtype=torch.int64).cpu().view(-1, 1), on)
+    out = onehot.clone()
+    for i, r in enumerate(rows.tolist()):
+        if r[1] != _lib.PTX_MIX_NONE:
+            out[i] = onehot[r[0]].mul(1.0 - float(lam[i])).add_(onehot[i].mul(float(lam[i])))
+    return out
+
+
+class BatchMix:
+    """RandomErasing per clip, then MixUp / CutMix across the clips of a batch, on the NORMALISED clip, in one launch that writes
+    the NCDHW clip once (include/ptx_amd_mix.h states the arithmetic, `batch_mix_torch` restates it: every output equals it bit
+    for bit).  The last two steps of the video fine-tuning recipes (timm's Mixup + RandomErasing, torchvision's v2.MixUp /
+    v2.CutMix / RandomErasing).
+
+    mixup_alpha / cutmix_alpha: the Beta(alpha, alpha) of lam, 0 switches the kind off; prob: the chance that a call (mode="batch")
+    or a clip (mode="clip") is mixed; switch_prob: with both alphas positive, the chance of CutMix.  erase_prob / erase_scale /
+    erase_ratio: torchvision's RandomErasing p / scale / ratio; erase_value: a number or an RGB triple in the normalised domain (one
+    per output channel), or "random".  generator: a CPU torch.Generator (None: torch's default one) for the draws;
+    noise_generator: a CUDA torch.Generator (None: the device's default one) for erase_value="random".
+
+    `bm(x)`: x a normalised CUDA clip [N,3,T,H,W], fp32 or bf16 -> the same shape and dtype; or uint8 CUDA frames [N,T,H,W,3] with
+    `opts=` (a model or settings dict, as FramesToTensor takes) -> the normalised fp32 clip, `dtype=torch.bfloat16` the bf16 one:
+    exactly FramesToTensor's value of every byte (bf16: rounded once) erased and mixed.  The draw is kept as `last_params` =
+    (rows CPU int32 [N, 11] of MIX_FIELDS, lam CPU float64 [N]) and `bm(x, params=p)` replays a given one; a row names its partner,
+    so a replayed draw may use any permutation.  `bm.targets(labels, num_classes, smoothing)` gives the soft targets of the last
+    (or a given) draw.
+
+    The draw, on the host from `generator` (`draw`): first the erase of every clip in clip order, which is torchvision's
+    RandomErasing.get_params on an H x W image (torch.rand(1) < erase_prob; then up to 10 attempts of area * uniform_(scale),
+    exp(uniform_(log ratio)), h = int(round(sqrt(area * ratio))), w = int(round(sqrt(area / ratio))), accepted when h < H and
+    w < W with i = randint(0, H - h + 1), j = randint(0, W - w + 1); no accepted attempt: no box); the box covers every frame and
+    channel of the clip.  Then the mix, torchvision v2's, once per call (mode="batch") or per clip in clip order (mode="clip"):
+    torch.rand(1) < prob; with both alphas positive torch.rand(1) < switch_prob chooses CutMix; lam =
+    float(torch._sample_dirichlet(torch.tensor([[a, a]]), generator)[0, 0]); CutMix draws r_x = randint(W), r_y = randint(H), takes
+    r = 0.5 * sqrt(1 - lam), the half extents int(r * W), int(r * H), the box clamped to the frame, and replaces lam by
+    1 - box_area / (W * H).  The partner of clip i is clip (i - 1) mod N (`roll(1, 0)`).
+
+    The one departure from torchvision: the noise of erase_value="random" is not drawn from the host stream but on the device, per
+    erased clip in clip order, as torch.randn((3, T, h, w), device=.., generator=noise_generator) (fp32; rounded once to bf16 for
+    bf16 output), packed into one buffer that the kernel copies from (`last_noise`; `bm(x, params=p, noise=buf)` replays it)."""
+
+    def __init__(self, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch", erase_prob=0.25,
+                 erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3), erase_value=0, generator=None, noise_generator=None):
+        for name, v in (("mixup_alpha", mixup_alpha), ("cutmix_alpha", cutmix_alpha)):
+            if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v) or v < 0:
+                raise PtxError("BatchMix: %s must be a finite number >= 0, got %r" % (name, v))
+        for name, v in (("prob", prob), ("switch_prob", switch_prob), ("erase_prob", erase_prob)):
+            if not isinstance(v, (int, float)) or isinstance(v, bool) or not 0.0 <= v <= 1.0:
+                raise PtxError("BatchMix: %s must be a probability in [0, 1], got %r" % (name, v))
+        if mode not in ("batch", "clip"):
+            raise PtxError("BatchMix: mode must be 'batch' or 'clip', got %r (timm's 'pair' mode is not offered)" % (mode,))
+        pairs = []
+        for name, v, hi in (("erase_scale", erase_scale, 1.0), ("erase_ratio", erase_ratio, float("inf"))):
+            try:
+                lo_, hi_ = (float(c) for c in v)
+                ok = (0.0 <= lo_ <= hi_ <= hi) if name == "erase_scale" else (0.0 < lo_ <= hi_ and math.isfinite(hi_))
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise PtxError("BatchMix: %s must be a pair lo <= hi (scale in [0, 1], ratio positive), got %r" % (name, v))
+            pairs.append((lo_, hi_))
+        for name, g in (("generator", generator), ("noise_generator", noise_generator)):
+            if g is not None and not isinstance(g, torch.Generator):
+                raise PtxError("BatchMix: %s must be a torch.Generator or None, got %r" % (name, g))
+        if generator is not None and generator.device.type != "cpu":
+            raise PtxError("BatchMix: generator must be a CPU torch.Generator (the draws are made on the host)")
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob, self.mode, self.erase_prob = float(prob), float(switch_prob), mode, float(erase_prob)
+        self.erase_scale, self.erase_ratio = pairs
+        self.erase_value = _mix_erase_value(erase_value)
+        self._log_ratio = [float(v) for v in torch.log(torch.tensor(self.erase_ratio))]     # float32 logarithms, as torchvision's
+        self.generator, self.noise_generator = generator, noise_generator
+        self.last_params, self.last_noise = None, None
+
+    # ---- host only: no device is touched -------------------------------------------------------
+    def _draw_erase(self, H, W):
+        g = self.generator
+        if not bool(torch.rand(1, generator=g) < self.erase_prob):
+            return 0, 0, 0, 0, 0
+        area = H * W
+        for _ in range(10):
+            erase_area = area * torch.empty(1).uniform_(self.erase_scale[0], self.erase_scale[1], generator=g).item()
+            aspect = torch.exp(torch.empty(1).uniform_(self._log_ratio[0], self._log_ratio[1], generator=g)).item()
+            h, w = int(round(math.sqrt(erase_area * aspect))), int(round(math.sqrt(erase_area / aspect)))
+            if not (h < H and w < W):
+                continue
+            i = int(torch.randint(0, H - h + 1, size=(1,), generator=g))
+            j = int(torch.randint(0, W - w + 1, size=(1,), generator=g))
+            return 1, i, j, h, w
+        return 0, 0, 0, 0, 0
+
+    def _draw_mix(self, H, W):
+        g = self.generator
+        if self.mixup_alpha <= 0 and self.cutmix_alpha <= 0:
+            return _lib.PTX_MIX_NONE, 1.0, (0, 0, 0, 0)
+        if not bool(torch.rand(1, generator=g) < self.prob):
+            return _lib.PTX_MIX_NONE, 1.0, (0, 0, 0, 0)
+        cutmix = self.cutmix_alpha > 0
+        if self.mixup_alpha > 0 and self.cutmix_alpha > 0:
+            cutmix = bool(torch.rand(1, generator=g) < self.switch_prob)
+        a = self.cutmix_alpha if cutmix else self.mixup_alpha
+        lam = float(torch._sample_dirichlet(torch.tensor([[a, a]]), g)[0, 0])
+        if not cutmix:
+            return _lib.PTX_MIX_MIXUP, lam, (0, 0, 0, 0)
+        r_x = int(torch.randint(W, size=(1,), generator=g))
+        r_y = int(torch.randint(H, size=(1,), generator=g))
+        r = 0.5 * math.sqrt(1.0 - lam)
+        r_w_half, r_h_half = int(r * W), int(r * H)
+        x1, y1 = max(r_x - r_w_half, 0), max(r_y - r_h_half, 0)
+        x2, y2 = min(r_x + r_w_half, W), min(r_y + r_h_half, H)
+        return _lib.PTX_MIX_CUTMIX, float(1.0 - (x2 - x1) * (y2 - y1) / (W * H)), (y1, x1, y2, x2)
+
+    def draw(self, N, H, W):
+        """The draw of N clips of H x W frames: (rows CPU int32 [N, 11] of MIX_FIELDS, lam CPU float64 [N]); see the class for the
+        order.  An unmixed clip has mode 0, lam 1 and is its own partner."""
+        N, H, W = int(N), int(H), int(W)
+        erase = [self._draw_erase(H, W) for _ in range(N)]
+        shared = self._draw_mix(H, W) if self.mode == "batch" else None
+        rows, lam = [], []
+        for i in range(N):
+            mode, l, box = shared if shared is not None else self._draw_mix(H, W)
+            rows.append(((i - 1) % N if mode != _lib.PTX_MIX_NONE else i, mode) + tuple(box) + tuple(erase[i]))
+            lam.append(l)
+        return torch.tensor(rows, dtype=torch.int32).view(N, len(MIX_FIELDS)), torch.tensor(lam, dtype=torch.float64)
+
+    def check_params(self, params, N=None, H=None, W=None):
+        """`params` as (CPU int32 [N, 11], CPU float64 [N]) tensors, or PtxError: shapes, N, and with H and W the library's own
+        check of the rows (`batch_mix_rows`, ptx_batch_mix_supported): a partner or a mode out of range, a box or an erase
+        rectangle outside the H x W frame or with a negative extent, a lam that is not finite or outside [0, 1].  No device is
+        touched."""
+        rows, lam = _mix_params(params, N)
+        bad = np.flatnonzero((rows[:, 6] != 0) & (rows[:, 6] != 1))
+        if len(bad):
+            raise PtxError("BatchMix: params[%d]: the erase flag must be 0 or 1, got %d" % (bad[0], rows[bad[0], 6]))
+        bad = np.flatnonzero(~np.isfinite(lam) | (lam < 0.0) | (lam > 1.0))
+        if len(bad):
+            raise PtxError("BatchMix: params[%d]: lam = %r must be finite and in [0, 1]" % (bad[0], float(lam[bad[0]])))
+        if H is not None and W is not None:
+            r, noise = batch_mix_rows((rows, lam), 1, self.erase_value)
+            _mix_supported(r, noise, 1, H, W)
+        return torch.from_numpy(rows.astype(np.int32)), torch.from_numpy(lam)
+
+    def _rows_for(self, N, T, H, W, params, src_mode, out_mode):
+        """The checked host rows and the noise size of a call on N clips of T frames of H x W: of a new draw (kept as
+        last_params) or of `params`."""
+        if params is None:
+            params = self.last_params = self.draw(N, H, W)
+        else:
+            params = self.check_params(params, N)
+        rows, noise = batch_mix_rows(params, T, self.erase_value, N)
+        return _mix_supported(rows, noise, T, H, W, src_mode, out_mode), noise
+
+    # ---- the launch ----------------------------------------------------------------------------
+    def _noise(self, rows, noise_elems, T, device, dtype, noise):
+        """The packed noise buffer of a call: given, or drawn per erased clip in clip order."""
+        if noise_elems == 0:
+            return None
+        if noise is not None:
+            if not isinstance(noise, torch.Tensor) or noise.device != device or noise.dtype != dtype or noise.numel() != noise_elems:
+                raise PtxError("BatchMix: noise= must be a %s tensor of %d elements on %s (last_noise of the same draw)" % (
+                    dtype, noise_elems, device))
+            return noise.contiguous().view(-1)
+        parts = []
+        for r in rows[rows[:, _lib.PTX_MIX_W_ERASE_KIND] == _lib.PTX_MIX_ERASE_NOISE]:
+            h, w = int(r[_lib.PTX_MIX_W_ERASE + 2]), int(r[_lib.PTX_MIX_W_ERASE + 3])
+            parts.append(torch.randn((3, T, h, w), device=device, generator=self.noise_generator).to(dtype).view(-1))
+        return torch.cat(parts)
+
+    def _launch(self, src, src_mode, N, T, H, W, dtype, norm, rows, noise_elems, noise=None):
+        """The launch on a contiguous CUDA source (uint8 [N,T,H,W,3] or a normalised [N,3,T,H,W]) with the checked host rows of
+        `_rows_for`: the normalised [N,3,T,H,W] of `dtype`."""
+        out_mode = _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+        with torch.cuda.device(src.device):
+            buf = self._noise(rows, noise_elems, T, src.device, dtype, noise)
+            self.last_noise = buf
+            dev_rows = torch.from_numpy(rows.reshape(-1)).to(src.device)                 # one upload
+            y = torch.empty((N, 3, T, H, W), device=src.device, dtype=dtype)
+            desc = _lib.MixDesc(N, T, H, W, src_mode, out_mode, noise_elems)
+            check(_lib.lib().ptx_batch_mix_apply(C.byref(desc), C.c_void_p(src.data_ptr()), C.c_void_p(dev_rows.data_ptr()),
+                                                 C.c_void_p(buf.data_ptr()) if buf is not None else None, C.c_void_p(y.data_ptr()),
+                                                 C.byref(norm) if norm is not None else None,
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), "ptx_batch_mix_apply")
+        return y
+
+    def __call__(self, x, params=None, opts=None, dtype=None, noise=None):
+        if not isinstance(x, torch.Tensor):
+            raise PtxError("BatchMix: expected a CUDA tensor, got %s" % type(x).__name__)
+        if x.dtype == torch.uint8:
+            if x.dim() != 5 or x.shape[-1] != 3:
+                raise PtxError("BatchMix: uint8 frames must be [N,T,H,W,3], got shape %s" % (tuple(x.shape),))
+            if opts is None:
+                raise PtxError("BatchMix: uint8 frames need opts= (a model or settings dict with input_space / input_range / mean / "
+                               "std): the arithmetic is defined on normalised values")
+            dtype = torch.float32 if dtype is None else dtype
+            if dtype not in (torch.float32, torch.bfloat16):
+                raise PtxError("BatchMix: dtype must be torch.float32 or torch.bfloat16, got %s" % (dtype,))
+            N, T, H, W, _ = x.shape
+            src_mode, norm = _lib.PTX_MIX_SRC_U8, FramesToTensor(opts).norm
+        elif x.dtype in (torch.float32, torch.bfloat16):
+            if x.dim() != 5 or x.shape[1] != 3:
+                raise PtxError("BatchMix: a normalised clip must be [N,3,T,H,W], got shape %s" % (tuple(x.shape),))
+            if dtype is not None and dtype != x.dtype:
+                raise PtxError("BatchMix: a normalised clip keeps its dtype (%s), got dtype=%s" % (x.dtype, dtype))
+            N, _, T, H, W = x.shape
+            src_mode = _lib.PTX_MIX_SRC_F32 if x.dtype == torch.float32 else _lib.PTX_MIX_SRC_BF16
+            dtype, norm = x.dtype, None
+        else:
+            raise PtxError("BatchMix: expected uint8 frames or an fp32 / bf16 clip, got dtype %s" % (x.dtype,))
+        if x.numel() == 0:
+            raise PtxError("BatchMix: empty batch")
+        if params is not None or x.is_cuda:                          # given params are validated before a device is touched
+            rows, noise_elems = self._rows_for(N, T, H, W, params, src_mode,
+                                               _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16)
+        if not x.is_cuda:
+            raise PtxError("BatchMix: expected a CUDA tensor (no CPU fallback; batch_mix_torch states the arithmetic)")
+        return self._launch(x.contiguous(), src_mode, N, T, H, W, dtype, norm, rows, noise_elems, noise)
+
+    def targets(self, labels, num_classes, smoothing=0.0, params=None):
+        """Soft targets fp32 [N, num_classes] of CUDA int64 labels [N] for the LAST call's draw (or `params`): one-hot rows with
+        off = smoothing / K and on = 1 - smoothing + off, mixed exactly as MixUp mixes pixels, in fp32, with the draw's lam (CutMix:
+        its adjusted lam) and partner; clips that were not mixed keep their own row (`batch_mix_targets_torch` restates it)."""
+        if not isinstance(num_classes, int) or isinstance(num_classes, bool) or num_classes < 1:
+            raise PtxError("BatchMix: num_classes must be a positive integer, got %r" % (num_classes,))
+        if not isinstance(smoothing, (int, float)) or isinstance(smoothing, bool) or not 0.0 <= smoothing <= 1.0:
+            raise PtxError("BatchMix: smoothing must be in [0, 1], got %r" % (smoothing,))
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() != 1:
+            raise PtxError("BatchMix: labels must be an int64 tensor [N]")
+        N = labels.shape[0]
+        if params is None:
+            if self.last_params is None:
+                raise PtxError("BatchMix: targets() needs a draw: call the transform first or pass params=")
+            params = self.last_params
+        params = self.check_params(params, N)
+        rows, _ = batch_mix_rows(params, 1, 0, N)
+        rows[:, _lib.PTX_MIX_W_BOX:_lib.PTX_MIX_W_ERASE_KIND + 1] = 0    # the boxes and the erase play no part here
+        _mix_supported(rows, 0, 1, 1, 1)                             # partners, modes, lam
+        if not labels.is_cuda:
+            raise PtxError("BatchMix: labels must be a CUDA tensor (no CPU fallback; batch_mix_targets_torch states the arithmetic)")
+        off = float(smoothing) / num_classes
+        on = 1.0 - float(smoothing) + off
+        with torch.cuda.device(labels.device):
+            lab = labels.contiguous()
+            dev_rows = torch.from_numpy(rows.reshape(-1)).to(labels.device)
+            y = torch.empty((N, num_classes), device=labels.device, dtype=torch.float32)
+            check(_lib.lib().ptx_batch_mix_targets(C.c_void_p(lab.data_ptr()), C.c_void_p(dev_rows.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                   N, num_classes, off, on, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                  "ptx_batch_mix_targets")
+        return y
+
+
+def _apply_mix(mix, frames_u8, dtype, norm, mix_params):
+    """The BatchMix stage of TransformFrames / SampleClips with mix=: `frames_u8` is the uint8 output of the stage in front
+    ([N,T,S,S,3] or a lower rank, one clip, which is its own partner), the result the normalised clip of the call."""
+    lead = frames_u8.dim()
+    f5 = frames_u8.view((1,) * (5 - lead) + tuple(frames_u8.shape))
+    N, T, H, W, _ = f5.shape
+    rows, noise_elems = mix._rows_for(N, T, H, W, mix_params, _lib.PTX_MIX_SRC_U8,
+                                      _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16)
+    y = mix._launch(f5, _lib.PTX_MIX_SRC_U8, N, T, H, W, dtype, norm, rows, noise_elems)
+    if lead == 5:
+        return y
+    return y[0] if lead == 4 else y[0, :, 0]
+
+
+def _check_mix(mix, out, who):
+    if mix is not None and not isinstance(mix, BatchMix):
+        raise PtxError("%s: mix must be a pretorched.transforms.BatchMix or None, got %r" % (who, mix))
+    if mix is not None and out != "tensor":
+        raise PtxError("%s: mix= needs out='tensor': erasing and mixing are defined on normalised values, out='frames' returns "
+                       "uint8 frames (forward_frames(.., transform=) takes those alone)" % who)
+    return mix
+
+
+def _apply_stages(color, augment, u8, out, dtype, norm, color_params, augment_params, mix=None, mix_params=None):
+    """The stages behind the resize of TransformFrames / SampleClips: colour, then augment, then mix; the last one writes the
+    call's output."""
+    if mix is not None:
+        if color is not None or augment is not None:
+            u8 = _apply_stages(color, augment, u8, "frames", torch.float32, norm, color_params, augment_params)
+        return _apply_mix(mix, u8, dtype, norm, mix_params)
     if augment is None:
         return _apply_color(color, u8, out, dtype, norm, color_params)
     if color is not None:
@@ -1508,6 +1918,12 @@ class TransformFrames:
     draw of the call (a seed gives the same geometry and colour with and without it) and is kept as `augment.last_params`;
     `tf(frames, augment_params=p)` applies a given draw instead.
 
+    mix: a `BatchMix` (None: off, the code path without it), run last: RandomErasing per clip and MixUp / CutMix across the clips
+    of the call on the normalised values, in one launch that reads the uint8 frames of the stage in front and writes the output.
+    It needs out="tensor".  Its draw comes after every other draw of the call (when it shares their generator, a seed gives the
+    same geometry, colour and augment draws with and without it) and is kept as `mix.last_params`; `tf(frames, mix_params=p)`
+    applies a given draw instead.
+
     interpolation: the resize filter, Pillow's `Image.resize(size, filter)` bit for bit: "nearest" | "box" | "bilinear" (the
     default) | "hamming" | "bicubic" | "lanczos", Pillow's integer code, or an enum of either (PIL.Image.Resampling,
     torchvision's InterpolationMode); kept as the canonical string `interpolation`.  The contract stays crop-then-resize
@@ -1519,10 +1935,11 @@ class TransformFrames:
     def __init__(self, opts, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, out="tensor",
                  dtype=torch.float32, *, random_crop=False, random_hflip=False, random_vflip=False, vflip=False,
                  generator=None, random_short_side=None, random_resized_crop=False, color=None, augment=None,
-                 interpolation="bilinear"):
+                 interpolation="bilinear", mix=None):
         self.interpolation = check_interpolation(interpolation, "TransformFrames")
         self.color = _check_color(color, "TransformFrames")
         self.augment = _check_augment(augment, "TransformFrames")
+        self.mix = _check_mix(mix, out, "TransformFrames")
         if out not in ("tensor", "frames"):
             raise PtxError("TransformFrames: out must be 'tensor' or 'frames', got %r" % (out,))
         if dtype not in (torch.float32, torch.bfloat16):
@@ -1603,15 +2020,20 @@ class TransformFrames:
         if self.per_clip_geometry:
             self._device_filter("random_short_side / random_resized_crop")
         self._resize = None
-        if self.color is not None or self.augment is not None:       # the resize half of a call with colour / augment: this
-            self._resize = copy.copy(self)                           # transform, writing uint8 frames (tables cache and generator shared)
+        if self.color is not None or self.augment is not None or self.mix is not None:   # the resize half of a call with colour /
+            self._resize = copy.copy(self)                           # augment / mix: this transform, writing uint8 frames (tables cache and generator shared)
             self._resize.color, self._resize.augment, self._resize.out, self._resize.dtype = None, None, "frames", torch.float32
+            self._resize.mix = None
 
-    def _call_color(self, frames, params, geometry, color_params, augment_params=None):
-        """A call with color= and / or augment=: the resize writes uint8 frames into scratch (every draw of the plain call, in its
-        order), then the colour lists are drawn clip by clip and applied, then the augment's draw; the last stage writes the
-        requested output, the stages in front of it uint8 scratch."""
+    def _call_color(self, frames, params, geometry, color_params, augment_params=None, mix_params=None):
+        """A call with color=, augment= and / or mix=: the resize writes uint8 frames into scratch (every draw of the plain call, in
+        its order), then the colour lists are drawn clip by clip and applied, then the augment's draw, then the mix's; the last
+        stage writes the requested output, the stages in front of it uint8 scratch."""
         rs = self._resize
+        if mix_params is not None:                                   # validated before a device is touched
+            if self.mix is None:
+                raise PtxError("TransformFrames: mix_params= needs a transform built with mix=BatchMix(..)")
+            mix_params = self.mix.check_params(mix_params, None, self.size, self.size)
         if color_params is not None:                                 # validated before a device is touched
             if self.color is None:
                 raise PtxError("TransformFrames: color_params= needs a transform built with color=ColorJitter(..)")
@@ -1622,7 +2044,8 @@ class TransformFrames:
             augment_params = self.augment.check_params(augment_params, None, self.size, self.size)
         u8 = rs(frames, params=params, geometry=geometry)
         self.last_params, self.last_geometry = rs.last_params, rs.last_geometry
-        return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params)
+        return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params, self.mix,
+                             mix_params)
 
     def _device_filter(self, what):
         """The PTX_RESAMPLE_* code of this transform's filter for the device table builder, or PtxError: a per-clip
@@ -1799,7 +2222,7 @@ class TransformFrames:
             self._cache.popitem(last=False)
         return hit
 
-    def __call__(self, frames, params=None, geometry=None, color_params=None, augment_params=None):
+    def __call__(self, frames, params=None, geometry=None, color_params=None, augment_params=None, mix_params=None):
         """uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3], any H, W  ->
         out="tensor": [N,3,T,S,S] | [3,T,S,S] | [3,S,S] (fp32 or bf16);  out="frames": uint8, same rank, H, W -> S, S.
         A `YUV420` source is taken in place of the frames (converted while the kernel stages its rows: the same bits as
@@ -1815,9 +2238,14 @@ class TransformFrames:
         without colour), and kept as `color.last_params`; color_params applies given lists instead.
         With augment= (a `RandAugment`) its positions run behind the resize and behind the colour launch, the last one writing
         the output; its draw comes after every other draw of the call and is kept as `augment.last_params`; augment_params
-        applies a given draw instead."""
-        if self.color is not None or self.augment is not None:
-            return self._call_color(frames, params, geometry, color_params, augment_params)
+        applies a given draw instead.
+        With mix= (a `BatchMix`) its launch runs last, behind the resize, the colour launch and the augment, reads their uint8
+        frames and writes the erased and mixed normalised clip; its draw comes after every other draw of the call and is kept as
+        `mix.last_params` (`mix.targets(labels, K)` gives the matching soft targets); mix_params applies a given draw instead."""
+        if self.color is not None or self.augment is not None or self.mix is not None:
+            return self._call_color(frames, params, geometry, color_params, augment_params, mix_params)
+        if mix_params is not None:
+            raise PtxError("TransformFrames: mix_params= needs a transform built with mix=BatchMix(..)")
         if color_params is not None:
             raise PtxError("TransformFrames: color_params= needs a transform built with color=ColorJitter(..)")
         if augment_params is not None:
@@ -2270,15 +2698,17 @@ class SampleClips:
 
     color: a `ColorJitter` applied behind the resize, one list per output clip, as for `TransformFrames(.., color=)`.
     augment: a `RandAugment` applied behind the resize and the colour, one draw per output clip, as for `TransformFrames(.., augment=)`.
+    mix: a `BatchMix` applied last, across the output clips of the call, as for `TransformFrames(.., mix=)` (out="tensor" only).
     interpolation: the resize filter, passed to `spatial`; every clip's tables are built on the device, so nearest, box,
     bilinear and bicubic (see TransformFrames)."""
 
     def __init__(self, opts, num_frames=16, frame_stride=4, clips=1, sampling="dense", random_start=True, scale=0.875,
                  preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False, random_crop=False, random_hflip=False,
                  random_vflip=False, random_short_side=None, random_resized_crop=False, out="tensor", dtype=torch.float32,
-                 generator=None, color=None, augment=None, interpolation="bilinear"):
+                 generator=None, color=None, augment=None, interpolation="bilinear", mix=None):
         self.color = _check_color(color, "SampleClips")
         self.augment = _check_augment(augment, "SampleClips")
+        self.mix = _check_mix(mix, out, "SampleClips")
         for name, v in (("num_frames", num_frames), ("frame_stride", frame_stride), ("clips", clips)):
             if not isinstance(v, int) or isinstance(v, bool) or v < 1:
                 raise PtxError("SampleClips: %s must be a positive integer, got %r" % (name, v))
@@ -2295,9 +2725,10 @@ class SampleClips:
         self.out, self.dtype, self.size, self.norm = out, dtype, self.spatial.size, self.spatial.norm
         self.last_indices, self.last_geometry = None, None
         self._resize = None
-        if self.color is not None or self.augment is not None:       # the resize half of a call with colour / augment (see TransformFrames)
+        if self.color is not None or self.augment is not None or self.mix is not None:   # the resize half of a call with colour / augment / mix (see TransformFrames)
             self._resize = copy.copy(self)
             self._resize.color, self._resize.augment, self._resize.out, self._resize.dtype = None, None, "frames", torch.float32
+            self._resize.mix = None
 
     # ---- host only: no device is touched -------------------------------------------------------
     @staticmethod
@@ -2448,7 +2879,7 @@ class SampleClips:
             raise PtxError("SampleClips: videos[%d] is on %s, videos[0] on %s: a batch lives on one device" % (i, devs[i], devs[0]))
         return videos
 
-    def __call__(self, videos, indices=None, geometry=None, color_params=None, augment_params=None):
+    def __call__(self, videos, indices=None, geometry=None, color_params=None, augment_params=None, mix_params=None):
         """videos: a list / tuple of uint8 CUDA tensors [Tv_i,H_i,W_i,3] of any sizes and lengths on one device | one
         [N,Tv,H,W,3] tensor (N videos) | one [Tv,H,W,3] tensor | a list of `YUV420` sources with planes [Tv,H,W] | one
         `YUV420` with planes [N,Tv,H,W] or [Tv,H,W]  ->  out="tensor": [N*clips,3,T,S,S] (fp32 or bf16); out="frames": uint8
@@ -2459,20 +2890,26 @@ class SampleClips:
         With color= (a `ColorJitter`) the resize writes uint8 clips into scratch and the colour launch writes the output: one
         list per output clip, drawn after every other draw of the call and kept as `color.last_params`; color_params applies
         given lists instead.  With augment= (a `RandAugment`) its positions run behind the resize and the colour launch, one draw
-        per output clip after every other draw of the call (`augment.last_params`); augment_params applies a given draw instead."""
+        per output clip after every other draw of the call (`augment.last_params`); augment_params applies a given draw instead.
+        With mix= (a `BatchMix`) its launch runs last across the output clips (`mix.last_params`); mix_params applies a given draw."""
+        if mix_params is not None and self.mix is None:
+            raise PtxError("SampleClips: mix_params= needs a sampler built with mix=BatchMix(..)")
         if color_params is not None and self.color is None:
             raise PtxError("SampleClips: color_params= needs a sampler built with color=ColorJitter(..)")
         if augment_params is not None and self.augment is None:
             raise PtxError("SampleClips: augment_params= needs a sampler built with augment=RandAugment(..)")
-        if self.color is not None or self.augment is not None:
+        if self.color is not None or self.augment is not None or self.mix is not None:
             if color_params is not None:                             # validated before a device is touched
                 color_params = self.color.check_params(color_params)
             if augment_params is not None:
                 augment_params = self.augment.check_params(augment_params, None, self.size, self.size)
+            if mix_params is not None:
+                mix_params = self.mix.check_params(mix_params, None, self.size, self.size)
             rs = self._resize
             u8 = rs(videos, indices=indices, geometry=geometry)
             self.last_indices, self.last_geometry = rs.last_indices, rs.last_geometry
-            return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params)
+            return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params, self.mix,
+                                 mix_params)
         if (indices is None) != (geometry is None):
             raise PtxError("SampleClips: indices= and geometry= are given together (a replay) or not at all (a draw)")
         vids = self._videos(videos)
