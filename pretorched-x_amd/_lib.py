@@ -18,6 +18,7 @@ COLOR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_col
 RANDAUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_randaug.h")  # RandAugment on uint8 frames
 RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_resample.h")  # PIL's other resize filters
 MIX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_mix.h")          # RandomErasing + MixUp / CutMix
+STEM_STRIDED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_stem_strided.h")  # the frame-strided bf16 stem
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -434,6 +435,14 @@ SIGNATURES_MIX = {
 }
 
 
+# include/ptx_amd_stem_strided.h: the patch-resident bf16 stem on every frame_step-th frame of its source
+# (csrc/conv_stem_bf16.hip; bf16 SlowFast), bound the same way (tests/test_slowfast_bf16_host.py)
+SIGNATURES_STEM_STRIDED = {
+    "ptx_conv_stem_bf16_strided_supported": (C.c_int, [C.POINTER(ConvDesc), _I, _I, _I]),
+    "ptx_conv_stem_bf16_strided_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _I, C.POINTER(NormDesc), _I, _I, _P, _P, _P, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -469,7 +478,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
-                list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()):
+                list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

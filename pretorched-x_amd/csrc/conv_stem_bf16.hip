@@ -33,8 +33,16 @@
 // Arithmetic: bf16 operands, fp32 accumulate, bias (+ ReLU) in fp32, one round-to-nearest-even to bf16 per output (NaN
 // kept).  Output: bf16 NDHWC, channels [Co, ldy) written as zero.  All global addressing is 64-bit per frame plus a
 // 32-bit offset inside one frame (ptx_conv_stem_bf16_supported refuses frames past that).
+// Frame sub-sampling (ptx_conv_stem_bf16_strided_fwd, include/ptx_amd_stem_strided.h: SlowFast's pathways read
+// input[:, :, ::step]): the source holds T_full frames and conv frame t is source frame t * frame_step -- a stride in the
+// 64-bit frame base of the staging loop, nothing else changes.  The stride is a template flag: the plain entry point (and
+// frame_step == 1) runs the instances without it, whose machine code is the one it had before the flag existed -- one
+// kernel for both measured 0.6 % slower on the plain path (0.3328 against 0.3306 ms at resnet3d50's config-2 stem, two
+// copies of the old library agreeing to 0.0001 ms), with an instruction stream that differed by one scalar load and one
+// multiply: the hot loop's placement, not its work.
 // Compiled as part of pack_layout.hip's translation unit (its last line includes this file), like resize_views.hip.
 #include "resize_common.h"
+#include "../../include/ptx_amd_stem_strided.h"
 
 namespace ptx {
 
@@ -61,11 +69,13 @@ struct StemBf16Args {
     int tiles_per_frame, n_tiles, w_tiles;
     unsigned flags;
     unsigned dv_wo[2], dv_pc2[2];
+    int frame_step, T_full;       // STRIDED instances: conv frame t = source frame t * frame_step of T_full (last: the plain
+                                  // instances never read them and keep the argument layout they had)
 };
 
 __device__ __forceinline__ unsigned short sb_bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
 
-template <int SRC>
+template <int SRC, bool STRIDED>
 __global__ void __launch_bounds__(kSbNT, 2) conv_stem_bf16_kernel(const StemBf16Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];
     const int patch_bytes = p.PR * p.PC * 8;
@@ -134,9 +144,12 @@ __global__ void __launch_bounds__(kSbNT, 2) conv_stem_bf16_kernel(const StemBf16
 
     // the patch of input frame t, rows from h0: pixel pairs (16 bytes) through registers
     auto stage = [&](int t, int h0) {
-        const unsigned short* xb = static_cast<const unsigned short*>(p.x) + ((size_t)n * 3 * p.Ti + t) * HW;
-        const unsigned char* fb = static_cast<const unsigned char*>(p.x) + ((size_t)n * p.Ti + t) * HW * 3;
-        const size_t cs = (size_t)p.Ti * HW;
+        // source frame and frames per clip: t * frame_step < T_full (Ti == ceil(T_full / frame_step)) | t of Ti
+        const size_t ts = STRIDED ? (size_t)t * p.frame_step : (size_t)t;
+        const int tf = STRIDED ? p.T_full : p.Ti;
+        const unsigned short* xb = static_cast<const unsigned short*>(p.x) + ((size_t)n * 3 * tf + ts) * HW;
+        const unsigned char* fb = static_cast<const unsigned char*>(p.x) + ((size_t)n * tf + ts) * HW * 3;
+        const size_t cs = (size_t)tf * HW;
         for (int u = tid; u < npairs; u += kSbNT) {
             const int pr = (int)fdiv((unsigned)u, p.dv_pc2);
             const int hh = h0 + pr, ww = w0 + 2 * (u - pr * pc2);
@@ -326,10 +339,19 @@ extern "C" int ptx_pack_stem_bf16_weight(const ptx_conv3d_desc* d, const void* w
     return hip_check(hipGetLastError(), "pack_stem_bf16 launch");
 }
 
-extern "C" int ptx_conv_stem_bf16_fwd(const ptx_conv3d_desc* d, const void* x, int32_t src, const ptx_norm_desc* norm,
-                                      const void* w_stem, const float* bias, void* y, ptx_stream_t stream) {
+extern "C" int ptx_conv_stem_bf16_strided_supported(const ptx_conv3d_desc* d, int32_t src, int32_t frame_step, int32_t T_full) {
+    if (!d) return sb_refuse("null descriptor");
+    if (frame_step < 1) return sb_refuse("frame_step must be >= 1");
+    if (T_full < 1 || (int64_t)d->Ti != ((int64_t)T_full + frame_step - 1) / frame_step)
+        return sb_refuse("Ti must be ceil(T_full / frame_step): the frames 0, frame_step, 2 frame_step, .. of the source");
+    return ptx_conv_stem_bf16_supported(d, src);
+}
+
+extern "C" int ptx_conv_stem_bf16_strided_fwd(const ptx_conv3d_desc* d, const void* x, int32_t src, const ptx_norm_desc* norm,
+                                              int32_t frame_step, int32_t T_full, const void* w_stem, const float* bias, void* y,
+                                              ptx_stream_t stream) {
     if (!d || !x || !w_stem || !y) return fail(PTX_ERR_INVALID, "conv_stem_bf16: null pointer");
-    if (!ptx_conv_stem_bf16_supported(d, src)) return PTX_ERR_UNSUPPORTED;         // (the reason is in the last-error string)
+    if (!ptx_conv_stem_bf16_strided_supported(d, src, frame_step, T_full)) return PTX_ERR_UNSUPPORTED;     // (the reason is in the last-error string)
     if (src == PTX_STEM_SRC_U8_NTHWC && !norm) return fail(PTX_ERR_INVALID, "conv_stem_bf16: uint8 frames need a ptx_norm_desc");
     if (src == PTX_STEM_SRC_BF16_NCDHW && ((uintptr_t)x & 1)) return fail(PTX_ERR_INVALID, "conv_stem_bf16: misaligned bf16 clip");
     if (((uintptr_t)w_stem | (uintptr_t)y) & 15) return fail(PTX_ERR_INVALID, "conv_stem_bf16: filter and output must be 16-byte aligned");
@@ -338,6 +360,7 @@ extern "C" int ptx_conv_stem_bf16_fwd(const ptx_conv3d_desc* d, const void* x, i
     StemBf16Args a{};
     a.x = x; a.w = static_cast<const unsigned short*>(w_stem); a.bias = bias; a.y = static_cast<unsigned short*>(y);
     if (norm) a.norm = *norm;
+    a.frame_step = frame_step; a.T_full = T_full;
     a.N = d->N; a.Ti = d->Ti; a.Hi = d->Hi; a.Wi = d->Wi; a.To = d->To; a.Ho = d->Ho; a.Wo = d->Wo; a.ldy = d->ldy; a.Co = d->Co;
     a.kT = d->kT; a.kH = d->kH; a.sT = d->sT; a.sH = d->sH; a.sW = d->sW; a.pT = d->pT; a.pH = d->pH; a.pW = d->pW;
     a.row_mode = g.row_mode; a.segs = g.segs; a.PR = g.PR; a.PC = g.PC; a.khc = g.khc;
@@ -349,9 +372,22 @@ extern "C" int ptx_conv_stem_bf16_fwd(const ptx_conv3d_desc* d, const void* x, i
     fdiv_make((unsigned)(g.PC / 2), a.dv_pc2);
     const size_t lds = (size_t)g.PR * g.PC * 8 + 2 * kSbWSlot * 2 + 3 * 256 * 2;
     const dim3 grid((unsigned)a.n_tiles, (unsigned)cdiv(d->ldy, kSbBN));
-    if (src == PTX_STEM_SRC_U8_NTHWC)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_bf16_kernel<PTX_STEM_SRC_U8_NTHWC>), grid, dim3(kSbNT), lds, (hipStream_t)stream, a);
+    // frame_step == 1 (then T_full == Ti) runs the plain instances: the code the plain entry point always ran
+    const bool strided = frame_step != 1;
+    if (src == PTX_STEM_SRC_U8_NTHWC && strided)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_bf16_kernel<PTX_STEM_SRC_U8_NTHWC, true>), grid, dim3(kSbNT), lds, (hipStream_t)stream, a);
+    else if (src == PTX_STEM_SRC_U8_NTHWC)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_bf16_kernel<PTX_STEM_SRC_U8_NTHWC, false>), grid, dim3(kSbNT), lds, (hipStream_t)stream, a);
+    else if (strided)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_bf16_kernel<PTX_STEM_SRC_BF16_NCDHW, true>), grid, dim3(kSbNT), lds, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_bf16_kernel<PTX_STEM_SRC_BF16_NCDHW>), grid, dim3(kSbNT), lds, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_stem_bf16_kernel<PTX_STEM_SRC_BF16_NCDHW, false>), grid, dim3(kSbNT), lds, (hipStream_t)stream, a);
     return hip_check(hipGetLastError(), "conv_stem_bf16 launch");
+}
+
+extern "C" int ptx_conv_stem_bf16_fwd(const ptx_conv3d_desc* d, const void* x, int32_t src, const ptx_norm_desc* norm,
+                                      const void* w_stem, const float* bias, void* y, ptx_stream_t stream) {
+    if (!d || !x || !w_stem || !y) return fail(PTX_ERR_INVALID, "conv_stem_bf16: null pointer");
+    if (!ptx_conv_stem_bf16_supported(d, src)) return PTX_ERR_UNSUPPORTED;         // (the reason is in the last-error string)
+    return ptx_conv_stem_bf16_strided_fwd(d, x, src, norm, 1, d->Ti, w_stem, bias, y, stream);
 }

@@ -136,6 +136,7 @@ class Engine:
         #   "fold"    (default) ptx_im2col_hw_bf16 + a (kT,1,1) conv on the generic bf16 tiles; bf16 models take bf16 clips only;
         #   "direct"  ptx_conv_stem_bf16_fwd: one patch-resident kernel that reads the bf16 clip -- or decoded uint8 frames,
         #             normalised while they are staged, so forward_frames / frames-out forward_views accept bf16 models.
+        #             It also reads every step-th frame (ptx_conv_stem_bf16_strided_fwd): bf16 SlowFast runs under it only.
         # Changing it drops the compiled plans.  Same operands as "fold", another summation order.
         self._bf16_stem = "fold"
         self.bf16_stem = os.environ.get("PTX_BF16_STEM", "fold")

@@ -36,6 +36,7 @@ BF16_FAMILIES = ("resnet3d10", "resnet3d18", "resnet3d34", "resnet3d50", "resnet
 BF16_NL_KINDS = ("nlblock", "mnist_nl")
 # ... and the BigGAN-deep generator (every resolution and width; plans.build_biggan's bf16 flow)
 BF16_GEN_KINDS = ("biggan",)
+# ... and, under Engine.bf16_stem = "direct" only, plan kind "slowfast" (SlowFast / SlowOnly / FastOnly: Plan._build)
 
 
 def model_precision(model):
@@ -106,6 +107,7 @@ class Plan:
         self.feat = self.pooled = None   # set by the family's builder
         self.head_error = None           # why the default / custom head cannot run on this shape (raised by run_head)
         self.head32 = None               # bf16 plans: fp32 copy of the classifier (head32_refresh)
+        self.kind = None                 # the model's plan_kind (set by _build)
         self.half_plan = self.gen_patch = False      # BigGAN-deep plans (plans.build_biggan): fp16 operands / patch kernels
         with _device_ctx(dev):
             self._build(model)
@@ -722,7 +724,10 @@ class Plan:
         and the stem becomes a (kT, 1, 1) conv over them on the bf16 tiles -- 160 / 147 = 1.09x the algorithmic MACs
         issued (plus tile padding), no torch layout pass."""
         direct = self.bf16_stem == "direct"
-        if (raw.norm is not None and not direct) or raw.t_step != 1 or not isinstance(conv, nn.Conv3d):
+        # a sub-sampled stem (input[:, :, ::step]) and every SlowFast stem: the direct kernel's frame-strided entry, and no
+        # fold fallback (a time-strided im2col does not exist; at 224 x 224 the fold would write 13x the fast clip)
+        strided = direct and isinstance(conv, nn.Conv3d) and (raw.t_step != 1 or self.kind == "slowfast")
+        if (raw.norm is not None and not direct) or (raw.t_step != 1 and not strided) or not isinstance(conv, nn.Conv3d):
             raise PtxError("%s: the bf16 stem reads a bf16 NCDHW clip (uint8 frames / frame sub-sampling are fp32 only%s)" % (
                 label, "" if direct else "; Engine.bf16_stem = 'direct' reads uint8 frames"))
         (kT, kH, kW), (sT, sH, sW), (pT, pH, pW) = _geom(conv)
@@ -732,7 +737,7 @@ class Plan:
         if min(Ho, Wo) < 1:
             raise PtxError("%s: input too small for the stem" % label)
         if direct:
-            y = self.stem_bf16_direct(raw, conv, bn, relu, label)
+            y = self.stem_bf16_direct(raw, conv, bn, relu, label, strided)
             if y is not None:
                 return y
         K = kH * kW * raw.C
@@ -748,12 +753,14 @@ class Plan:
         self.stem_steps += 1
         return y
 
-    def stem_bf16_direct(self, raw, conv, bn, relu, label):
+    def stem_bf16_direct(self, raw, conv, bn, relu, label, strided=False):
         """Engine.bf16_stem = "direct": ONE ptx_conv_stem_bf16_fwd launch reads the caller's bf16 NCDHW clip -- or the decoded
         uint8 frames, normalised while the patch is staged -- and serves every (kh, kw) tap from an LDS-resident patch: no
         im2col pass, no 160-channel copy.  The filter is the fold path's own packed filter (same BN fold, same single
         rounding), re-laid bit-exactly into the kernel's fragment order.  Returns None when the kernel refuses a bf16-clip
-        geometry (the fold path then runs); a refused uint8 geometry raises with the kernel's reason."""
+        geometry (the fold path then runs); a refused uint8 geometry raises with the kernel's reason.
+        strided: ptx_conv_stem_bf16_strided_fwd on every raw.t_step-th of raw.T_full frames (SlowFast's pathways); a refused
+        geometry raises for either source -- there is no fold path behind a sub-sampled stem."""
         (kT, kH, kW), (sT, sH, sW), (pT, pH, pW) = _geom(conv)
         To, Ho, Wo = (raw.T + 2 * pT - kT) // sT + 1, (raw.H + 2 * pH - kH) // sH + 1, (raw.W + 2 * pW - kW) // sW + 1
         Co = conv.out_channels
@@ -765,7 +772,12 @@ class Plan:
         d.flags = PTX_F16_OPERANDS | PTX_BF16_OPERANDS | PTX_EPI_OUT_F16 | (PTX_EPI_RELU if relu else 0)
         src = PTX_STEM_SRC_U8_NTHWC if raw.norm is not None else PTX_STEM_SRC_BF16_NCDHW
         lib = self.lib
-        if To < 1 or not lib.ptx_conv_stem_bf16_supported(C.byref(d), src):
+        if strided:
+            if To < 1 or not lib.ptx_conv_stem_bf16_strided_supported(C.byref(d), src, raw.t_step, raw.T_full):
+                raise PtxError("%s: the direct bf16 stem cannot read frames 0, %d, .. of %d %s: %s" % (
+                    label, raw.t_step, raw.T_full, "bf16 frames" if raw.norm is None else "uint8 frames",
+                    lib.ptx_last_error().decode(errors="replace") if To >= 1 else "input too short for the stem"))
+        elif To < 1 or not lib.ptx_conv_stem_bf16_supported(C.byref(d), src):
             if raw.norm is not None:
                 raise PtxError("%s: the direct bf16 stem cannot read these uint8 frames: %s" % (
                     label, lib.ptx_last_error().decode(errors="replace") if To >= 1 else "input too short for the stem"))
@@ -784,8 +796,11 @@ class Plan:
         if raw.norm is not None:
             st.norm = raw.norm
             self.keepalive.append(raw.norm)
+        if strided:
+            st.frame_step, st.T_full = raw.t_step, raw.T_full
         st.macs = raw.N * To * Ho * Wo * Co * raw.C * kT * kH * kW
-        # compulsory traffic: the clip (or the frames) once in, the bf16 activation out, the filter
+        # compulsory traffic: the clip (or the frames; the raw.T = ceil(T_full / t_step) frames that are read) once in, the
+        # bf16 activation out, the filter
         st.hbm_bytes = raw.N * raw.C * raw.T * raw.H * raw.W * (1 if raw.norm is not None else 2) + 2 * y.t.numel() + 2 * w2.numel()
         self.steps.append(st)
         self.stem_steps += 1
@@ -1210,16 +1225,20 @@ class Plan:
 
     # ---------------------------------------------------------------- network
     def _build(self, model):
-        kind = getattr(model, "plan_kind", "resnet")
+        kind = self.kind = getattr(model, "plan_kind", "resnet")
         if self.bf16:
             name = str(getattr(model, "arch_name", None) or type(model).__name__)
             arch = getattr(model, "arch", None)
+            # SlowFast / SlowOnly / FastOnly: only on the frame-strided direct stem (both pathways read input[:, :, ::step])
+            if kind == "slowfast" and self.bf16_stem != "direct":
+                raise PtxError("bf16 SlowFast runs on the direct bf16 stem only (its pathways sub-sample the clip in time): set "
+                               "Engine.bf16_stem = 'direct' (PTX_BF16_STEM=direct), or run %s in float32" % name)
             # the standalone non-local blocks and MNISTNonLocalNet run on the bf16 attention kernel
-            if kind not in BF16_NL_KINDS + BF16_GEN_KINDS and (
+            if kind not in BF16_NL_KINDS + BF16_GEN_KINDS + ("slowfast",) and (
                     kind != "resnet" or name.split("@")[0] not in BF16_FAMILIES or arch is None or arch.nonlocal_layers
                     or arch.dims != 3 or arch.block not in ("basic", "bottleneck")):
                 raise PtxError("bf16 inference covers the ResNet3D (resnet3d10..200) and R(2+1)D (r2plus1d10..50) families, "
-                               "the non-local blocks and the BigGAN-deep generator; "
+                               "the non-local blocks, the BigGAN-deep generator and (under bf16_stem = 'direct') SlowFast; "
                                "%s (plan kind %r) has bf16 parameters: run it in float32" % (name, kind))
         if kind == "nlblock":                    # a standalone NonLocalBlock3D: [B,C,T,H,W] -> [B,C,T,H,W]
             N, Cc, T, H, W = self.shape

@@ -58,7 +58,12 @@ def build_slowfast(self, model):
                 raise PtxError("SlowFast: lateral %d yields %s but the slow pathway is %s at that stage -- "
                                "torch.cat would fail in the reference too (slowfast.py:145-151); the lateral convs "
                                "stride time by 8, so slow_stride must be 8 * fast_stride" % (i, lt, dims))
-            cat = self.act(N, dims[0], dims[1], dims[2], main_C + lat.out_channels)
+            if self.bf16 and main_C % 8:
+                # bf16 rows are written in 16-byte pieces: the lateral slice starts on an 8-channel boundary (every stock
+                # width does: 64|16, 256|64, 512|128, 1024|256)
+                raise PtxError("SlowFast in bf16: the slow pathway's %d channels ahead of lateral %d do not end on an 8-channel "
+                               "(16-byte) boundary -- run this width in float32" % (main_C, i))
+            cat = self.act(N, dims[0], dims[1], dims[2], main_C + lat.out_channels, f16=self.bf16)
             self.conv(src, self.pack(lat, None), st_, pd, y=cat.slice(main_C, lat.out_channels),
                       label="fast.lateral%d" % i)
             return cat
@@ -97,9 +102,14 @@ def build_slowfast(self, model):
     def head(engine, model):
         st = _stream()
         for f_, p_ in ((slow_feat, ps), (fast_feat, pf)):
-            check(lib.ptx_global_avgpool(_ptr(f_.t), _ptr(p_), f_.N, f_.C, f_.S, f_.ld, 0, st), "ptx_global_avgpool")
+            if self.bf16:       # bf16 features, fp32 means: the classifier below runs in fp32 as in the bf16 ResNets
+                check(lib.ptx_global_avgpool_bf16(_ptr(f_.t), _ptr(p_), f_.N, f_.C, f_.S, f_.ld, st), "ptx_global_avgpool_bf16")
+            else:
+                check(lib.ptx_global_avgpool(_ptr(f_.t), _ptr(p_), f_.N, f_.C, f_.S, f_.ld, 0, st), "ptx_global_avgpool")
         check(lib.ptx_copy2d(_ptr(ps), _ptr(pooled), N, cs, cs, cs + cf, st), "ptx_copy2d")
         check(lib.ptx_copy2d(_ptr(pf), _ptr(pooled, cs), N, cf, cf, cs + cf, st), "ptx_copy2d")
+        if self.bf16:           # fp32 copy of last_linear (no bias), logits rounded to bf16 once; a user's head gets bf16
+            return engine._head_bf16(model, pooled, self)
         out = engine._head(model, _ptr(pooled), N, cs + cf, self.dev)
         return out if out is not None else model.head_module(pooled.clone())
     self.head = head

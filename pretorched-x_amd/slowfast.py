@@ -7,7 +7,8 @@ factories with their `mode='SF'|'S'|'F'` switch -- but the modules only hold par
 pass is compiled by `plans.build_slowfast` into libptx_amd launches.
 
 What the engine does differently from the reference graph (slowfast.py:140-156, 280-299, 385-398):
-  * `input[:, :, ::stride]` is a frame stride of the stem's fold kernel, not a strided copy;
+  * `input[:, :, ::stride]` is a frame stride of the stem's fold kernel (bf16 models: of the direct bf16 stem,
+    `engine().bf16_stem = "direct"`), not a strided copy;
   * `torch.cat([x, lateral], dim=1)` never happens: the stage's last conv and the lateral conv write
     their channel slices of one pre-allocated tensor (conv/pool outputs take a row stride);
   * BN is folded into the filters, ReLU / residual adds run in the conv epilogue, the stage-entry

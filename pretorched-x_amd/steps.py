@@ -689,8 +689,10 @@ def stem_bf16_tiles(d):
 class StemBf16Step(_Step):
     """One ptx_conv_stem_bf16_fwd launch (Engine.bf16_stem = "direct"): the RGB stem of a bf16 plan on the bf16 matrix
     cores, read straight from the caller's bf16 NCDHW clip or from decoded uint8 frames (bound per run: plan.in_ptr;
-    `norm` set = uint8 frames, normalised while the patch is staged) -- no im2col pass, no folded copy."""
-    __slots__ = ("d", "plan", "src", "norm", "w", "b", "y", "label", "macs", "hbm_bytes")
+    `norm` set = uint8 frames, normalised while the patch is staged) -- no im2col pass, no folded copy.
+    `frame_step` set (SlowFast's pathways, any sub-sampled stem): ptx_conv_stem_bf16_strided_fwd -- d.Ti frames are used,
+    conv frame t is frame t * frame_step of the T_full the source holds."""
+    __slots__ = ("d", "plan", "src", "norm", "w", "b", "y", "label", "macs", "hbm_bytes", "frame_step", "T_full")
     _defaults = {"hbm_bytes": 0, "norm": None}
     kernel = "conv_stem_bf16"
 
@@ -709,5 +711,9 @@ class StemBf16Step(_Step):
 
     def __call__(self, st):
         norm = C.byref(self.norm) if self.norm is not None else None
+        if self.frame_step is not None:
+            check(_lib.lib().ptx_conv_stem_bf16_strided_fwd(C.byref(self.d), self.plan.in_ptr, self.src, norm, self.frame_step,
+                                                            self.T_full, self.w, self.b, self.y, st), self.label)
+            return
         check(_lib.lib().ptx_conv_stem_bf16_fwd(C.byref(self.d), self.plan.in_ptr, self.src, norm, self.w, self.b, self.y, st),
               self.label)
