@@ -19,6 +19,7 @@ RANDAUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_r
 RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_resample.h")  # PIL's other resize filters
 MIX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_mix.h")          # RandomErasing + MixUp / CutMix
 STEM_STRIDED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_stem_strided.h")  # the frame-strided bf16 stem
+NL_KS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_nl_ks.h")      # the bf16 attention's two forms by name
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -443,6 +444,15 @@ SIGNATURES_STEM_STRIDED = {
 }
 
 
+# include/ptx_amd_nl_ks.h: the single-group / key-split forms of the bf16 attention by name (csrc/nonlocal_attn.hip), bound
+# the same way (tests/test_nl_resnet_bf16_host.py)
+SIGNATURES_NL_KS = {
+    "ptx_nonlocal_bf16_variant": (C.c_int, [C.POINTER(NonlocalDesc)]),
+    "ptx_nonlocal_bf16_variant_supported": (C.c_int, [C.POINTER(NonlocalDesc), _I]),
+    "ptx_nonlocal_bf16_variant_fwd": (C.c_int, [C.POINTER(NonlocalDesc), _I, _P, _P, _P, _P, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -478,7 +488,8 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
-                list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()):
+                list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()) + \
+                list(SIGNATURES_NL_KS.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -22,6 +22,7 @@
 // No shuffle, no LDS round trip between the two matmuls.  Online softmax (running max m, running sum l, O
 // rescaled by exp(m_old - m_new) only when some query's maximum moved).
 #include "ptx_common.h"
+#include "../../include/ptx_amd_nl_ks.h"
 #include <cfloat>
 #include <cstdlib>
 
@@ -823,25 +824,36 @@ __device__ __forceinline__ unsigned half16(uint2 v, int j) {      // 16-bit elem
     return ((j < 2 ? v.x : v.y) >> (16 * (j & 1))) & 0xffffu;
 }
 
-template <int D, int DV, int KT>
+template <int D, int DV, int KT, int KS = 1>
 constexpr size_t nl_bf16_lds_bytes() {
-    constexpr size_t tiles = ((size_t)2 * 16 * KT * D + (size_t)2 * DV * (16 * KT + 4)) * 2;
+    constexpr size_t tiles = ((size_t)2 * 16 * KT * KS * D + (size_t)2 * DV * (16 * KT * KS + 4)) * 2;
     constexpr size_t ys = (size_t)64 * (DV + 8) * 2;
-    return tiles > ys ? tiles : ys;
+    constexpr size_t mx = KS == 2 ? (size_t)4 * 64 * (DV / 4 + 2) * sizeof(float) : 0;     // the key groups' merge buffer
+    return tiles > ys ? (tiles > mx ? tiles : mx) : (ys > mx ? ys : mx);
 }
 
 // TG: theta fragments from global memory inside the d loop (D = 1024: 'gaussian' mode at C = 1024), as in the fp32 kernel
-template <int D, int DV, bool SOFTMAX, bool TG, int KT>
-__global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args p) {
-    constexpr int TK = 16 * KT;              // keys per tile
+// KS ("key split", 2; ptx_nonlocal_bf16_variant_fwd's variant 1): 8 waves per workgroup on tiles of 64 keys -- wave group
+// grp = wave / 4 takes keys [32 grp, 32 grp + 32) of every tile for the SAME 64 queries, with its own fp32 (m, l, O).  Group
+// 1 parks its state lane-linearly in the idle tile buffers after the last tile, group 0 folds it in (M = max(m0, m1),
+// l = l0 e^(m0 - M) + l1 e^(m1 - M), O likewise per query row; a plain sum in the scale modes) and runs the epilogue.
+// The tile grows to 64 keys rather than the 32-key tile being halved: a tile step is one barrier plus one exposed
+// global-load round trip of the register-staged value tile (issued at the top of step t, stored to LDS at its end), and
+// all waves of a workgroup take that step together -- eight waves on a 32-key tile would wait as often as four do.  On
+// 64 keys a wave's work per step, its DMA pieces (KPW) and its staging items (GPT) are those of KS = 1, the steps halve.
+template <int D, int DV, bool SOFTMAX, bool TG, int KT, int KS = 1>
+__global__ void __launch_bounds__(256 * KS) nl_attention_bf16_kernel(const NlBf16Args p) {
+    static_assert(KS == 1 || (KS == 2 && !TG), "key split: two wave groups");
+    constexpr int TK = 16 * KT * KS;         // keys per tile (16 * KT per wave group)
+    constexpr int NW = 4 * KS, NT = 256 * KS;        // waves / threads per workgroup
     constexpr int QJ = D / 32;               // 32-wide d steps (one ds_read_b128 + one MFMA per 16 keys)
     constexpr int CB = DV / 16;              // 16-channel output blocks (one ds_read_b64 + one MFMA per 16 keys)
     constexpr int S8 = D / 8;                // 16-byte slots per key row
     constexpr int NKP = TK * D / 512;        // 1-KiB DMA pieces of a key tile
-    constexpr int KPW = (NKP + 3) / 4;       // ... per wave
+    constexpr int KPW = (NKP + NW - 1) / NW;       // ... per wave
     constexpr int RS = TK + 4;               // row stride (bf16) of the transposed value tile [DV][RS]
     constexpr int GI = TK * DV / 16;         // staging items (4 keys x 4 channels) per value tile
-    constexpr int GPT = (GI + 255) / 256;    // ... per thread
+    constexpr int GPT = (GI + NT - 1) / NT;  // ... per thread
     constexpr int YS = DV + 8;               // row stride (bf16) of the epilogue's output staging [64][YS]
     static_assert(D % 32 == 0 && DV % 16 == 0 && (TK * D) % 512 == 0 && S8 >= 4, "tile extents");
     constexpr unsigned kOOB = 0x80000000u;
@@ -856,7 +868,8 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
     const int b = tile / p.q_tiles, qt = tile - b * p.q_tiles;
     const int c0 = blockIdx.y * DV;
     const int n = lane & 15, gq = lane >> 4;
-    const int q = qt * 64 + wave * 16 + n;
+    const int grp = KS == 1 ? 0 : wave >> 2, wq = KS == 1 ? wave : wave & 3;      // key group, query sub-tile of the wave
+    const int q = qt * 64 + wq * 16 + n;
 
     const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned short*>(p.theta + (size_t)b * p.bs_t), 0, p.t_bytes, 0x00020000);
@@ -884,23 +897,23 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
     unsigned koff[KPW];
 #pragma unroll
     for (int i = 0; i < KPW; ++i) {
-        const int f = (wave + 4 * i) * 512 + lane * 8;            // bf16 index in the linear [TK][D] image
+        const int f = (wave + NW * i) * 512 + lane * 8;            // bf16 index in the linear [TK][D] image
         const int row = f / D, slot = (f % D) / 8;
         const int col = swz(row, slot) * 8;                       // logical column this physical slot holds
-        koff[i] = (wave + 4 * i < NKP && col < p.d) ? ((unsigned)row * (unsigned)p.ld_p + (unsigned)col) * 2u : kOOB;
+        koff[i] = (wave + NW * i < NKP && col < p.d) ? ((unsigned)row * (unsigned)p.ld_p + (unsigned)col) * 2u : kOOB;
     }
     auto issue_keys = [&](int t, int buf) {
         const unsigned kbase = (unsigned)t * TK * (unsigned)p.ld_p * 2u;
 #pragma unroll
         for (int i = 0; i < KPW; ++i)
-            if (wave + 4 * i < NKP)
-                dma16_b16(rs_p, Ks + buf * TK * D + (wave + 4 * i) * 512, koff[i] == kOOB ? kOOB : koff[i] + kbase);
+            if (wave + NW * i < NKP)
+                dma16_b16(rs_p, Ks + buf * TK * D + (wave + NW * i) * 512, koff[i] == kOOB ? kOOB : koff[i] + kbase);
     };
     // value staging item it: keys 4 * (it % (TK / 4)) + 0..3, channels c0 + 4 * (it / (TK / 4)) + 0..3
     unsigned goff[GPT];
 #pragma unroll
     for (int i = 0; i < GPT; ++i) {
-        const int it = tid + 256 * i, kg = it % (TK / 4), cg = it / (TK / 4);
+        const int it = tid + NT * i, kg = it % (TK / 4), cg = it / (TK / 4);
         const int ch = c0 + 4 * cg;
         goff[i] = (it < GI && ch < p.dv) ? ((unsigned)(4 * kg) * (unsigned)p.ld_g + (unsigned)ch) * 2u : kOOB;
     }
@@ -918,8 +931,8 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
         unsigned short* V = Vt + buf * DV * RS;
 #pragma unroll
         for (int i = 0; i < GPT; ++i) {
-            const int it = tid + 256 * i, kg = it % (TK / 4), cg = it / (TK / 4);
-            if (GI % 256 == 0 || it < GI) {
+            const int it = tid + NT * i, kg = it % (TK / 4), cg = it / (TK / 4);
+            if (GI % NT == 0 || it < GI) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const uint2 w = {half16(gr[i][0], j) | (half16(gr[i][1], j) << 16), half16(gr[i][2], j) | (half16(gr[i][3], j) << 16)};
@@ -939,8 +952,8 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
     load_values(0);
     store_values(0);
     // fragment read offsets (bf16): key row n of each 16-key sub-tile; value row = channel n, keys 4 * gq .. + 3
-    const int k_row_off = n * D;                                  // (16 * kt is a multiple of every swizzle period)
-    const int v_row_off = n * RS + 4 * gq;
+    const int k_row_off = (16 * KT * grp + n) * D;                // (16 * kt is a multiple of every swizzle period)
+    const int v_row_off = n * RS + 16 * KT * grp + 4 * gq;
     for (int t = 0; t < n_tiles; ++t) {
         const int buf = t & 1;
         int ko = k_row_off, vo = v_row_off;
@@ -968,7 +981,7 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
         // s[kt][r] = S[q = n][key = t * TK + 16 kt + 4 gq + r]
         float pr[KT][4];
         if constexpr (SOFTMAX) {
-            const int key0 = t * TK + 4 * gq;
+            const int key0 = t * TK + 16 * KT * grp + 4 * gq;
             float mx = -INFINITY;
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
@@ -1021,6 +1034,37 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
         if (t + 1 < n_tiles) store_values(buf ^ 1);
     }
 
+    if constexpr (KS == 2) {
+        // ---- merge the two key groups through the (idle) tile buffers: [DV / 4 + 2][64 lanes] floats per query sub-tile ----
+        __syncthreads();                                  // every wave is done with the last tile
+        float* Mx = reinterpret_cast<float*>(smem_b16) + wq * (64 * (CB * 4 + 2));
+        if (grp == 1) {
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Mx[(cb * 4 + r) * 64 + lane] = O[cb][r];
+            Mx[(CB * 4) * 64 + lane] = m_run;
+            Mx[(CB * 4 + 1) * 64 + lane] = l_run;
+        }
+        __syncthreads();
+        if (grp == 0) {
+            const float m1 = Mx[(CB * 4) * 64 + lane], l1 = Mx[(CB * 4 + 1) * 64 + lane];
+            float a0 = 1.f, a1 = 1.f;
+            if constexpr (SOFTMAX) {
+                const float M = fmaxf(m_run, m1);         // finite: group 0 always owns at least one valid key
+                a0 = __expf(m_run - M);
+                a1 = __expf(m1 - M);                      // exp(-inf) = 0 when group 1 saw no key (its O and l are 0)
+                l_run = l_run * a0 + l1 * a1;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float b0 = SOFTMAX ? __shfl(a0, 4 * gq + r, 64) : 1.f, b1 = SOFTMAX ? __shfl(a1, 4 * gq + r, 64) : 1.f;
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb) O[cb][r] = O[cb][r] * b0 + Mx[(cb * 4 + r) * 64 + lane] * b1;
+            }
+        }
+    }
+
     // ---- epilogue: 1 / l per query, one rounding to bf16, zeros above dv; rows leave as 16-byte pieces via LDS ----
     float inv = 1.f;
     if constexpr (SOFTMAX) {
@@ -1033,7 +1077,8 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const float iv = SOFTMAX ? __shfl(inv, 4 * gq + r, 64) : 1.f;
-        const int row = wave * 16 + 4 * gq + r;
+        const int row = wq * 16 + 4 * gq + r;
+        if (grp != 0) continue;                       // (KS == 2: group 0 holds the merged rows)
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) {
             const float v = (c0 + cb * 16 + n < p.dv) ? O[cb][r] * iv : 0.f;
@@ -1044,7 +1089,7 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
     const int lim = min(DV, ((p.dv + 7) & ~7) - c0);  // columns [c0, c0 + lim) of y are this workgroup's
     unsigned short* yb = p.y + (size_t)b * p.bs_y;
 #pragma unroll
-    for (int e = tid; e < 64 * (DV / 8); e += 256) {
+    for (int e = tid; e < 64 * (DV / 8); e += NT) {
         const int row = e / (DV / 8), ch = (e % (DV / 8)) * 8;
         const int qo = qt * 64 + row;
         if (qo < p.Nq && ch < lim)
@@ -1052,11 +1097,11 @@ __global__ void __launch_bounds__(256) nl_attention_bf16_kernel(const NlBf16Args
     }
 }
 
-template <int D, int DV, bool SOFTMAX, bool TG, int KT>
+template <int D, int DV, bool SOFTMAX, bool TG, int KT, int KS = 1>
 static int launch_nl_bf16_mode(const NlBf16Args& a, hipStream_t st) {
-    constexpr size_t lds = nl_bf16_lds_bytes<D, DV, KT>();
+    constexpr size_t lds = nl_bf16_lds_bytes<D, DV, KT, KS>();
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = nl_attention_bf16_kernel<D, DV, SOFTMAX, TG, KT>;
+    auto kern = nl_attention_bf16_kernel<D, DV, SOFTMAX, TG, KT, KS>;
     static bool attr_set[64] = {};   // per device; benign race (idempotent call)
     int dev = 0;
     PTX_HIP(hipGetDevice(&dev));
@@ -1064,7 +1109,7 @@ static int launch_nl_bf16_mode(const NlBf16Args& a, hipStream_t st) {
         PTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.q_tiles * a.batch), (unsigned)cdiv(a.dv, DV)), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a.q_tiles * a.batch), (unsigned)cdiv(a.dv, DV)), dim3(256 * KS), lds, st, a);
     return hip_check(hipGetLastError(), "nonlocal attention (bf16) launch");
 }
 template <int D, int DV, bool TG = false, int KT = 2>
@@ -1076,6 +1121,17 @@ static int launch_nl_bf16_dv(const NlBf16Args& a, bool scale_only, hipStream_t s
     if (a.dv <= 64) return launch_nl_bf16<D, 64>(a, scale_only, st);
     if (a.dv <= 128) return launch_nl_bf16<D, 128>(a, scale_only, st);
     return launch_nl_bf16<D, 256>(a, scale_only, st);            // dv > 256: chunks of 256 over blockIdx.y
+}
+// key split (variant 1): 8 waves, two key groups on 64-key tiles
+template <int D, int DV>
+static int launch_nl_bf16_ks(const NlBf16Args& a, bool scale_only, hipStream_t st) {
+    return scale_only ? launch_nl_bf16_mode<D, DV, false, false, 2, 2>(a, st) : launch_nl_bf16_mode<D, DV, true, false, 2, 2>(a, st);
+}
+template <int D>
+static int launch_nl_bf16_ks_dv(const NlBf16Args& a, bool scale_only, hipStream_t st) {
+    if (a.dv <= 64) return launch_nl_bf16_ks<D, 64>(a, scale_only, st);
+    if (a.dv <= 128) return launch_nl_bf16_ks<D, 128>(a, scale_only, st);
+    return launch_nl_bf16_ks<D, 256>(a, scale_only, st);
 }
 
 }  // namespace ptx
@@ -1194,8 +1250,38 @@ extern "C" int ptx_nonlocal_ws_fwd(const ptx_nonlocal_desc* d, const float* thet
     return launch_nl<512, 256>(a, st);
 }
 
+// ---- the two forms of the bf16 attention (include/ptx_amd_nl_ks.h): 0 = single group, 1 = key split ----
+extern "C" int ptx_nonlocal_bf16_variant_supported(const ptx_nonlocal_desc* d, int variant) {
+    if (!d || !(d->mode & PTX_NL_BF16) || !ptx_nonlocal_supported(d)) return 0;
+    if (variant == 0) return 1;
+    // d = 512 and the theta-from-global form (d > 512) stay single-group: their grids are the short N = 196 / 392 shapes
+    return variant == 1 && d->d <= 256;
+}
+
+// Smallest Nk for which the key split is the default, or 0: no default class.  Decided by measurement
+// (scripts/nl_bf16_attention.py --ab, profiles/nl_bf16_ksplit.json): at 8 clips and d = dv = 256 the key
+// split takes 0.83 of the single-group time at N = 1568 and 0.86 at N = 784 (grids short of the chip), but 1.23 at
+// N = 3136 (variant 0 fits two workgroups per CU, the 132 KiB of variant 1 one) and 1.08 - 1.13 at N = 128 / 144.  Every
+// class Nk >= K0 that holds N = 1568 holds N = 3136, so none qualifies: OFF unless PTX_NL_BF16_KSPLIT=1.
+constexpr int kNlBf16KsMinNk = 0;
+
+// The form ptx_nonlocal_bf16_fwd runs: a function of PER-SAMPLE extents and the mode only, never of the batch or the grid
+// (a clip's bits must not depend on the batch it arrives in).  PTX_NL_BF16_KSPLIT=0 / 1, read at every call, forces the key
+// split off / on wherever it is supported (A/B runs), as PTX_NL_KSPLIT does for the fp32 kernel.
+extern "C" int ptx_nonlocal_bf16_variant(const ptx_nonlocal_desc* d) {
+    if (!ptx_nonlocal_bf16_variant_supported(d, 1)) return 0;
+    const char* e = getenv("PTX_NL_BF16_KSPLIT");
+    if (e) return atoi(e) != 0;
+    return kNlBf16KsMinNk > 0 && d->Nk >= kNlBf16KsMinNk;
+}
+
 extern "C" int ptx_nonlocal_bf16_fwd(const ptx_nonlocal_desc* d, const void* theta, const void* phi, const void* g, void* y,
                                      ptx_stream_t stream) {
+    return ptx_nonlocal_bf16_variant_fwd(d, ptx_nonlocal_bf16_variant(d), theta, phi, g, y, stream);
+}
+
+extern "C" int ptx_nonlocal_bf16_variant_fwd(const ptx_nonlocal_desc* d, int variant, const void* theta, const void* phi,
+                                             const void* g, void* y, ptx_stream_t stream) {
     if (!d || !theta || !phi || !g || !y) return fail(PTX_ERR_INVALID, "nonlocal_bf16: null pointer");
     if (!(d->mode & PTX_NL_BF16))
         return fail(PTX_ERR_INVALID, "nonlocal_bf16: the descriptor lacks PTX_NL_BF16 (fp32 operands go to ptx_nonlocal_fwd)");
@@ -1204,6 +1290,9 @@ extern "C" int ptx_nonlocal_bf16_fwd(const ptx_nonlocal_desc* d, const void* the
                     "d <= 1024 (d=%d dv=%d), row / batch strides multiples of 8 bf16 covering d / dv", d->d, d->dv);
     if (((uintptr_t)theta | (uintptr_t)phi | (uintptr_t)g | (uintptr_t)y) & 15)
         return fail(PTX_ERR_INVALID, "nonlocal_bf16: pointers must be 16-byte aligned");
+    if (!ptx_nonlocal_bf16_variant_supported(d, variant))
+        return fail(PTX_ERR_UNSUPPORTED, "nonlocal_bf16: variant %d does not cover this descriptor (0 = single group: every "
+                    "bf16 descriptor; 1 = key split: d <= 256; d=%d)", variant, d->d);
     const uint64_t tb = (uint64_t)d->Nq * d->ld_theta * 2ull, pb = (uint64_t)d->Nk * d->ld_phi * 2ull, gb = (uint64_t)d->Nk * d->ld_g * 2ull;
     if (tb >= 0x80000000ull || pb >= 0x80000000ull || gb >= 0x80000000ull)
         return fail(PTX_ERR_UNSUPPORTED, "nonlocal_bf16: one batch item of theta / phi / g must be < 2 GiB");
@@ -1221,6 +1310,12 @@ extern "C" int ptx_nonlocal_bf16_fwd(const ptx_nonlocal_desc* d, const void* the
     const bool scale_only = (d->mode & PTX_NL_SCALE) != 0;
     hipStream_t st = (hipStream_t)stream;
     // the smallest compiled D covering d, from PER-SAMPLE extents only (a clip's bits do not depend on its batch)
+    if (variant == 1) {
+        if (d->d <= 32) return launch_nl_bf16_ks_dv<32>(a, scale_only, st);
+        if (d->d <= 64) return launch_nl_bf16_ks_dv<64>(a, scale_only, st);
+        if (d->d <= 128) return launch_nl_bf16_ks_dv<128>(a, scale_only, st);
+        return launch_nl_bf16_ks_dv<256>(a, scale_only, st);
+    }
     if (d->d > 512) return launch_nl_bf16<1024, 256, true, 1>(a, scale_only, st);     // theta from global, 16-key tiles
     if (d->d <= 32) return launch_nl_bf16_dv<32>(a, scale_only, st);
     if (d->d <= 64) return launch_nl_bf16_dv<64>(a, scale_only, st);

@@ -31,12 +31,24 @@ from .tuned import (BODY_FILTERS, BODY_SHAPES, _flags_kind, alt_lookup, body_loo
 # bf16 kernels.  Everything else raises at plan build time.
 BF16_FAMILIES = ("resnet3d10", "resnet3d18", "resnet3d34", "resnet3d50", "resnet3d101", "resnet3d152", "resnet3d200",
                  "r2plus1d10", "r2plus1d18", "r2plus1d34", "r2plus1d50")
-# ... and the plan kinds built from non-local blocks alone: NonLocalBlock1D / 2D / 3D and MNISTNonLocalNet (the networks that
-# embed blocks in a ResNet, nonlocalresnet3d50 / nonlocal_r2plus1d50, keep raising)
+# ... and the plan kinds built from non-local blocks alone: NonLocalBlock1D / 2D / 3D and MNISTNonLocalNet
 BF16_NL_KINDS = ("nlblock", "mnist_nl")
+# ... and, under Engine.bf16_stem = "direct" only, the networks that embed non-local blocks in one of the families above
+# (arch.nonlocal_layers: nonlocalresnet3d18 .. 101, NonLocalResNet3D(nonlocal_layers=...), nonlocal_r2plus1d50; Plan._build).
+# Under the default "fold" stem they keep raising.
 # ... and the BigGAN-deep generator (every resolution and width; plans.build_biggan's bf16 flow)
 BF16_GEN_KINDS = ("biggan",)
 # ... and, under Engine.bf16_stem = "direct" only, plan kind "slowfast" (SlowFast / SlowOnly / FastOnly: Plan._build)
+
+
+def _bf16_base(name):
+    """The BF16_FAMILIES entry a non-local network is built on: 'nonlocalresnet3d50' -> 'resnet3d50', 'nonlocal_r2plus1d50' ->
+    'r2plus1d50' (arch keys: the '/5', '/nl0-1-1-0' placement and '@B' shortcut suffixes dropped)."""
+    name = name.split("@")[0].split("/")[0]
+    for prefix in ("nonlocal_", "nonlocal"):
+        if name.startswith(prefix):
+            return name[len(prefix):]
+    return name
 
 
 def model_precision(model):
@@ -103,6 +115,7 @@ class Plan:
         self.bf16_stem = getattr(engine, "bf16_stem", "fold")            # "fold" | "direct" (ptx_conv_stem_bf16_fwd)
         self.stem_steps = self.patch_steps = self.attn_steps = 0         # launches outside conv_steps, by kind
         self.attn_descs, self.attn_operands = [], []                     # bf16 attention launches: descriptors, (th, ph, g, y)
+        self.attn_variants = []          # ... and the kernel form the dispatcher picks for each (ptx_nonlocal_bf16_variant, at build time)
         self._stem_src = {}              # stem_source()'s buffers by (uint8 frames?, row pitch)
         self.feat = self.pooled = None   # set by the family's builder
         self.head_error = None           # why the default / custom head cannot run on this shape (raised by run_head)
@@ -1067,6 +1080,7 @@ class Plan:
                                macs=th.N * th.S * ph.S * (th.C + g.C)))
         self.attn_steps += 1
         self.attn_descs.append(d)
+        self.attn_variants.append(int(lib.ptx_nonlocal_bf16_variant(C.byref(d))))
         self.attn_operands.append((th, ph, g, y))
         return True
 
@@ -1233,12 +1247,19 @@ class Plan:
             if kind == "slowfast" and self.bf16_stem != "direct":
                 raise PtxError("bf16 SlowFast runs on the direct bf16 stem only (its pathways sub-sample the clip in time): set "
                                "Engine.bf16_stem = 'direct' (PTX_BF16_STEM=direct), or run %s in float32" % name)
+            # a ResNet3D / R(2+1)D with non-local blocks: on the direct bf16 stem only (the contract SlowFast got)
+            nl_net = (kind == "resnet" and arch is not None and bool(arch.nonlocal_layers) and _bf16_base(name) in BF16_FAMILIES
+                      and arch.dims == 3 and arch.block in ("basic", "bottleneck"))
+            if nl_net and self.bf16_stem != "direct":
+                raise PtxError("bf16 non-local ResNets run on the direct bf16 stem only: set Engine.bf16_stem = 'direct' "
+                               "(PTX_BF16_STEM=direct), or run %s in float32" % name)
             # the standalone non-local blocks and MNISTNonLocalNet run on the bf16 attention kernel
-            if kind not in BF16_NL_KINDS + BF16_GEN_KINDS + ("slowfast",) and (
+            if not nl_net and kind not in BF16_NL_KINDS + BF16_GEN_KINDS + ("slowfast",) and (
                     kind != "resnet" or name.split("@")[0] not in BF16_FAMILIES or arch is None or arch.nonlocal_layers
                     or arch.dims != 3 or arch.block not in ("basic", "bottleneck")):
                 raise PtxError("bf16 inference covers the ResNet3D (resnet3d10..200) and R(2+1)D (r2plus1d10..50) families, "
-                               "the non-local blocks, the BigGAN-deep generator and (under bf16_stem = 'direct') SlowFast; "
+                               "the non-local blocks, the BigGAN-deep generator and (under bf16_stem = 'direct') SlowFast and "
+                               "the non-local ResNets; "
                                "%s (plan kind %r) has bf16 parameters: run it in float32" % (name, kind))
         if kind == "nlblock":                    # a standalone NonLocalBlock3D: [B,C,T,H,W] -> [B,C,T,H,W]
             N, Cc, T, H, W = self.shape
