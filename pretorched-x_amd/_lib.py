@@ -20,6 +20,7 @@ RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_
 MIX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_mix.h")          # RandomErasing + MixUp / CutMix
 STEM_STRIDED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_stem_strided.h")  # the frame-strided bf16 stem
 NL_KS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_nl_ks.h")      # the bf16 attention's two forms by name
+LINEAR_BF16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_linear_bf16.h")  # Linear layers with bf16 weights
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -453,6 +454,20 @@ SIGNATURES_NL_KS = {
 }
 
 
+# include/ptx_amd_linear_bf16.h: Linear layers with bf16 weights for few rows (csrc/linear_bf16.hip; the bf16 TRN heads), bound
+# the same way (tests/test_trn_bf16_host.py)
+PTX_LIN_X_BF16, PTX_LIN_X_F32 = 0, 1
+SIGNATURES_LINEAR_BF16 = {
+    "ptx_linear_bf16w_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "ptx_linear_bf16w_supported": (C.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, C.c_uint32]),
+    "ptx_linear_bf16w_fwd": (C.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, C.c_uint32, _P, C.c_size_t, _P]),
+    "ptx_relation_linear_bf16w_supported": (C.c_int, [C.POINTER(RelationDesc), _P, _I, _P, _P, _P, _I, _I, C.c_uint32]),
+    "ptx_relation_linear_bf16w_fwd": (C.c_int, [C.POINTER(RelationDesc), _P, _I, _P, _P, _P, _I, _I, C.c_uint32, _P, C.c_size_t, _P]),
+    "ptx_linear_setsum_bf16w_supported": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint32]),
+    "ptx_linear_setsum_bf16w_fwd": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint32, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -489,7 +504,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
                 list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()) + \
-                list(SIGNATURES_NL_KS.items()):
+                list(SIGNATURES_NL_KS.items()) + list(SIGNATURES_LINEAR_BF16.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

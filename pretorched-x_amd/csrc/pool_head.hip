@@ -1159,3 +1159,7 @@ extern "C" int ptx_views_mean(const void* logits, float* y, int32_t N, int32_t V
         hipLaunchKernelGGL(views_mean_kernel<false>, dim3((unsigned)N), dim3(256), lds, st, logits, y, V, K, (long long)ld, mode);
     return hip_check(hipGetLastError(), "views_mean launch");
 }
+
+// The Linear layers with bf16 weights (include/ptx_amd_linear_bf16.h: the bf16 TRN relation MLPs and classifier) are a file of
+// their own compiled as part of this translation unit (build.py follows the include, so its bytes are in this object's stamp).
+#include "linear_bf16.hip"

@@ -137,6 +137,7 @@ class Engine:
         #   "direct"  ptx_conv_stem_bf16_fwd: one patch-resident kernel that reads the bf16 clip -- or decoded uint8 frames,
         #             normalised while they are staged, so forward_frames / frames-out forward_views accept bf16 models.
         #             It also reads every step-th frame (ptx_conv_stem_bf16_strided_fwd): bf16 SlowFast runs under it only.
+        #             A Conv2d stem is its kT = 1 case: the bf16 2-D ResNets (and so a bf16 TRN) run under it only as well.
         # Changing it drops the compiled plans.  Same operands as "fold", another summation order.
         self._bf16_stem = "fold"
         self.bf16_stem = os.environ.get("PTX_BF16_STEM", "fold")

@@ -89,6 +89,60 @@ def check_views(views, model, want_out, who="forward_views", bf16_stem="fold"):
 # ---------------------------------------------------------------------------------------------
 # TRN relation MLP (trn.py:39-45): ReLU -> Linear -> ReLU -> Linear
 # ---------------------------------------------------------------------------------------------
+def _bf16_head(who, x, *lins):
+    """True when this head call runs on the bf16-weight kernels (include/ptx_amd_linear_bf16.h): every Linear holds bfloat16
+    parameters and x is a bfloat16 CUDA tensor.  A dtype mismatch in either direction raises; float32 calls return False."""
+    wd = {t.dtype for lin in lins for t in (lin.weight, lin.bias) if t is not None}
+    if torch.bfloat16 not in wd:
+        if isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16:
+            raise PtxError("%s: the input is bfloat16 but the Linear parameters are %s: convert the module with "
+                           ".to(torch.bfloat16), or pass a float32 input" % (who, sorted(str(d) for d in wd)))
+        return False
+    if wd != {torch.bfloat16}:
+        raise PtxError("%s: the Linear parameters mix %s" % (who, sorted(str(d) for d in wd)))
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.bfloat16:
+        raise PtxError("%s: the Linear parameters are bfloat16: the input must be a bfloat16 CUDA tensor too (got %s; no CPU "
+                       "fallback)" % (who, getattr(x, "dtype", type(x))))
+    return True
+
+
+def _wb(lin):
+    """The live bf16 parameters of a Linear (no copies: nothing to refresh)."""
+    w = lin.weight.detach()
+    b = lin.bias.detach() if lin.bias is not None else None
+    return (w if w.is_contiguous() else w.contiguous()), (None if b is None else b.contiguous())
+
+
+def _bp(t):
+    return _ptr(t) if t is not None else C.c_void_p(0)
+
+
+def _workspace(M, K, Nout, dev):
+    """(tensor or None, pointer, bytes): the split-K partial tiles of one bf16-weight launch."""
+    n = int(_lib.lib().ptx_linear_bf16w_workspace_bytes(M, K, Nout))
+    if n == 0:
+        return None, C.c_void_p(0), 0
+    ws = torch.empty((n + 3) // 4, device=dev, dtype=torch.float32)
+    return ws, _ptr(ws), n
+
+
+def _dense_bf16w(x, x_kind, lin, y, flags, what):
+    """y (fp32 [M, Nout], contiguous) (+)= act(x) @ W^T + b through ptx_linear_bf16w_fwd; x: contiguous [M, K] bf16 / fp32."""
+    M, K = x.shape
+    w, b = _wb(lin)
+    ws, wsp, wsn = _workspace(M, K, lin.out_features, x.device)
+    check(_lib.lib().ptx_linear_bf16w_fwd(_ptr(x), x_kind, _ptr(w), _bp(b), _ptr(y), M, K, lin.out_features, K, y.stride(0), flags,
+                                          wsp, wsn, _stream()), what)
+
+
+def round_bf16(y32):
+    """fp32 -> bf16, one round-to-nearest-even per element (ptx_f32_to_bf16)."""
+    out = torch.empty(y32.shape, device=y32.device, dtype=torch.bfloat16)
+    with torch.cuda.device(y32.device):
+        check(_lib.lib().ptx_f32_to_bf16(_ptr(y32), _ptr(out), y32.numel(), _stream()), "ptx_f32_to_bf16")
+    return out
+
+
 def linear(x, lin, flags=0):
     """y = x @ W^T + b through ptx_linear_fwd for any [..., K] float32 CUDA tensor (TRN classifier,
     trn.py:257-258)."""
@@ -97,6 +151,13 @@ def linear(x, lin, flags=0):
     from . import eager
     if eager.wanted(lin, x):                            # train() / autograd / CPU model (eager.py)
         return lin(x)
+    if _bf16_head("linear", x, lin):
+        # bf16 parameters on bf16 features: ptx_linear_bf16w_fwd on the live weights, fp32 accumulate, logits rounded once
+        flat = x.contiguous().view(-1, lin.in_features)
+        with torch.cuda.device(x.device):
+            out32 = torch.empty((flat.shape[0], lin.out_features), device=x.device, dtype=torch.float32)
+            _dense_bf16w(flat, _lib.PTX_LIN_X_BF16, lin, out32, flags, "ptx_linear_bf16w_fwd")
+        return round_bf16(out32).view(tuple(x.shape[:-1]) + (lin.out_features,))
     if not x.is_cuda or x.dtype != torch.float32:
         raise PtxError("linear: input must be a float32 CUDA tensor (no CPU fallback)")
     K = lin.in_features
@@ -116,7 +177,10 @@ def relation_scale(x, subsets, lin1, lin2, out=None, accumulate=False):
     """All frame subsets of ONE relation scale in two launches (reference trn.py:101-110 runs one MLP per
     subset): launch 1 gathers the frames inside the kernel and reads W1 once for every subset, launch 2
     applies W2 to the sum of the hidden vectors (linearity of `stack(output).sum(0)`) and accumulates
-    into `out`.  x: [B, T, F] fp32 CUDA; subsets: tuples of frame indices, all of one length."""
+    into `out`.  x: [B, T, F] fp32 CUDA; subsets: tuples of frame indices, all of one length.
+    bf16 parameters take a bf16 x through the bf16-weight twins of the two launches; hidden vector and `out` stay fp32."""
+    if _bf16_head("relation_scale", x, lin1, lin2):
+        return _relation_scale_bf16(x, subsets, lin1, lin2, out, accumulate)
     if not x.is_cuda or x.dtype != torch.float32:
         raise PtxError("relation_scale: input must be a float32 CUDA tensor (no CPU fallback)")
     B, T, F_ = x.shape
@@ -139,7 +203,41 @@ def relation_scale(x, subsets, lin1, lin2, out=None, accumulate=False):
     return res
 
 
+def _relation_scale_bf16(x, subsets, lin1, lin2, out, accumulate):
+    B, T, F_ = x.shape
+    x = x.contiguous()
+    d = _lib.RelationDesc()
+    d.B, d.n_sets, d.n_frames, d.frame_len = B, len(subsets), len(subsets[0]), F_
+    for r, sub in enumerate(subsets):
+        for f, i in enumerate(sub):
+            d.idx[r][f] = int(i)
+    lib = _lib.lib()
+    hid_n, out_n = lin1.out_features, lin2.out_features
+    M, K = len(subsets) * B, len(subsets[0]) * F_
+    with torch.cuda.device(x.device):
+        hid = torch.empty((M, hid_n), device=x.device, dtype=torch.float32)
+        res = out if out is not None else torch.empty((B, out_n), device=x.device, dtype=torch.float32)
+        (w1, b1), (w2, b2) = _wb(lin1), _wb(lin2)
+        ws, wsp, wsn = _workspace(M, K, hid_n, x.device)
+        check(lib.ptx_relation_linear_bf16w_fwd(C.byref(d), _ptr(x), T * F_, _ptr(w1), _bp(b1), _ptr(hid), hid_n, hid_n,
+                                                PTX_PRO_RELU | PTX_EPI_RELU, wsp, wsn, _stream()), "relation.linear1 (bf16 weights)")
+        check(lib.ptx_linear_setsum_bf16w_fwd(_ptr(hid), _ptr(w2), _bp(b2), _ptr(res), B, len(subsets), hid_n, out_n, hid_n,
+                                              out_n, PTX_EPI_ACCUM if accumulate else 0, _stream()), "relation.linear2 (bf16 weights)")
+    return res
+
+
 def relation_mlp(flat, lin1, lin2, out=None, accumulate=False):
+    """ReLU -> lin1 -> ReLU -> lin2 on [M, K] rows, fp32 [M, out] back (accumulated into `out` when asked).  bf16 parameters
+    take a bf16 `flat`: the hidden vector and the result stay fp32 (the relation module rounds its output once)."""
+    if _bf16_head("relation_mlp", flat, lin1, lin2):
+        flat = flat.contiguous()
+        M = flat.shape[0]
+        with torch.cuda.device(flat.device):
+            hid = torch.empty((M, lin1.out_features), device=flat.device, dtype=torch.float32)
+            res = out if out is not None else torch.empty((M, lin2.out_features), device=flat.device, dtype=torch.float32)
+            _dense_bf16w(flat, _lib.PTX_LIN_X_BF16, lin1, hid, PTX_PRO_RELU | PTX_EPI_RELU, "relation.linear1 (bf16 weights)")
+            _dense_bf16w(hid, _lib.PTX_LIN_X_F32, lin2, res, PTX_EPI_ACCUM if accumulate else 0, "relation.linear2 (bf16 weights)")
+        return res
     if not flat.is_cuda or flat.dtype != torch.float32:
         raise PtxError("relation_mlp: input must be a float32 CUDA tensor (no CPU fallback)")
     flat = flat.contiguous()

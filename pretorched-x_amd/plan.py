@@ -36,6 +36,9 @@ BF16_NL_KINDS = ("nlblock", "mnist_nl")
 # ... and, under Engine.bf16_stem = "direct" only, the networks that embed non-local blocks in one of the families above
 # (arch.nonlocal_layers: nonlocalresnet3d18 .. 101, NonLocalResNet3D(nonlocal_layers=...), nonlocal_r2plus1d50; Plan._build).
 # Under the default "fold" stem they keep raising.
+# ... and, under Engine.bf16_stem = "direct" only, the 2-D ResNets (TRN's per-frame backbone): the Conv2d stem is the direct
+# kernel's kT = 1 case on T = 1, and there is no fold route behind it
+BF16_FAMILIES_2D = ("resnet18", "resnet34", "resnet50", "resnet101", "resnet152")
 # ... and the BigGAN-deep generator (every resolution and width; plans.build_biggan's bf16 flow)
 BF16_GEN_KINDS = ("biggan",)
 # ... and, under Engine.bf16_stem = "direct" only, plan kind "slowfast" (SlowFast / SlowOnly / FastOnly: Plan._build)
@@ -740,7 +743,9 @@ class Plan:
         # a sub-sampled stem (input[:, :, ::step]) and every SlowFast stem: the direct kernel's frame-strided entry, and no
         # fold fallback (a time-strided im2col does not exist; at 224 x 224 the fold would write 13x the fast clip)
         strided = direct and isinstance(conv, nn.Conv3d) and (raw.t_step != 1 or self.kind == "slowfast")
-        if (raw.norm is not None and not direct) or (raw.t_step != 1 and not strided) or not isinstance(conv, nn.Conv3d):
+        # a 2-D ResNet's Conv2d stem: the direct kernel's kT = 1 case on T = 1 (Plan._build lets 2-D models in under "direct" only)
+        conv2d = direct and isinstance(conv, nn.Conv2d) and raw.T == 1 and raw.t_step == 1
+        if (raw.norm is not None and not direct) or (raw.t_step != 1 and not strided) or not (isinstance(conv, nn.Conv3d) or conv2d):
             raise PtxError("%s: the bf16 stem reads a bf16 NCDHW clip (uint8 frames / frame sub-sampling are fp32 only%s)" % (
                 label, "" if direct else "; Engine.bf16_stem = 'direct' reads uint8 frames"))
         (kT, kH, kW), (sT, sH, sW), (pT, pH, pW) = _geom(conv)
@@ -753,6 +758,9 @@ class Plan:
             y = self.stem_bf16_direct(raw, conv, bn, relu, label, strided)
             if y is not None:
                 return y
+        if conv2d:                       # no fold route behind a Conv2d stem
+            raise PtxError("%s: the direct bf16 stem cannot run this 2-D stem: %s" % (
+                label, self.lib.ptx_last_error().decode(errors="replace")))
         K = kH * kW * raw.C
         xf = self.act(raw.N, raw.T, Ho, Wo, K, ld=(K + 31) // 32 * 32, f16=True)
         lib, yp = self.lib, _ptr(xf.t)
@@ -1253,13 +1261,19 @@ class Plan:
             if nl_net and self.bf16_stem != "direct":
                 raise PtxError("bf16 non-local ResNets run on the direct bf16 stem only: set Engine.bf16_stem = 'direct' "
                                "(PTX_BF16_STEM=direct), or run %s in float32" % name)
+            # the 2-D ResNets (resnet18..152): on the direct bf16 stem only, as well
+            net_2d = (kind == "resnet" and arch is not None and arch.dims == 2 and name in BF16_FAMILIES_2D
+                      and not arch.nonlocal_layers and arch.block in ("basic", "bottleneck"))
+            if net_2d and self.bf16_stem != "direct":
+                raise PtxError("bf16 2-D ResNets run on the direct bf16 stem only (its kT = 1 case; there is no fold route for a "
+                               "Conv2d stem): set Engine.bf16_stem = 'direct' (PTX_BF16_STEM=direct), or run %s in float32" % name)
             # the standalone non-local blocks and MNISTNonLocalNet run on the bf16 attention kernel
-            if not nl_net and kind not in BF16_NL_KINDS + BF16_GEN_KINDS + ("slowfast",) and (
+            if not nl_net and not net_2d and kind not in BF16_NL_KINDS + BF16_GEN_KINDS + ("slowfast",) and (
                     kind != "resnet" or name.split("@")[0] not in BF16_FAMILIES or arch is None or arch.nonlocal_layers
                     or arch.dims != 3 or arch.block not in ("basic", "bottleneck")):
                 raise PtxError("bf16 inference covers the ResNet3D (resnet3d10..200) and R(2+1)D (r2plus1d10..50) families, "
-                               "the non-local blocks, the BigGAN-deep generator and (under bf16_stem = 'direct') SlowFast and "
-                               "the non-local ResNets; "
+                               "the non-local blocks, the BigGAN-deep generator and (under bf16_stem = 'direct') SlowFast, "
+                               "the non-local ResNets and the 2-D ResNets (resnet18..152); "
                                "%s (plan kind %r) has bf16 parameters: run it in float32" % (name, kind))
         if kind == "nlblock":                    # a standalone NonLocalBlock3D: [B,C,T,H,W] -> [B,C,T,H,W]
             N, Cc, T, H, W = self.shape

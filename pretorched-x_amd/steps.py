@@ -230,6 +230,8 @@ class Packed:
             if w.dtype != torch.bfloat16 or not w.is_cuda:
                 raise PtxError("weights of a bf16 model must be bf16 CUDA tensors on the plan's device (got %s)" % w.dtype)
             if self.fold_hw:          # [Co][Cin][kT][kH][kW] -> [Co][(kh*kW + kw)*Cin + c][kT][1][1] (ptx_im2col_hw_bf16's order)
+                if w.dim() == 4:      # a 2-D ResNet's Conv2d stem: kT = 1
+                    w = w.unsqueeze(2)
                 co, ci, kt, kh, kw = w.shape
                 w = w.permute(0, 3, 4, 1, 2).reshape(co, kh * kw * ci, kt, 1, 1)
             w = w.float()

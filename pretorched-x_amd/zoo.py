@@ -453,11 +453,13 @@ class Relation(nn.Module):
         self.eval()
 
     def forward(self, input):
-        from .heads import relation_mlp
+        from .heads import relation_mlp, round_bf16
         if eager.wanted(self, input):
             return eager.relation(self, input)
         flat = input.contiguous().view(-1, self.num_inputs * self.in_features)
         out = relation_mlp(flat, self.relate[1], self.relate[3])
+        if input.dtype == torch.bfloat16:       # bf16 module: hidden vector and sums in fp32, the output rounded once
+            out = round_bf16(out)
         return out.view(input.size(0), -1, self.out_features)
 
 
@@ -481,7 +483,7 @@ class MultiScaleRelation(nn.Module):
     def forward(self, input):
         import numpy as np
         from ._lib import PTX_REL_MAX_FRAMES, PTX_REL_MAX_SETS
-        from .heads import relation_mlp, relation_scale
+        from .heads import relation_mlp, relation_scale, round_bf16
         x = input.contiguous().view(-1, self.num_input, self.in_features)        # [B, T, F]
         if eager.wanted(self, input):          # trn.py:95-113 on the torch.nn path: same RNG consumption
             outs = []
@@ -490,7 +492,8 @@ class MultiScaleRelation(nn.Module):
                 for idx in picks:
                     outs.append(self.relations[si](input[..., self.relations_scales[si][idx], :]))
             return torch.stack(outs).sum(0).view(input.size(0), -1, self.out_features)
-        grouped = (self.in_features % 4 == 0 and self.num_input <= PTX_REL_MAX_FRAMES
+        bf16 = input.dtype == torch.bfloat16    # bf16 module: the gather kernel reads 16-byte bf16 frames
+        grouped = (self.in_features % (8 if bf16 else 4) == 0 and self.num_input <= PTX_REL_MAX_FRAMES
                    and max(self.subsample_scales) <= PTX_REL_MAX_SETS)
         total = None
         for si in range(len(self.scales)):
@@ -505,6 +508,8 @@ class MultiScaleRelation(nn.Module):
             for sub_idx in subsets:
                 flat = x[:, sub_idx, :].contiguous().view(-1, rel.num_inputs * rel.in_features)
                 total = relation_mlp(flat, rel.relate[1], rel.relate[3], out=total, accumulate=total is not None)
+        if bf16:                                # the sum over scales accumulated in fp32 (PTX_EPI_ACCUM), rounded once
+            total = round_bf16(total)
         return total.view(input.size(0), -1, self.out_features)
 
 
@@ -644,12 +649,17 @@ class TRN(nn.Module):
     def forward_views(self, video, opts=None, views=None, reduce="softmax", chunk=None):
         """Decoded uint8 video [N,Tv,H,W,3] -> class probabilities fp32 [N, classes] averaged over `views` (a
         `transforms.SampleViews` with out="frames" and num_frames == num_segments; sampling="segments" is TSN's rule).
-        reduce / chunk as Engine.forward_views; every chunk goes through forward_frames."""
+        reduce / chunk as Engine.forward_views; every chunk goes through forward_frames.  A bfloat16 TRN needs its backbone's
+        engine under bf16_stem = "direct" (the frames are read in the stem); its bf16 logits are reduced by ptx_views_mean."""
         from ._lib import PtxError
         from .heads import check_views, run_views
         from .plan import model_precision
-        if model_precision(self.base_model) != "fp32":
-            raise PtxError("TRN.forward_views runs float32 models only")
+        prec = model_precision(self.base_model)
+        if prec == "bf16" and self.base_model._engine.bf16_stem != "direct":
+            raise PtxError("TRN.forward_views: a bfloat16 TRN reads the frames in its backbone's direct bf16 stem: set "
+                           "model.base_model.engine().bf16_stem = 'direct' (PTX_BF16_STEM=direct)")
+        if prec not in ("fp32", "bf16"):
+            raise PtxError("TRN.forward_views runs float32 and bfloat16 models (this model's parameters are %s)" % prec)
         check_views(views, self, "frames", "TRN.forward_views")
         if views.num_frames != self.num_segments:
             raise PtxError("TRN.forward_views: the sampler draws %d frames per clip, the model has num_segments = %d" % (
