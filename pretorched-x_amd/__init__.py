@@ -32,6 +32,16 @@ from .zoo import (ARCHS, TRN, Arch, HierarchicalRelation, MNISTNonLocalNet, Mult
 
 __version__ = "0.1.0"
 
+
+def update_bn(loader, model, device=None, momentum=None, reset=True):
+    """torch.optim.swa_utils.update_bn(loader, model, device) on the HIP engine: recompute running_mean / running_var /
+    num_batches_tracked of every BatchNorm with one forward-only pass over `loader` (clips, or lists / tuples whose first
+    element is the clip), every batch normalised by its own statistics.  momentum / reset: Engine.update_bn.  Models the
+    batch-statistics plans do not cover raise PtxError (plan.BATCH_STATS_SCOPE); nothing runs on torch.nn."""
+    from .plan import check_batch_stats_scope
+    check_batch_stats_scope(model)
+    return model.engine().update_bn(model, loader, device=device, momentum=momentum, reset=reset)
+
 # ---------------------------------------------------------------------------------------------
 # pretrained_settings: same keys/values the reference publishes (resnet3D.py:18-55,
 # nonlocalnet.py:11-47, torchvision_models.py:40-112).  URLs need network access, which this

@@ -21,6 +21,7 @@ MIX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_mix.h
 STEM_STRIDED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_stem_strided.h")  # the frame-strided bf16 stem
 NL_KS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_nl_ks.h")      # the bf16 attention's two forms by name
 LINEAR_BF16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_linear_bf16.h")  # Linear layers with bf16 weights
+BN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_bn.h")            # batch-statistics BatchNorm (update_bn)
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -468,6 +469,22 @@ SIGNATURES_LINEAR_BF16 = {
 }
 
 
+class BnApplyDesc(C.Structure):
+    """ptx_bn_apply_desc: y = act(raw * scale + shift [+ residual]) on [N][T][H][W] positions of C channels."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "H", "W", "C", "ldx", "ldy")] + [("flags", C.c_uint32)] + \
+               [(n, C.c_int32) for n in ("ldr", "res_C", "res_T", "res_H", "res_W", "res_sT", "res_sH", "res_sW")]
+
+
+# include/ptx_amd_bn.h: batch-statistics BatchNorm forward (csrc/bn_batch.hip; update_bn), bound the same way
+# (tests/test_update_bn_host.py)
+SIGNATURES_BN = {
+    "ptx_bn_batch_stats_workspace_bytes": (C.c_size_t, [_L, _I]),
+    "ptx_bn_batch_stats_f32": (C.c_int, [_P, _L, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "ptx_bn_batch_update_f32": (C.c_int, [_P, _P, _L, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "ptx_bn_apply_f32": (C.c_int, [C.POINTER(BnApplyDesc), _P, _P, _P, _P, _P, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -504,7 +521,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
                 list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()) + \
-                list(SIGNATURES_NL_KS.items()) + list(SIGNATURES_LINEAR_BF16.items()):
+                list(SIGNATURES_NL_KS.items()) + list(SIGNATURES_LINEAR_BF16.items()) + list(SIGNATURES_BN.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -1163,3 +1163,6 @@ extern "C" int ptx_views_mean(const void* logits, float* y, int32_t N, int32_t V
 // The Linear layers with bf16 weights (include/ptx_amd_linear_bf16.h: the bf16 TRN relation MLPs and classifier) are a file of
 // their own compiled as part of this translation unit (build.py follows the include, so its bytes are in this object's stamp).
 #include "linear_bf16.hip"
+
+// ... and so are the batch-statistics BatchNorm passes (include/ptx_amd_bn.h: what update_bn runs).
+#include "bn_batch.hip"

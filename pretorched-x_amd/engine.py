@@ -30,7 +30,7 @@ import torch.nn as nn
 from . import _lib, tuner
 from ._lib import NormDesc, PtxError, check
 from .heads import check_views, linear, relation_mlp, relation_scale, run_views, views_chunk, views_mean  # noqa: F401
-from .plan import BF16_FAMILIES, BF16_GEN_KINDS, BF16_NL_KINDS, Plan, _foldable, model_precision  # noqa: F401
+from .plan import BATCH_STATS_SCOPE, BF16_FAMILIES, BF16_GEN_KINDS, BF16_NL_KINDS, Plan, _foldable, check_batch_stats_scope, model_precision  # noqa: F401
 from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, Wino4Step, WinoStep, _WinoExec,  # noqa: F401
                     StemBf16Step, StemF32Step, StemStep, StemTfirStep, _ConcatRowsPack, _Ref, _dense16, _device_ctx, _geom, _ptr, _r4, _r8, _r128,
                     _same_geometry, _stem_ld, _stream, _t3, _tag, _tile_dims, issued_conv_flop)
@@ -242,10 +242,11 @@ class Engine:
         own = self._owner() if self._owner is not None else None
         return own if own is not None else model
 
-    def dry_plan(self, model, shape):
+    def dry_plan(self, model, shape, batch_stats=False):
         """Compile a plan on the 'meta' device: every descriptor, tile choice and buffer shape is
-        produced, nothing is allocated or launched.  Host-logic tests use this without a GPU."""
-        return Plan(self, model, shape, torch.device("meta"))
+        produced, nothing is allocated or launched.  Host-logic tests use this without a GPU.
+        batch_stats: the batch-statistics flavour update_bn runs -- always ONE plan for the whole batch, whatever `lanes` says."""
+        return Plan(self, model, shape, torch.device("meta"), batch_stats=batch_stats)
 
     # ------------------------------------------------------------------------------------
     @staticmethod
@@ -307,19 +308,20 @@ class Engine:
                     check(getattr(_lib.lib(), fn)(C.c_void_p(tab.data_ptr()), len(lst), C.c_void_p(out.data_ptr()), _stream()), fn)
             return int(out.item())
 
-    def plan_for(self, model, x, shape=None, norm=None, lane=0):
+    def plan_for(self, model, x, shape=None, norm=None, lane=0, batch_stats=False):
         """shape / norm: the NCDHW view and NormDesc of a uint8-frames input (forward_frames).  lane: which of the
-        Engine.lanes concurrent slices this plan serves -- lanes of one shape are separate plans (separate buffers)."""
+        Engine.lanes concurrent slices this plan serves -- lanes of one shape are separate plans (separate buffers).
+        batch_stats: the batch-statistics flavour of this shape (update_bn), a plan of its own next to the eval plan."""
         shape = tuple(x.shape) if shape is None else tuple(shape)
         nkey = None if norm is None else (tuple(norm.mean), tuple(norm.std), norm.swap_rb, norm.to_255)
-        key = (shape, x.device.index, nkey) + ((lane,) if lane else ())
+        key = (shape, x.device.index, nkey) + ((lane,) if lane else ()) + (("batch_stats",) if batch_stats else ())
         if model_precision(model) == "bf16":
             key += ("bf16",) + (("direct",) if self._bf16_stem == "direct" else ())
         with self._lock:
             plan = self._plans.get(key)
             fresh = plan is None
             if fresh:
-                plan = Plan(self, model, shape, x.device, norm)
+                plan = Plan(self, model, shape, x.device, norm, batch_stats=batch_stats)
                 self.plan_builds += 1
                 self._plans[key] = plan
                 while len(self._plans) > max(1, self.max_plans):
@@ -724,6 +726,77 @@ class Engine:
             run = lambda clip: self.forward(model, clip)
         return run_views(video, views, run, mb, reduce, chunk)
 
+    # ------------------------------------------------------------------------------------
+    def update_bn(self, model, loader, device=None, momentum=None, reset=True):
+        """torch.optim.swa_utils.update_bn(loader, model, device) on the HIP engine: one forward-only pass over `loader` in which
+        every BatchNorm of the trunk normalises with the batch's own mean and biased variance and moves its running_mean /
+        running_var / num_batches_tracked, as train()-mode F.batch_norm does.  `loader` yields clips, or lists / tuples
+        whose first element is the clip; with `device` each clip is moved there first.  reset: running statistics are reset
+        first (as torch does).  momentum None: the cumulative average over the pass, every batch with equal weight (what
+        torch's update_bn sets); a float: that factor for every layer.  Neither model.training nor any BN's `.momentum` is
+        touched, and no torch.nn forward runs.  The running statistics of the pass live in buffers of the pass and are
+        copied into the BatchNorm buffers when the loader is exhausted (copy_ bumps their version counters, so the next
+        eval-mode forward re-folds the filters without refresh()).  Each batch runs through ONE batch-statistics plan
+        (Plan(batch_stats=True)): never clip lanes, never chunks -- both would compute part-batch statistics -- and always
+        the fp32 tiles (`precision = "x3"` is ignored)."""
+        check_batch_stats_scope(model)
+        if momentum is not None and not (isinstance(momentum, (int, float)) and not isinstance(momentum, bool) and 0.0 <= momentum <= 1.0):
+            raise PtxError("update_bn: momentum must be None or a number in [0, 1] (got %r)" % (momentum,))
+        bns = [m for m in model.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+        for bn in bns:
+            if not bn.track_running_stats or bn.running_mean is None:
+                raise PtxError("update_bn: every BatchNorm must track running statistics")
+            if reset:
+                bn.reset_running_stats()         # in place: zero_() / fill_(1) / zero_()
+        run = sizes = tracked = dev = None
+        dims = model.arch.dims
+        for batch in loader:
+            x = batch[0] if isinstance(batch, (list, tuple)) else batch
+            if device is not None:
+                x = x.to(device)
+            if not isinstance(x, torch.Tensor) or not x.is_cuda:
+                raise PtxError("update_bn: clips must be CUDA (ROCm) tensors -- there is no CPU path in this call (pass device=...)")
+            if x.dtype != torch.float32 or x.dim() != (4 if dims == 2 else 5):
+                raise PtxError("update_bn: expected a float32 %d-D clip batch, got %s %s" % (4 if dims == 2 else 5, x.dtype, tuple(x.shape)))
+            if _first_weight(model).device != x.device or (dev is not None and dev != x.device):
+                raise PtxError("update_bn: clips on %s but parameters on %s (one device per pass)" % (x.device, _first_weight(model).device))
+            dev = x.device
+            if x.shape[0] > self._max_batch(model, x.shape[1:]):
+                raise PtxError("update_bn: a batch of %d clips of %s exceeds the 2 GiB per-launch limit (%d clips); batch statistics "
+                               "need the whole batch in one plan -- use smaller batches" % (
+                                   x.shape[0], tuple(x.shape[1:]), self._max_batch(model, x.shape[1:])))
+            x = _dense16(x)
+            with torch.cuda.device(dev):
+                plan = self.plan_for(model, x, batch_stats=True)
+                self._maybe_tune(model, plan, x)
+                with plan.exclusive():
+                    plan.bind(model)
+                    if run is None:
+                        if {id(plan.get(r)) for r in plan.bn_refs} != {id(bn) for bn in bns} or len(plan.bn_refs) != len(bns):
+                            raise PtxError("update_bn: the model holds BatchNorm layers outside its trunk (or one used twice)")
+                        sizes = list(plan.bn_sizes)
+                        run = tuple(torch.zeros_like(t) for t in plan.bn_own_run)
+                        layers = [plan.get(r) for r in plan.bn_refs]
+                        for (off, c), bn in zip(sizes, layers):
+                            run[0][off:off + c].copy_(bn.running_mean)
+                            run[1][off:off + c].copy_(bn.running_var)
+                        tracked = [0] * len(layers) if reset else [int(v) for v in torch.stack([bn.num_batches_tracked for bn in layers]).tolist()]
+                    elif list(plan.bn_sizes) != sizes:
+                        raise PtxError("update_bn: the BatchNorm layers of this batch's plan differ from the first batch's (internal error)")
+                    tracked = [t + 1 for t in tracked]
+                    plan.bn_f[:] = [float(momentum) if momentum is not None else 1.0 / t for t in tracked]
+                    plan.bn_run = run
+                    try:
+                        plan.run_features(x)
+                    finally:
+                        plan.bn_run = plan.bn_own_run
+        if run is not None:
+            with torch.cuda.device(dev), torch.no_grad():
+                for (off, c), bn, t in zip(sizes, layers, tracked):
+                    bn.running_mean.copy_(run[0][off:off + c])
+                    bn.running_var.copy_(run[1][off:off + c])
+                    bn.num_batches_tracked.fill_(t)
+
     # ------------------------------------------------------------------------------------ tuner.py
     def autotune(self, model, x, iters=3, verbose=False, persist=False, only_untuned=False, plan=None):
         return tuner.autotune(self, model, x, iters, verbose, persist, only_untuned, plan)
@@ -758,6 +831,11 @@ class EngineOwner:
         `engine().check_weights = False` need this call (or `engine().check_weights = "checksum"`)."""
         self._engine.invalidate()
         return self
+
+    def update_bn(self, loader, momentum=None, reset=True):
+        """Recompute the running statistics of every BatchNorm with a forward-only pass over `loader` on the HIP engine
+        (Engine.update_bn; `pretorched_x_amd.update_bn(loader, model, device)` is torch.optim.swa_utils.update_bn's signature)."""
+        return self._engine.update_bn(self, loader, momentum=momentum, reset=reset)
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)

@@ -21,6 +21,8 @@ from ._lib import (ConvDesc, ConvFusedExt, ConvProgramInfo, ConvStage, NonlocalD
                    PTX_F16_OPERANDS, PTX_F16X3_OPERANDS, PTX_NL_BF16, PTX_NL_F16, PTX_NL_OUT_F16, PTX_NL_RELU, PTX_NL_SCALE,
                    PTX_NL_SOFTMAX, PTX_NL_X3, PTX_POOL_BF16, PTX_POOL_PAD_ZERO, PTX_POOL_SAME, PTX_PRO_UP2, PTX_RES_F16,
                    PTX_SPLITK_FUSED, PTX_STEM_SRC_BF16_NCDHW, PTX_STEM_SRC_U8_NTHWC, PtxError, check)
+from ._lib import BnApplyDesc
+from .steps import BnApplyStep, BnStatsStep, BnUpdateStep
 from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step, StemTfirStep, TFIR_SCHEMES, Wino4Step, WinoStep, _WinoExec,
                     StemStep, _ConcatRowsPack, _Ref, _device_ctx, _geom, _ptr, _r4, _r8, _r128, _same_geometry, _stem_ld, _stream,
                     _t3, _tag)
@@ -63,13 +65,56 @@ def model_precision(model):
     return {torch.bfloat16: "bf16", torch.float16: "fp16"}.get(getattr(w, "dtype", None), "fp32")
 
 
+# Batch-statistics plans (Plan(batch_stats=True): what Engine.update_bn runs) cover float32 models of plan kind "resnet" whose
+# convs are nn.Conv3d / nn.Conv2d / (2+1)D pairs and that hold no non-local block
+BATCH_STATS_SCOPE = ("float32 resnet3d10..200, r2plus1d10..50, resnext3d10..200, wideresnet3d50, preact_resnet3d10..200 and the 2-D "
+                     "resnet18..152 (either shortcut type), built by this package and living on the GPU -- not bfloat16 / float16 "
+                     "models, non-local networks, MultiViewConv networks, SlowFast, I3D, TRN, BigGAN or adopted instances")
+
+
+def check_batch_stats_scope(model):
+    """Raise PtxError unless `model` is one a batch-statistics plan can be compiled for (BATCH_STATS_SCOPE)."""
+    name = str(getattr(model, "arch_name", None) or type(model).__name__)
+    arch = getattr(model, "arch", None)
+    why = None
+    if getattr(model, "_engine", None) is None:
+        why = "it does not run on the HIP engine"
+    elif name.startswith("adopted:") or "_ptx_twin" in getattr(model, "__dict__", {}):
+        why = "it is an adopted instance"
+    elif getattr(model, "plan_kind", "resnet") != "resnet" or arch is None or not hasattr(arch, "block"):
+        why = "its plan kind is %r" % getattr(model, "plan_kind", None)
+    elif model_precision(model) != "fp32":
+        why = "its parameters are %s" % model_precision(model)
+    elif arch.nonlocal_layers:
+        why = "it holds non-local blocks"
+    elif arch.conv == "mv":
+        why = "its convs are MultiViewConv"
+    if why is not None:
+        raise PtxError("update_bn does not cover %s (%s): it runs %s" % (name, why, BATCH_STATS_SCOPE))
+
+
 def _foldable(conv, x):
     """Small-Cin first conv reading the raw NCDHW input: fold kW into the channel axis."""
     return isinstance(x, RawInput)
 
 
 class Plan:
-    def __init__(self, engine, model, shape, dev, norm=None):
+    def __init__(self, engine, model, shape, dev, norm=None, batch_stats=False):
+        # batch_stats: the second plan flavour of a (shape, device) -- every BatchNorm normalises with the moments of THIS batch
+        # (train()-mode F.batch_norm) and moves its running statistics: conv_bn becomes the raw conv + statistics + update +
+        # apply, nothing is fused across a BN (no chained pairs, no dual-source shortcut GEMM, no conv programs), the
+        # arithmetic is fp32 whatever Engine.precision says, and the plan ends at the trunk's features (Engine.update_bn)
+        self.batch_stats = bool(batch_stats)
+        if self.batch_stats:
+            check_batch_stats_scope(model)
+            if norm is not None:
+                raise PtxError("update_bn takes float32 clips, not uint8 frames")
+        self.bn_steps = []               # BnStatsStep per BatchNorm, in execution order (batch-statistics plans)
+        self.bn_refs, self.bn_sizes = [], []      # ... their modules (_Ref) and (offset into bn_run, channels)
+        self.bn_f = []                   # ... the factor f of their running-statistics update (set per batch by the pass)
+        self.bn_run = None               # (running_mean, running_var) of every BN, concatenated: the plan's own scratch pair
+        self.bn_own_run = None           # ... unless a pass points bn_run at its buffers (Engine.update_bn)
+        self.bn_ws_bytes, self.bn_ws, self.bn_ws_ptr = 0, None, C.c_void_p(0)         # partial sums of the statistics kernel
         self.dev = dev
         self.shape = tuple(shape)        # always the NCDHW / NCHW view of the input
         self.norm = norm                 # NormDesc when the input is uint8 frames (Engine.forward_frames)
@@ -85,7 +130,7 @@ class Plan:
         self.alt_steps = []      # AltStep: chained launch | the two launches, chosen by measurement
         # chained convs (conv -> 1x1x1 conv in one launch): fp32 and split-operand plans; PTX_CHAIN=0 keeps every conv its
         # own launch
-        self.chain = os.environ.get("PTX_CHAIN", "1") != "0"
+        self.chain = os.environ.get("PTX_CHAIN", "1") != "0" and not self.batch_stats
         self.packs = []
         self.acts = []
         self._pack_cache = {}
@@ -97,14 +142,14 @@ class Plan:
         self.keepalive = []
         self.tuned = False
         self.graph = None
-        self.fuse_shortcut = os.environ.get("PTX_FUSE_SHORTCUT", "1") != "0"
+        self.fuse_shortcut = os.environ.get("PTX_FUSE_SHORTCUT", "1") != "0" and not self.batch_stats
         # arithmetic: the model's parameter dtype decides bf16 (every conv on the bf16 tiles, bf16 activations); for fp32
         # models Engine.precision picks fp32 / x3
         prec = model_precision(model)
         if prec == "fp16":
             raise PtxError("fp16 models (model.half()) are not supported: use bfloat16 (model.to(torch.bfloat16)) or float32")
         self.bf16 = prec == "bf16"
-        self.precision = "bf16" if self.bf16 else engine.precision
+        self.precision = "bf16" if self.bf16 else "fp32" if self.batch_stats else engine.precision
         self.x3 = self.precision == "x3"     # split fp32 operands on the fp16 matrix cores
         # qualified names of the model's modules: everything the plan keeps from the model is a _Ref
         self._names = {id(m): n for n, m in model.named_modules()}
@@ -127,8 +172,15 @@ class Plan:
         self.half_plan = self.gen_patch = False      # BigGAN-deep plans (plans.build_biggan): fp16 operands / patch kernels
         with _device_ctx(dev):
             self._build(model)
-            self._fuse_programs()
+            if not self.batch_stats:
+                self._fuse_programs()
             self._bind_wino_arena()
+            if self.bn_steps:
+                f32 = dict(device=dev, dtype=torch.float32)
+                total = sum(_r4(c) for _, c in self.bn_sizes)
+                self.bn_own_run = self.bn_run = (torch.zeros(total, **f32), torch.ones(total, **f32))
+                self.bn_ws = torch.empty(self.bn_ws_bytes // 4, **f32)
+                self.bn_ws_ptr = _ptr(self.bn_ws)
             if self.ws_bytes:
                 self.ws = torch.zeros(self.ws_bytes // 4, device=dev, dtype=torch.float32)
                 self.ws_ptr = _ptr(self.ws)
@@ -623,6 +675,8 @@ class Plan:
 
     def conv_bn(self, x, conv, bn, relu=False, res=None, res_kind=None, res_stride=1, label="conv", y=None):
         """nn.Conv{2,3}d or a (2+1)D pair, followed by `bn`, with the epilogue fused."""
+        if self.batch_stats and bn is not None:
+            return self._conv_bn_batch(x, conv, bn, relu, res, res_kind, res_stride, label, y)
         if hasattr(conv, "spatial_conv"):      # r2plus1d.py:85-88
             ks, ss, ps = _geom(conv.spatial_conv)
             fold = _foldable(conv.spatial_conv, x)
@@ -663,6 +717,73 @@ class Plan:
             s, p = (s[0], s[1], 1), (p[0], p[1], 0)
         return self.conv(x, self.pack(conv, bn, fold), s, p, relu=relu, res=res, res_kind=res_kind,
                          res_stride=res_stride, label=label, y=y, same=same)
+
+    def _conv_bn_batch(self, x, conv, bn, relu, res, res_kind, res_stride, label, y):
+        """conv_bn of a batch-statistics plan: the raw conv (bn=None: no fold, no activation, no residual -- on whatever
+        tiles / Winograd execution the library picks), then the BN on this batch's own moments, in place on the conv's output."""
+        if y is not None:
+            raise PtxError("%s: a batch-statistics plan writes no channel-slice targets" % label)
+        if hasattr(conv, "spatial_conv"):      # (2+1)D pair: its inner conv.bn takes batch statistics as well
+            mid = self.conv_bn(x, conv.spatial_conv, conv.bn, relu=True, label=label + ".spatial")
+            raw = self.conv_bn(mid, conv.temporal_conv, None, label=label + ".temporal")
+        elif isinstance(conv, (nn.Conv3d, nn.Conv2d)):
+            raw = self.conv_bn(x, conv, None, label=label)
+        else:
+            raise PtxError("%s: update_bn does not cover %s convs: it runs %s" % (label, type(conv).__name__, BATCH_STATS_SCOPE))
+        return self.bn_batch(raw, bn, relu, res, res_kind, res_stride, label + ".bn", y=raw)
+
+    def bn_batch(self, x, bn, relu, res=None, res_kind=None, res_stride=1, label="bn", y=None):
+        """Train()-mode BatchNorm of a batch-statistics plan on activation x, as three steps: the batch moments
+        (ptx_bn_batch_stats_f32), this batch's scale / shift + the running-statistics update (ptx_bn_batch_update_f32),
+        and y = act(x * scale + shift [+ res]) (ptx_bn_apply_f32; y may be x itself)."""
+        if not isinstance(bn, (nn.BatchNorm3d, nn.BatchNorm2d)) or not bn.track_running_stats or bn.running_mean is None:
+            raise PtxError("%s: update_bn needs nn.BatchNorm2d / nn.BatchNorm3d layers that track running statistics (got %s)" % (
+                label, type(bn).__name__))
+        if x.f16 or bn.num_features != x.C:
+            raise PtxError("%s: a %d-feature BatchNorm on a %d-channel %s activation" % (label, bn.num_features, x.C, x.t.dtype))
+        n = x.N * x.S
+        if n <= 1:      # F.batch_norm(training=True) raises ValueError here; the shapes are known now, nothing is launched
+            raise PtxError("%s: Expected more than 1 value per channel when computing batch statistics, got input size [%d, %d, %d, %d, %d]"
+                           % (label, x.N, x.C, x.T, x.H, x.W))
+        if y is None:
+            y = self.act(x.N, x.T, x.H, x.W, x.C)
+        f32 = dict(device=self.dev, dtype=torch.float32)
+        mean, var, scale, shift = (torch.empty(_r4(x.C), **f32) for _ in range(4))
+        self.keepalive += [mean, var, scale, shift]
+        index = len(self.bn_steps)
+        off = sum(_r4(c) for _, c in self.bn_sizes)
+        ref = self.ref(bn)
+        self.bn_refs.append(ref)
+        self.bn_sizes.append((off, x.C))
+        self.bn_f.append(1.0)
+        self.bn_ws_bytes = max(self.bn_ws_bytes, int(self.lib.ptx_bn_batch_stats_workspace_bytes(n, x.C)))
+        st = BnStatsStep()
+        st.plan, st.index, st.x, st.rows, st.C, st.ld, st.mean, st.var = self, index, _ptr(x.t), n, x.C, x.ld, _ptr(mean), _ptr(var)
+        st.label, st.hbm_bytes = label + ".stats", 4 * n * x.C
+        up = BnUpdateStep()
+        up.plan, up.index, up.off, up.n, up.C, up.eps, up.bn = self, index, off, n, x.C, float(bn.eps), ref
+        up.mean, up.var, up.scale, up.shift, up.label = st.mean, st.var, _ptr(scale), _ptr(shift), label + ".update"
+        d = BnApplyDesc()
+        d.N, d.T, d.H, d.W, d.C, d.ldx, d.ldy = x.N, x.T, x.H, x.W, x.C, x.ld, y.ld
+        d.flags = PTX_EPI_RELU if relu else 0
+        if res is not None:
+            d.ldr = res.ld
+            if res_kind == "padA":
+                d.flags |= PTX_EPI_RES_PADA
+                d.res_C, d.res_T, d.res_H, d.res_W = res.C, res.T, res.H, res.W
+                d.res_sT = d.res_sH = d.res_sW = int(res_stride)
+            elif res_kind is None:
+                d.flags |= PTX_EPI_RES_ADD
+                assert (res.N, res.T, res.H, res.W, res.C) == (x.N, x.T, x.H, x.W, x.C), "residual shape"
+            else:
+                raise PtxError("%s: residual kind %r has no batch-statistics form" % (label, res_kind))
+        ap = BnApplyStep()
+        ap.d, ap.raw, ap.scale, ap.shift, ap.y, ap.label = d, st.x, up.scale, up.shift, _ptr(y.t), label + ".apply"
+        ap.res = _ptr(res.t) if res is not None else C.c_void_p(0)
+        ap.hbm_bytes = 4 * n * x.C * (3 if res is not None else 2)
+        self.steps += [st, up, ap]
+        self.bn_steps.append(st)
+        return y
 
     def stem_direct(self, raw, conv, bn, relu, label):
         """Split-operand stems skip the kW fold: the input becomes [N,T,H,W,4] (16-byte positions) and
@@ -1341,7 +1462,8 @@ class Plan:
                 # conv_chain composes conv2's geometry with a UNIT-stride, unpadded pointwise tail: anything else keeps
                 # the two launches (the reference's bottlenecks qualify, resnet3D.py:117-119; a user-edited block may not)
                 plain_tail = _geom(blk.conv3) == ((1, 1, 1), (1, 1, 1), (0, 0, 0)) and not getattr(blk.conv3, "tf_same", False)
-                tail = None if not plain_tail else self.conv_chain(o, self.pack(blk.conv2, blk.bn2), s2, p2, self.pack(blk.conv3, blk.bn3), relu1=True,
+                # (a batch-statistics plan chains nothing, and must not even pack the BN-folded filters of the pair)
+                tail = None if not plain_tail or self.batch_stats else self.conv_chain(o, self.pack(blk.conv2, blk.bn2), s2, p2, self.pack(blk.conv3, blk.bn3), relu1=True,
                                        relu2=True, res=res, label=name + ".conv2+conv3", y=out)
             first = len(self.steps)
             o2 = self.conv_bn(o, blk.conv2, blk.bn2, relu=True, label=name + ".conv2")
@@ -1360,6 +1482,8 @@ class Plan:
     def bn_relu(self, x, bn, label):
         """Eval-mode BN -> ReLU as one HBM pass ahead of a conv (pre-activation blocks): the BN is folded to
         a per-channel affine by ptx_cbn_fold whenever the weights change."""
+        if self.batch_stats:    # this batch's own moments; x stays as it is (the residual reads it)
+            return self.bn_batch(x, bn, True, label=label)
         f32 = dict(device=self.dev, dtype=torch.float32)
         sc, sh = torch.empty(x.C, **f32), torch.empty(x.C, **f32)
         self.keepalive += [sc, sh]

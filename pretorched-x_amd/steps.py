@@ -719,3 +719,46 @@ class StemBf16Step(_Step):
             return
         check(_lib.lib().ptx_conv_stem_bf16_fwd(C.byref(self.d), self.plan.in_ptr, self.src, norm, self.w, self.b, self.y, st),
               self.label)
+
+
+class BnStatsStep(_Step):
+    """One ptx_bn_batch_stats_f32 call (two launches) of a batch-statistics plan: mean and biased variance of activation `x`
+    over its rows, into the plan-owned `mean` / `var` of BatchNorm number `index`.  The partials go through the plan's
+    `bn_ws` (bound after the plan is built: one workspace, the largest need)."""
+    __slots__ = ("plan", "index", "x", "rows", "C", "ld", "mean", "var", "label", "macs", "hbm_bytes")
+    _defaults = {"macs": 0, "hbm_bytes": 0}
+    kernel = "bn_batch_stats_f32"
+
+    def __call__(self, st):
+        p = self.plan
+        check(_lib.lib().ptx_bn_batch_stats_f32(self.x, self.rows, self.C, self.ld, self.mean, self.var, p.bn_ws_ptr, p.bn_ws_bytes, st),
+              self.label)
+
+
+class BnUpdateStep(_Step):
+    """One ptx_bn_batch_update_f32 launch: this batch's scale / shift, and the running statistics of BatchNorm `index` -- its
+    slice of the plan's `bn_run` pair, which Engine.update_bn points at the buffers of the pass -- moved by the factor
+    `plan.bn_f[index]` the pass sets per batch."""
+    __slots__ = ("plan", "index", "off", "n", "C", "eps", "mean", "var", "gamma", "beta", "scale", "shift", "bn", "label", "macs", "hbm_bytes")
+    _defaults = {"macs": 0, "hbm_bytes": 0}
+    kernel = "bn_batch_update_f32"
+
+    def __call__(self, st):
+        p = self.plan
+        bn = p.get(self.bn)
+        gamma = _ptr(bn.weight.detach()) if bn.weight is not None else None
+        beta = _ptr(bn.bias.detach()) if bn.bias is not None else None
+        rm, rv = p.bn_run
+        check(_lib.lib().ptx_bn_batch_update_f32(self.mean, self.var, self.n, C.c_float(p.bn_f[self.index]), C.c_float(self.eps),
+                                                 gamma, beta, _ptr(rm, self.off), _ptr(rv, self.off), self.scale, self.shift,
+                                                 self.C, st), self.label)
+
+
+class BnApplyStep(_Step):
+    """One ptx_bn_apply_f32 launch: y = act(raw * scale + shift [+ residual]) with the scale / shift of this batch."""
+    __slots__ = ("d", "raw", "scale", "shift", "res", "y", "label", "macs", "hbm_bytes")
+    _defaults = {"macs": 0, "hbm_bytes": 0}
+    kernel = "bn_apply_f32"
+
+    def __call__(self, st):
+        check(_lib.lib().ptx_bn_apply_f32(C.byref(self.d), self.raw, self.scale, self.shift, self.res, self.y, st), self.label)
