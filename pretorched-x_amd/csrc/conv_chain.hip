@@ -200,7 +200,7 @@ extern "C" int ptx_conv3d_chain_fwd(const ptx_conv3d_desc* conv, const ptx_conv3
     const ptx_conv3d_desc* d = conv;
     ConvArgs a{};
     a.x = x; a.w = w_packed; a.bias = bias; a.res = res; a.y = y;
-    a.N = d->N; a.Ti = d->Ti; a.Hi = d->Hi; a.Wi = d->Wi; a.ldx = d->ldx; a.kA = d->ldx;
+    a.N = d->N; a.Ti = d->Ti; a.Hi = d->Hi; a.Wi = d->Wi; a.ldx = d->ldx; a.kA = std::min(d->ldx, d->Kc);   // as make_conv_args
     a.To = d->To; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co; a.ldy = tail->ldy; a.k_live = d->Ci;
     a.kT = d->kT; a.kH = d->kH; a.kW = d->kW; a.sT = d->sT; a.sH = d->sH; a.sW = d->sW;
     a.pT = d->pT; a.pH = d->pH; a.pW = d->pW;

@@ -131,12 +131,12 @@ static int launch_cfg(const ConvArgs& a, dim3 grid, hipStream_t st) {
     }
     if constexpr (BK == 24 && MT == 32 && !DMA) {
         // kW-folded stem: one 24-wide chunk per tap of which at most 22 columns are live
-        if (a.k_live <= 22 && a.kA == 24 && a.kB == 24)
+        if (a.k_live <= 22 && a.ldx == 24 && a.kA == 24 && a.kB == 24)
             return launch_one<BM, BN, BK, WM, WN, MT, false, true, false, 2>(a, grid, st);
     }
     if constexpr (BK == 32 && MT == 32 && DMA && NSTAGE == 2 && BN == 64) {
         // kW-folded stem on 32-float rows (fold ld = 32): LDS-DMA staging, 11 MFMAs per tap as on the BK = 24 tiles
-        if (a.k_live <= 22 && a.kA == 32 && a.kB == 32 && !a.dual && a.groups <= 1)
+        if (a.k_live <= 22 && a.ldx == 32 && a.kA == 32 && a.kB == 32 && !a.dual && a.groups <= 1)
             return launch_one<BM, BN, BK, WM, WN, MT, false, true, true, 2>(a, grid, st);
     }
     if ((a.kA % BK) || (a.kB % BK) || (a.dual && ((a.kA2 % BK) || (a.wcol2 % BK))))
@@ -893,7 +893,9 @@ int make_conv_args(const ptx_conv3d_desc* d, const float* x, const float* x2, co
     }
     a = ConvArgs{};
     a.x = x; a.w = w_packed; a.bias = bias; a.res = res; a.y = y;
-    a.N = d->N; a.Ti = d->Ti; a.Hi = d->Hi; a.Wi = d->Wi; a.ldx = d->ldx; a.kA = d->ldx;
+    // K extent of the A operand per tap: the row's columns the packed filter has columns for.  Columns [Kc, ldx) of a wider
+    // row meet no filter column, so they are not read at all (0 * NaN would otherwise reach the sum)
+    a.N = d->N; a.Ti = d->Ti; a.Hi = d->Hi; a.Wi = d->Wi; a.ldx = d->ldx; a.kA = std::min(d->ldx, d->Kc);
     a.To = d->To; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co; a.ldy = d->ldy; a.k_live = d->Ci;
     a.kT = d->kT; a.kH = d->kH; a.kW = d->kW; a.sT = d->sT; a.sH = d->sH; a.sW = d->sW;
     a.pT = d->pT; a.pH = d->pH; a.pW = d->pW;
