@@ -22,6 +22,7 @@ STEM_STRIDED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_
 NL_KS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_nl_ks.h")      # the bf16 attention's two forms by name
 LINEAR_BF16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_linear_bf16.h")  # Linear layers with bf16 weights
 BN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_bn.h")            # batch-statistics BatchNorm (update_bn)
+WARP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_warp.h")        # interpolated affine / perspective warps
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -198,6 +199,15 @@ PTX_MIX_ERASE_NONE, PTX_MIX_ERASE_CONST, PTX_MIX_ERASE_NOISE = range(3)
 PTX_MIX_SRC_U8, PTX_MIX_SRC_F32, PTX_MIX_SRC_BF16 = range(3)
 (PTX_MIX_W_PARTNER, PTX_MIX_W_MODE, PTX_MIX_W_A, PTX_MIX_W_B, PTX_MIX_W_BOX, PTX_MIX_W_ERASE, PTX_MIX_W_ERASE_KIND, PTX_MIX_W_CONST,
  PTX_MIX_W_NOISE, PTX_MIX_ROW) = 0, 1, 2, 3, 4, 8, 12, 13, 16, 20
+
+
+class WarpDesc(C.Structure):
+    """ptx_warp_desc (ptx_amd_warp.h): the frames of a warp launch, its filter (a PTX_RESAMPLE_* code), the fill colour."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "H", "W", "filter", "fill_r", "fill_g", "fill_b", "reserved")]
+
+
+PTX_WARP_IDENTITY, PTX_WARP_AFFINE, PTX_WARP_PERSPECTIVE = range(3)
+PTX_WARP_COEFFS = 8
 
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
@@ -485,6 +495,14 @@ SIGNATURES_BN = {
 }
 
 
+# include/ptx_amd_warp.h: interpolated per-clip affine / perspective warps of uint8 frames (csrc/warp_frames.h), bound the same
+# way (tests/test_warp_frames_host.py)
+SIGNATURES_WARP = {
+    "ptx_warp_frames_supported": (C.c_int, [C.POINTER(WarpDesc), _P, _P]),
+    "ptx_warp_frames": (C.c_int, [C.POINTER(WarpDesc), _P, _P, _P, _P, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -521,7 +539,8 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WINO4.items()) + list(SIGNATURES_TFIR.items()) + \
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
                 list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()) + \
-                list(SIGNATURES_NL_KS.items()) + list(SIGNATURES_LINEAR_BF16.items()) + list(SIGNATURES_BN.items()):
+                list(SIGNATURES_NL_KS.items()) + list(SIGNATURES_LINEAR_BF16.items()) + list(SIGNATURES_BN.items()) + \
+                list(SIGNATURES_WARP.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

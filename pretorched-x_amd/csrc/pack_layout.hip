@@ -1443,3 +1443,7 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 // So is the last stage of the training input path (include/ptx_amd_mix.h): RandomErasing per clip and MixUp / CutMix across the
 // clips of the batch on the normalised values, from uint8 frames or a normalised clip, in one launch that writes the NCDHW clip.
 #include "batch_mix.h"
+
+// So are the interpolated per-clip warps (include/ptx_amd_warp.h): affine and perspective transforms of uint8 frames with
+// Pillow's bilinear / bicubic interpolation in fp64, one launch per batch.
+#include "warp_frames.h"

@@ -1089,8 +1089,9 @@ def rand_augment_space(num_bins, H, W):
             8 - (torch.arange(num_bins) / ((num_bins - 1) / 4)).round().int(), lin(255.0, 0.0), None, None]
 
 
-def _inverse_affine_matrix(center, angle, translate, shear):
-    """torchvision's _get_inverse_affine_matrix (scale 1): PIL's six coefficients, output pixel -> input position."""
+def _inverse_affine_matrix(center, angle, translate, shear, scale=1.0):
+    """torchvision's _get_inverse_affine_matrix: PIL's six coefficients, output pixel -> input position.  `scale` divides the
+    six entries before the translation and the centre go in, as torchvision does."""
     rot, sx, sy = math.radians(angle), math.radians(shear[0]), math.radians(shear[1])
     cx, cy = center
     tx, ty = translate
@@ -1098,7 +1099,7 @@ def _inverse_affine_matrix(center, angle, translate, shear):
     b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
     c = math.sin(rot - sy) / math.cos(sy)
     d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
-    m = [d, -b, 0.0, -c, a, 0.0]
+    m = [v / scale for v in (d, -b, 0.0, -c, a, 0.0)]
     m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
     m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
     m[2] += cx
@@ -1121,9 +1122,15 @@ def rand_augment_matrix(code, magnitude, H, W):
         return _inverse_affine_matrix((W * 0.5, H * 0.5), 0.0, (0, int(mag)), (0.0, 0.0))
     if code != _lib.PTX_RANDAUG_ROTATE:
         raise PtxError("rand_augment_matrix: op code %r is not geometric (1..5)" % (code,))
-    angle = -math.radians(mag % 360.0)
+    return rotation_matrix(mag, H, W)
+
+
+def rotation_matrix(angle, H, W, center=None):
+    """PIL.Image.Image.rotate's own matrix (expand=False, no translate) for `angle` degrees counter-clockwise on an H x W image:
+    the sine and cosine rounded to 15 decimals, about `center` = (cx, cy) (None: (W / 2, H / 2))."""
+    angle = -math.radians(float(angle) % 360.0)
     m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
-    cx, cy = W / 2, H / 2
+    cx, cy = (W / 2, H / 2) if center is None else center
     m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
     m[2] += cx
     m[5] += cy
@@ -1310,24 +1317,49 @@ def rand_augment_op_numpy(img, row, fill=(0, 0, 0)):
     return c.astype(np.uint8)
 
 
-def rand_augment_numpy(frames, params, fill=0):
+def _randaug_plan(params, H, W, N, fill, interpolation, who="RandAugment"):
+    """The checked launches of `params` on N clips of H x W frames under `interpolation`: (rows, warps).  "nearest": the rows
+    of `rand_augment_rows`, warps None.  "bilinear" / "bicubic": per position k, warps[k] is None or the (kinds int32 [N],
+    coeffs float64 [N, 8]) of a warp launch -- AFFINE with `rand_augment_matrix` for the clips whose op there is geometric,
+    IDENTITY for the others --, and those clips' rows are PTX_RANDAUG_IDENTITY."""
+    if interpolation == "nearest":
+        return _randaug_supported(rand_augment_rows(params, H, W, N, who), H, W, fill, who), None
+    codes, mags = _randaug_params(params, N, who)
+    geometric = np.isin(codes, _RANDAUG_GEOMETRIC)
+    rows = _randaug_supported(rand_augment_rows((np.where(geometric, _lib.PTX_RANDAUG_IDENTITY, codes), mags), H, W, N, who), H, W, fill, who)
+    warps = []
+    for k in range(codes.shape[1]):
+        if not geometric[:, k].any():
+            warps.append(None)
+            continue
+        kinds = np.where(geometric[:, k], _lib.PTX_WARP_AFFINE, _lib.PTX_WARP_IDENTITY).astype(np.int32)
+        coeffs = np.zeros((codes.shape[0], _lib.PTX_WARP_COEFFS), np.float64)
+        for n in np.nonzero(geometric[:, k])[0]:
+            coeffs[n, :6] = rand_augment_matrix(int(codes[n, k]), float(mags[n, k]), H, W)
+        warps.append(_warp_supported(kinds, coeffs, H, W, fill, interpolation, who))
+    return rows, warps
+
+
+def rand_augment_numpy(frames, params, fill=0, interpolation="nearest"):
     """The kernels' arithmetic in numpy: uint8 frames [N,T,H,W,3] and `params` = (codes [N, K], magnitudes [N, K]) -> uint8
     [N,T,H,W,3].  Every clip's positions run in order on every frame; contrast, autocontrast and equalize take the statistics of
-    the FRAME as it stands at their position.  The host-side model the tests compare with PIL; not a fallback (RandAugment never
+    the FRAME as it stands at their position.  With `interpolation` "bilinear" or "bicubic" the geometric ops are `warp_numpy`
+    of `rand_augment_matrix`'s coefficients.  The host-side model the tests compare with PIL; not a fallback (RandAugment never
     calls it)."""
     frames = np.asarray(frames)
     if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[-1] != 3:
         raise PtxError("rand_augment_numpy: frames must be uint8 [N,T,H,W,3], got %s %s" % (frames.dtype, frames.shape))
     fill = _randaug_fill(fill, "rand_augment_numpy")
+    interpolation = check_warp_interpolation(interpolation, "rand_augment_numpy")
     N, T, H, W, _ = frames.shape
-    rows = _randaug_supported(rand_augment_rows(params, H, W, N, "rand_augment_numpy"), H, W, fill, "rand_augment_numpy")
-    out = np.empty_like(frames)
-    for n in range(N):
-        for t in range(T):
-            img = frames[n, t]
-            for row in rows[n]:
-                img = rand_augment_op_numpy(img, row, fill)
-            out[n, t] = img
+    rows, warps = _randaug_plan(params, H, W, N, fill, interpolation, "rand_augment_numpy")
+    out = frames.copy()
+    for k in range(rows.shape[1]):
+        if warps is not None and warps[k] is not None:
+            out = warp_numpy(out, warps[k][0], warps[k][1], interpolation, fill)
+        for n in range(N):
+            for t in range(T):
+                out[n, t] = rand_augment_op_numpy(out[n, t], rows[n, k], fill)
     return out
 
 
@@ -1338,15 +1370,20 @@ class RandAugment:
 
     num_ops: ops per clip, 1..PTX_RANDAUG_MAX_OPS; magnitude: the bin, 0 <= magnitude < num_magnitude_bins; fill: what the
     geometric ops write where they have no source pixel, an integer or an RGB triple in 0..255; generator: a CPU torch.Generator
-    (None: torch's default one).
+    (None: torch's default one); interpolation: how shear, translate and rotate resample -- "nearest" (the default, PIL's
+    fixed-point walk inside the apply launch), "bilinear" or "bicubic" (a name, Pillow's code or an enum of those; the draws do
+    not depend on it).  With bilinear or bicubic a position where some clip's op is geometric runs a "warp" launch first
+    (include/ptx_amd_warp.h: those clips AFFINE with `rand_augment_matrix`'s coefficients in fp64, the others copied), then the
+    apply launch with those clips' rows rewritten to identity; the apply launch is skipped where every row of the position is
+    identity and the position does not write the call's output.
 
     `ra(frames)` augments uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3] (one draw per clip: N, or one; statistics are per
     frame) and keeps the draw as `last_params` = (codes CPU int32 [N, num_ops], magnitudes CPU float64 [N, num_ops]): per clip
     the op codes in running order, indexing `RANDAUG_OPS`, and the signed magnitudes.  `ra(frames, params=p)` applies a given
     draw (on any RandAugment, any num_ops in range).  Per position a call is one apply launch, plus a statistics launch when some
-    clip's op there is contrast, autocontrast or equalize (`last_launches`)."""
+    clip's op there is contrast, autocontrast or equalize (`last_launches`: "stats", "apply" and "warp" in running order)."""
 
-    def __init__(self, num_ops=2, magnitude=9, num_magnitude_bins=31, fill=0, generator=None):
+    def __init__(self, num_ops=2, magnitude=9, num_magnitude_bins=31, fill=0, generator=None, interpolation="nearest"):
         for name, v in (("num_ops", num_ops), ("magnitude", magnitude), ("num_magnitude_bins", num_magnitude_bins)):
             if not isinstance(v, int) or isinstance(v, bool):
                 raise PtxError("RandAugment: %s must be an integer, got %r" % (name, v))
@@ -1360,6 +1397,7 @@ class RandAugment:
             raise PtxError("RandAugment: generator must be a torch.Generator or None, got %r" % (generator,))
         self.num_ops, self.magnitude, self.num_magnitude_bins = num_ops, magnitude, num_magnitude_bins
         self.fill = _randaug_fill(fill)
+        self.interpolation = check_warp_interpolation(interpolation, "RandAugment")
         self.generator, self.last_params, self.last_launches = generator, None, ()
 
     def draw(self, n, H, W):
@@ -1386,18 +1424,23 @@ class RandAugment:
         of the rows (`rand_augment_rows`) for frames of that size.  No device is touched."""
         codes, mags = _randaug_params(params, N)
         if H is not None and W is not None:
-            _randaug_supported(rand_augment_rows((codes, mags), int(H), int(W), N), int(H), int(W), self.fill)
+            _randaug_plan((codes, mags), int(H), int(W), N, self.fill, self.interpolation)
         return torch.from_numpy(codes), torch.from_numpy(mags)
 
     def _rows_for(self, N, H, W, params):
-        """The checked host rows of a call on N clips of H x W frames: of a new draw (kept as last_params) or of `params`."""
+        """The checked host rows of a call on N clips of H x W frames: of a new draw (kept as last_params) or of `params`.  With an
+        interpolated filter a `_RandAugPlan`: the rows and the warp launches of `_randaug_plan`."""
         if params is None:
             params = self.last_params = self.draw(N, H, W)
-        return _randaug_supported(rand_augment_rows(params, H, W, N), H, W, self.fill)
+        rows, warps = _randaug_plan(params, H, W, N, self.fill, self.interpolation)
+        return rows if warps is None else _RandAugPlan(rows, warps)
 
     def _launch(self, f5, rows, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
         """The launches on contiguous uint8 CUDA frames f5 [N,T,H,W,3] with checked host rows [N, K, 8]: uint8 [N,T,H,W,3] or the
-        normalised [N,3,T,H,W] of `dtype`.  Positions ping-pong between two uint8 scratch buffers; the last one writes y."""
+        normalised [N,3,T,H,W] of `dtype`.  Positions ping-pong between two uint8 scratch buffers; the last one writes y.  `rows`
+        may be a `_RandAugPlan`, whose warp launches run in front of their positions."""
+        if isinstance(rows, _RandAugPlan):
+            return self._launch_warped(f5, rows, mode, norm, dtype)
         N, T, H, W, _ = f5.shape
         K = rows.shape[1]
         lib = _lib.lib()
@@ -1433,6 +1476,60 @@ class RandAugment:
         self.last_launches = tuple(launches)
         return y
 
+    def _launch_warped(self, f5, plan, mode, norm, dtype):
+        """`_launch` with an interpolated filter: per position the warp launch (when some clip's op there is geometric), the
+        statistics launch (when needed) and the apply launch, which is skipped where it would only copy into a scratch buffer."""
+        N, T, H, W, _ = f5.shape
+        rows, warps = plan.rows, plan.warps
+        K = rows.shape[1]
+        lib = _lib.lib()
+        launches = []
+        with torch.cuda.device(f5.device):
+            dev_rows = torch.from_numpy(rows.reshape(-1)).to(f5.device)                  # one upload
+            rows_p = C.c_void_p(dev_rows.data_ptr())
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            pool = []
+
+            def scratch(cur):                                                            # a uint8 buffer that is not `cur`
+                for b in pool:
+                    if b is not cur:
+                        return b
+                pool.append(torch.empty_like(f5))
+                return pool[-1]
+
+            if mode == _lib.PTX_RESIZE_OUT_U8:
+                y = torch.empty((N, T, H, W, 3), device=f5.device, dtype=torch.uint8)
+            else:
+                y = torch.empty((N, 3, T, H, W), device=f5.device, dtype=dtype)
+            stats = None
+            cur = f5
+            for k in range(K):
+                last = k == K - 1
+                if warps[k] is not None:
+                    dst = scratch(cur)
+                    _warp_launch(cur, dst, warps[k][0], warps[k][1], self.interpolation, self.fill, stream)
+                    launches.append("warp")
+                    cur = dst
+                    if not last and not rows[:, k, 0].any():                             # every row identity: nothing left to do
+                        continue
+                need = bool(np.isin(rows[:, k, 0], _RANDAUG_STATS).any())
+                desc = _lib.RandAugDesc(N, T, H, W, mode if last else _lib.PTX_RESIZE_OUT_U8, K, k, int(need), self.fill[0],
+                                        self.fill[1], self.fill[2], 0)
+                if need:
+                    if stats is None:
+                        stats = torch.empty(N * T * _lib.PTX_RANDAUG_STATS_WORDS, device=f5.device, dtype=torch.int32)
+                    check(lib.ptx_rand_augment_stats(C.byref(desc), C.c_void_p(cur.data_ptr()), rows_p, C.c_void_p(stats.data_ptr()),
+                                                     stream), "ptx_rand_augment_stats")
+                    launches.append("stats")
+                dst = y if last else scratch(cur)
+                check(lib.ptx_rand_augment_apply(C.byref(desc), C.c_void_p(cur.data_ptr()), rows_p,
+                                                 C.c_void_p(stats.data_ptr()) if need else None, C.c_void_p(dst.data_ptr()),
+                                                 C.byref(norm) if (last and norm is not None) else None, stream), "ptx_rand_augment_apply")
+                launches.append("apply")
+                cur = dst
+        self.last_launches = tuple(launches)
+        return y
+
     def __call__(self, frames, params=None):
         if not isinstance(frames, torch.Tensor):
             raise PtxError("RandAugment: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
@@ -1450,6 +1547,14 @@ class RandAugment:
         return self._launch(f5, self._rows_for(N, H, W, params)).view(frames.shape)
 
 
+class _RandAugPlan:
+    """The launches of a RandAugment call with an interpolated filter: `rows` [N, K, 8] and, per position, None or the (kinds,
+    coeffs) of its warp launch (`_randaug_plan`)."""
+
+    def __init__(self, rows, warps):
+        self.rows, self.warps = rows, warps
+
+
 def _apply_augment(augment, frames_u8, out, dtype, norm, augment_params):
     """The RandAugment half of TransformFrames / SampleClips with augment=: `frames_u8` is the uint8 output of the stage in front
     ([N,T,S,S,3] or a lower rank, one clip), the result the requested output of the call."""
@@ -1463,6 +1568,363 @@ def _apply_augment(augment, frames_u8, out, dtype, norm, augment_params):
     if lead == 5:
         return y
     return y[0] if lead == 4 else y[0, :, 0]
+
+
+# ---------------------------------------------------------------------------------------------
+# Interpolated per-clip warps (include/ptx_amd_warp.h): the arithmetic contract in numpy, the launch, RandomAffine /
+# RandomRotation / RandomPerspective
+# ---------------------------------------------------------------------------------------------
+WARP_KINDS = ("identity", "affine", "perspective")                                  # the PTX_WARP_* codes, by index
+WARP_INTERPOLATIONS = ("nearest", "bilinear", "bicubic")                            # what Image.transform takes
+
+
+def check_warp_interpolation(interpolation, who="warp"):
+    """`check_interpolation`, then the three filters a warp can take (Image.transform's); PtxError for the other three."""
+    name = check_interpolation(interpolation, who)
+    if name not in WARP_INTERPOLATIONS:
+        raise PtxError("%s: a warp takes interpolation 'nearest', 'bilinear' or 'bicubic' (what PIL's Image.transform takes), got %r"
+                       % (who, interpolation))
+    return name
+
+
+def _warp_params(kinds, coeffs, N=None, who="warp"):
+    """(kinds [N] integers, coeffs [N, 8] numbers) -- arrays or CPU tensors -- as contiguous (int32, float64) numpy arrays, or
+    PtxError (shapes and dtypes only; the values are ptx_warp_frames_supported's to check)."""
+    arrs = []
+    for name, a, ok, shape in (("kinds", kinds, "iu", "[N]"), ("coeffs", coeffs, "fiu", "[N, %d]" % _lib.PTX_WARP_COEFFS)):
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                raise PtxError("%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
+            a = a.numpy()
+        a = np.asarray(a)
+        if a.dtype.kind not in ok:
+            raise PtxError("%s: params %s must hold %s, got dtype %s" % (who, name, "integers" if ok == "iu" else "numbers", a.dtype))
+        if a.ndim != (1 if name == "kinds" else 2) or (name == "coeffs" and a.shape[1] != _lib.PTX_WARP_COEFFS):
+            raise PtxError("%s: params %s must be %s, got shape %s" % (who, name, shape, a.shape))
+        if N is not None and a.shape[0] != N:
+            raise PtxError("%s: params %s hold %d clips, the frames hold N = %d" % (who, name, a.shape[0], N))
+        arrs.append(a)
+    if arrs[0].shape[0] != arrs[1].shape[0]:
+        raise PtxError("%s: params kinds and coeffs differ in length: %d and %d" % (who, arrs[0].shape[0], arrs[1].shape[0]))
+    if arrs[0].shape[0] == 0:
+        raise PtxError("%s: empty batch" % who)
+    k64 = arrs[0].astype(np.int64)
+    if (np.abs(k64) >= 2 ** 31).any():
+        raise PtxError("%s: params kinds must be PTX_WARP_* codes 0..2" % who)
+    return np.ascontiguousarray(k64.astype(np.int32)), np.ascontiguousarray(arrs[1].astype(np.float64))
+
+
+def _warp_supported(kinds, coeffs, H, W, fill, interpolation, who="warp"):
+    """ptx_warp_frames_supported on host kinds [N] and coeffs [N, 8]: the contiguous (int32, float64) arrays, or PtxError with
+    the library's reason."""
+    kinds, coeffs = _warp_params(kinds, coeffs, None, who)
+    desc = _lib.WarpDesc(kinds.shape[0], 1, int(H), int(W), INTERPOLATIONS.index(interpolation), fill[0], fill[1], fill[2], 0)
+    if not _lib.lib().ptx_warp_frames_supported(C.byref(desc), C.c_void_p(kinds.ctypes.data), C.c_void_p(coeffs.ctypes.data)):
+        raise PtxError("%s: %s" % (who, _lib.lib().ptx_last_error().decode(errors="replace")))
+    return kinds, coeffs
+
+
+def _warp_clip_numpy(clip, kind, a, interpolation, fill):
+    """One clip, uint8 [T, H, W, 3]: include/ptx_amd_warp.h's arithmetic, operation for operation (numpy's float64 is IEEE and
+    numpy does not contract)."""
+    T, H, W, _ = clip.shape
+    if kind == _lib.PTX_WARP_IDENTITY:
+        return clip.copy()
+    X, Y = np.arange(W, dtype=np.float64)[None, :] + 0.5, np.arange(H, dtype=np.float64)[:, None] + 0.5
+    with np.errstate(all="ignore"):
+        xin, yin = a[0] * X + a[1] * Y + a[2], a[3] * X + a[4] * Y + a[5]
+        if kind == _lib.PTX_WARP_PERSPECTIVE:
+            den = a[6] * X + a[7] * Y + 1.0
+            xin, yin = xin / den, yin / den
+        inside = (xin >= 0.0) & (xin < W) & (yin >= 0.0) & (yin < H)
+    xin, yin = np.where(inside, xin, 0.0), np.where(inside, yin, 0.0)
+    out = np.empty_like(clip)
+    out[...] = np.asarray(fill, np.uint8)
+    if interpolation == "nearest":                       # xin >= 0 here, so PIL's COORD is the truncation
+        out[:, inside] = clip[:, yin.astype(np.int64)[inside], xin.astype(np.int64)[inside]]
+        return out
+    xin, yin = xin - 0.5, yin - 0.5
+    xi, yi = np.floor(xin), np.floor(yin)
+    dx, dy = (xin - xi)[None, :, :, None], (yin - yi)[None, :, :, None]
+    xi, yi = xi.astype(np.int64), yi.astype(np.int64)
+    src = clip.astype(np.float64)                        # bytes and their small integer sums are exact in float64
+    cx = lambda i: np.clip(i, 0, W - 1)
+    if interpolation == "bilinear":
+        x0, x1 = cx(xi), cx(xi + 1)
+
+        def row(r):
+            return src[:, r, x0] + (src[:, r, x1] - src[:, r, x0]) * dx
+
+        v1 = row(np.clip(yi, 0, H - 1))
+        ok = ((yi + 1 >= 0) & (yi + 1 < H))[None, :, :, None]
+        v2 = np.where(ok, row(np.clip(yi + 1, 0, H - 1)), v1)
+        val = np.trunc(v1 + (v2 - v1) * dy)
+    else:
+        xi, yi = xi - 1, yi - 1
+        xs = [cx(xi + j) for j in range(4)]
+
+        def cub(v1, v2, v3, v4, d):
+            p1, p2, p3, p4 = v2, -v1 + v3, 2 * (v1 - v2) + v3 - v4, -v1 + v2 - v3 + v4
+            return p1 + d * (p2 + d * (p3 + d * p4))
+
+        def row(r):
+            return cub(src[:, r, xs[0]], src[:, r, xs[1]], src[:, r, xs[2]], src[:, r, xs[3]], dx)
+
+        r = [row(np.clip(yi, 0, H - 1))]
+        for k in (1, 2, 3):
+            ok = ((yi + k >= 0) & (yi + k < H))[None, :, :, None]
+            r.append(np.where(ok, row(np.clip(yi + k, 0, H - 1)), r[-1]))
+        v = cub(r[0], r[1], r[2], r[3], dy)
+        val = np.where(v <= 0.0, 0.0, np.where(v >= 255.0, 255.0, np.trunc(v)))
+    out[:, inside] = val.astype(np.uint8)[:, inside]
+    return out
+
+
+def warp_numpy(frames, kinds, coeffs, interpolation="bilinear", fill=0):
+    """The warp kernel's arithmetic in numpy: uint8 frames [N,T,H,W,3], kinds [N] (PTX_WARP_* codes, `WARP_KINDS` by index) and
+    coeffs float64 [N, 8] (a0 .. a7 of Image.transform's AFFINE -- a6, a7 unused -- or PERSPECTIVE data) -> uint8 [N,T,H,W,3],
+    as include/ptx_amd_warp.h states it.  A nearest affine clip is refused, as the kernel refuses it (PIL walks it in fixed
+    point: `affine_fixed`).  The host-side model the tests compare with Pillow; not a fallback (nothing on the device path calls
+    it)."""
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[-1] != 3:
+        raise PtxError("warp_numpy: frames must be uint8 [N,T,H,W,3], got %s %s" % (frames.dtype, frames.shape))
+    fill = _randaug_fill(fill, "warp_numpy")
+    interpolation = check_warp_interpolation(interpolation, "warp_numpy")
+    N, T, H, W, _ = frames.shape
+    kinds, coeffs = _warp_params(kinds, coeffs, N, "warp_numpy")
+    kinds, coeffs = _warp_supported(kinds, coeffs, H, W, fill, interpolation, "warp_numpy")
+    return np.stack([_warp_clip_numpy(frames[n], int(kinds[n]), [float(v) for v in coeffs[n]], interpolation, fill) for n in range(N)])
+
+
+def _warp_launch(src, dst, kinds, coeffs, interpolation, fill, stream):
+    """ptx_warp_frames on contiguous uint8 CUDA frames src -> dst [N,T,H,W,3] with checked host kinds and coeffs."""
+    N, T, H, W, _ = src.shape
+    dev_kinds = torch.from_numpy(kinds).to(src.device)
+    dev_coeffs = torch.from_numpy(coeffs.reshape(-1)).to(src.device)
+    desc = _lib.WarpDesc(N, T, H, W, INTERPOLATIONS.index(interpolation), fill[0], fill[1], fill[2], 0)
+    check(_lib.lib().ptx_warp_frames(C.byref(desc), C.c_void_p(src.data_ptr()), C.c_void_p(dev_kinds.data_ptr()),
+                                     C.c_void_p(dev_coeffs.data_ptr()), C.c_void_p(dst.data_ptr()), stream), "ptx_warp_frames")
+
+
+def _uniform(lo, hi, generator):
+    return float(torch.empty(1).uniform_(float(lo), float(hi), generator=generator).item())
+
+
+def _warp_range(value, name, who, lengths=(2,), nonneg=False, number=True):
+    """A number d (the range -d .. d; only with `number`) or a sequence of one of `lengths` numbers, as a tuple of floats."""
+    if number and isinstance(value, (int, float)) and not isinstance(value, bool):
+        if value < 0:
+            raise PtxError("%s: a single %s must not be negative, got %r" % (who, name, value))
+        return (-float(value), float(value))
+    try:
+        vals = tuple(float(v) for v in value)
+    except (TypeError, ValueError):
+        vals = ()
+    if len(vals) not in lengths or not all(math.isfinite(v) for v in vals):
+        raise PtxError("%s: %s must be %sa sequence of %s finite numbers, got %r" % (who, name, "a number or " if number else "",
+                                                                                 " or ".join(map(str, lengths)), value))
+    if nonneg and any(v <= 0 for v in vals):
+        raise PtxError("%s: %s values must be positive, got %r" % (who, name, value))
+    return vals
+
+
+class _ClipWarp:
+    """What RandomAffine, RandomRotation and RandomPerspective share: one draw per CLIP as (kinds CPU int32 [N], coeffs CPU
+    float64 [N, 8]) -- `WARP_KINDS` codes and the a0 .. a7 that Image.transform takes --, kept as `last_params` and replayed
+    with `params=`; the call on uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3], which returns uint8 frames of the same
+    shape in one launch (`last_launches`): ptx_warp_frames ("warp"), or, for nearest affine clips, one position of
+    ptx_rand_augment_apply ("apply") with `affine_fixed`'s rotate-coded row, PIL's own fixed-point walk."""
+
+    def _init_warp(self, interpolation, fill, generator):
+        who = type(self).__name__
+        self.interpolation = check_warp_interpolation(interpolation, who)
+        self.fill = _randaug_fill(fill, who)
+        if generator is not None and not isinstance(generator, torch.Generator):
+            raise PtxError("%s: generator must be a torch.Generator or None, got %r" % (who, generator))
+        self.generator, self.last_params, self.last_launches = generator, None, ()
+
+    def check_params(self, params, N=None, H=None, W=None):
+        """`params` as (CPU int32 [N], CPU float64 [N, 8]) tensors, or PtxError: shapes, N; with H and W also the library's own
+        check of the kinds and coefficients for frames of that size.  No device is touched."""
+        who = type(self).__name__
+        try:
+            kinds, coeffs = params
+        except (TypeError, ValueError):
+            raise PtxError("%s: params must be a pair (kinds [N], coeffs [N, 8]), got %r" % (who, type(params).__name__))
+        kinds, coeffs = _warp_params(kinds, coeffs, N, who)
+        if H is not None and W is not None:
+            self._plan(kinds, coeffs, int(H), int(W))
+        return torch.from_numpy(kinds), torch.from_numpy(coeffs)
+
+    def _plan(self, kinds, coeffs, H, W):
+        """("apply", rows [N, 1, 8]) for nearest affine clips, else ("warp", kinds, coeffs); checked by the library."""
+        who = type(self).__name__
+        if self.interpolation == "nearest" and (kinds == _lib.PTX_WARP_AFFINE).any():
+            if not np.isin(kinds, (_lib.PTX_WARP_IDENTITY, _lib.PTX_WARP_AFFINE)).all():
+                raise PtxError("%s: nearest affine clips run PIL's fixed-point walk and cannot share a launch with another kind" % who)
+            rows = np.zeros((kinds.shape[0], 1, _lib.PTX_RANDAUG_ROW), np.int32)
+            for n in np.nonzero(kinds == _lib.PTX_WARP_AFFINE)[0]:
+                if not np.isfinite(coeffs[n, :6]).all():
+                    raise PtxError("%s: clip %d: a coefficient is not finite" % (who, n))
+                rows[n, 0, 0] = _lib.PTX_RANDAUG_ROTATE
+                rows[n, 0, 1:7] = affine_fixed([float(v) for v in coeffs[n, :6]], H, W, who)
+            return ("apply", _randaug_supported(rows, H, W, self.fill, who))
+        return ("warp",) + _warp_supported(kinds, coeffs, H, W, self.fill, self.interpolation, who)
+
+    def __call__(self, frames, params=None):
+        who = type(self).__name__
+        if not isinstance(frames, torch.Tensor):
+            raise PtxError("%s: frames must be a uint8 CUDA tensor, got %s" % (who, type(frames).__name__))
+        if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
+            raise PtxError("%s: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (who, tuple(frames.shape)))
+        N = frames.shape[0] if frames.dim() == 5 else 1
+        H, W = int(frames.shape[-3]), int(frames.shape[-2])
+        if frames.numel() == 0:
+            raise PtxError("%s: empty batch" % who)
+        if params is not None:                                       # validated before a device is touched
+            params = self.check_params(params, N, H, W)
+        if not frames.is_cuda or frames.dtype != torch.uint8:
+            raise PtxError("%s: frames must be a uint8 CUDA tensor (no CPU fallback)" % who)
+        if params is None:
+            params = self.last_params = self.draw(N, H, W)
+        plan = self._plan(params[0].numpy(), params[1].numpy(), H, W)
+        f5 = frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
+        with torch.cuda.device(f5.device):
+            y = torch.empty_like(f5)
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if plan[0] == "warp":
+                _warp_launch(f5, y, plan[1], plan[2], self.interpolation, self.fill, stream)
+            else:
+                dev_rows = torch.from_numpy(plan[1].reshape(-1)).to(f5.device)
+                desc = _lib.RandAugDesc(N, f5.shape[1], H, W, _lib.PTX_RESIZE_OUT_U8, 1, 0, 0, self.fill[0], self.fill[1], self.fill[2], 0)
+                check(_lib.lib().ptx_rand_augment_apply(C.byref(desc), C.c_void_p(f5.data_ptr()), C.c_void_p(dev_rows.data_ptr()), None,
+                                                        C.c_void_p(y.data_ptr()), None, stream), "ptx_rand_augment_apply")
+        self.last_launches = (plan[0],)
+        return y.view(frames.shape)
+
+    @staticmethod
+    def _pack(rows):
+        """[(kind, coefficients)] per clip -> (kinds CPU int32 [N], coeffs CPU float64 [N, 8])."""
+        kinds = torch.tensor([k for k, _ in rows], dtype=torch.int32)
+        coeffs = torch.zeros((len(rows), _lib.PTX_WARP_COEFFS), dtype=torch.float64)
+        for n, (_, a) in enumerate(rows):
+            coeffs[n, :len(a)] = torch.tensor([float(v) for v in a], dtype=torch.float64)
+        return kinds, coeffs
+
+
+class RandomAffine(_ClipWarp):
+    """torchvision's RandomAffine on decoded uint8 frames on the device, one draw per CLIP, equal to its PIL-image code path
+    (Image.transform(AFFINE) with the interpolation) bit for bit on the drawn coefficients.  degrees: a number d (-d .. d) or a
+    pair; translate: None or a pair of fractions in 0..1 of the width and the height; scale: None or a (lo, hi) pair of positive
+    numbers; shear: None, a number s (x shear -s .. s), a pair (x) or four numbers (x, then y); center: None (the image centre,
+    (W * 0.5, H * 0.5)) or (cx, cy); fill and generator as RandAugment's.
+
+    THE DRAW (the contract: torchvision's RandomAffine.get_params order), per clip from `generator`, each a
+    torch.empty(1).uniform_(lo, hi): the angle; if translate, tx then ty, each int(round(.)) of a draw in -max .. max with max_dx
+    = translate[0] * W, max_dy = translate[1] * H; if scale, the scale; if shear, the x shear, then (four numbers only) the y
+    shear.  The coefficients are `_inverse_affine_matrix(center, angle, (tx, ty), (shear_x, shear_y), scale)`."""
+
+    def __init__(self, degrees, translate=None, scale=None, shear=None, interpolation="nearest", fill=0, center=None, generator=None):
+        who = "RandomAffine"
+        self._init_warp(interpolation, fill, generator)
+        self.degrees = _warp_range(degrees, "degrees", who)
+        self.translate = None if translate is None else _warp_range(translate, "translate", who, number=False)
+        if self.translate is not None and not all(0.0 <= v <= 1.0 for v in self.translate):
+            raise PtxError("%s: translate values must be between 0 and 1, got %r" % (who, translate))
+        self.scale = None if scale is None else _warp_range(scale, "scale", who, nonneg=True, number=False)
+        self.shear = None if shear is None else _warp_range(shear, "shear", who, lengths=(2, 4))
+        self.center = None if center is None else _warp_range(center, "center", who, number=False)
+
+    def draw(self, n, H, W):
+        g, rows = self.generator, []
+        for _ in range(int(n)):
+            angle = _uniform(self.degrees[0], self.degrees[1], g)
+            tx = ty = 0
+            if self.translate is not None:
+                max_dx, max_dy = float(self.translate[0] * W), float(self.translate[1] * H)
+                tx = int(round(_uniform(-max_dx, max_dx, g)))
+                ty = int(round(_uniform(-max_dy, max_dy, g)))
+            scale = _uniform(self.scale[0], self.scale[1], g) if self.scale is not None else 1.0
+            sx = sy = 0.0
+            if self.shear is not None:
+                sx = _uniform(self.shear[0], self.shear[1], g)
+                if len(self.shear) == 4:
+                    sy = _uniform(self.shear[2], self.shear[3], g)
+            center = (W * 0.5, H * 0.5) if self.center is None else self.center
+            rows.append((_lib.PTX_WARP_AFFINE, _inverse_affine_matrix(center, angle, (tx, ty), (sx, sy), scale)))
+        return self._pack(rows)
+
+
+class RandomRotation(_ClipWarp):
+    """torchvision's RandomRotation on decoded uint8 frames on the device, one draw per CLIP, equal to its PIL-image code path
+    (Image.rotate(angle, interpolation, center=.., fillcolor=..)) bit for bit on the drawn coefficients.  degrees: a number d
+    (-d .. d) or a pair; center: None (PIL's (W / 2, H / 2)) or (cx, cy); expand=True is not offered: the clips of a batch would
+    differ in size.
+
+    THE DRAW (the contract), per clip from `generator`: the angle, one torch.empty(1).uniform_(lo, hi).  The coefficients are
+    `rotation_matrix(angle, H, W, center)`: Image.rotate's own matrix, its sine and cosine rounded to 15 decimals."""
+
+    def __init__(self, degrees, interpolation="nearest", center=None, fill=0, generator=None, expand=False):
+        who = "RandomRotation"
+        if expand:
+            raise PtxError("%s: expand=True is not offered: the clips of a batch would differ in size" % who)
+        self._init_warp(interpolation, fill, generator)
+        self.degrees = _warp_range(degrees, "degrees", who)
+        self.center = None if center is None else _warp_range(center, "center", who, number=False)
+
+    def draw(self, n, H, W):
+        return self._pack([(_lib.PTX_WARP_AFFINE, rotation_matrix(_uniform(self.degrees[0], self.degrees[1], self.generator), H, W, self.center))
+                           for _ in range(int(n))])
+
+
+def perspective_coefficients(startpoints, endpoints):
+    """torchvision's _get_perspective_coeffs (0.15 and later): the eight coefficients that map the four `endpoints` to the four
+    `startpoints`, from the 8 x 8 least-squares system in float64 (torch.linalg.lstsq, driver gels), rounded to float32 and
+    widened to Python floats."""
+    a = torch.zeros(8, 8, dtype=torch.float64)
+    for i, (p1, p2) in enumerate(zip(endpoints, startpoints)):
+        a[2 * i, :] = torch.tensor([p1[0], p1[1], 1, 0, 0, 0, -p2[0] * p1[0], -p2[0] * p1[1]], dtype=torch.float64)
+        a[2 * i + 1, :] = torch.tensor([0, 0, 0, p1[0], p1[1], 1, -p2[1] * p1[0], -p2[1] * p1[1]], dtype=torch.float64)
+    b = torch.tensor(startpoints, dtype=torch.float64).view(8)
+    return torch.linalg.lstsq(a, b, driver="gels").solution.to(torch.float32).tolist()
+
+
+class RandomPerspective(_ClipWarp):
+    """torchvision's RandomPerspective on decoded uint8 frames on the device, one draw per CLIP, equal to its PIL-image code path
+    (Image.transform(PERSPECTIVE) with the interpolation) bit for bit on the drawn coefficients.  distortion_scale: 0..1; p: the
+    probability that a clip is warped (the others are copied).
+
+    THE DRAW (the contract: torchvision's forward and get_params order), per clip from `generator`: torch.rand(1) < p; only
+    then eight torch.randint(lo, hi, (1,)) -- top-left x, y, top-right x, y, bottom-right x, y, bottom-left x, y -- with hw =
+    int(distortion_scale * (W // 2)), hh = int(distortion_scale * (H // 2)): a left x in 0 .. hw, a right x in W - hw - 1 .. W -
+    1, a top y in 0 .. hh, a bottom y in H - hh - 1 .. H - 1.  The coefficients are `perspective_coefficients` of the frame's
+    corners [0, 0], [W - 1, 0], [W - 1, H - 1], [0, H - 1] and the drawn ones.  A degenerate quadrilateral, whose denominator
+    vanishes inside the frame, raises PtxError."""
+
+    def __init__(self, distortion_scale=0.5, p=0.5, interpolation="bilinear", fill=0, generator=None):
+        who = "RandomPerspective"
+        self._init_warp(interpolation, fill, generator)
+        for name, v in (("distortion_scale", distortion_scale), ("p", p)):
+            if not isinstance(v, (int, float)) or isinstance(v, bool) or not 0.0 <= v <= 1.0:
+                raise PtxError("%s: %s must be a number in 0..1, got %r" % (who, name, v))
+        self.distortion_scale, self.p = float(distortion_scale), float(p)
+
+    def draw(self, n, H, W):
+        g, rows = self.generator, []
+        ri = lambda lo, hi: int(torch.randint(lo, hi, (1,), generator=g).item())
+        hw, hh = int(self.distortion_scale * (W // 2)), int(self.distortion_scale * (H // 2))
+        for _ in range(int(n)):
+            if not bool(torch.rand(1, generator=g) < self.p):
+                rows.append((_lib.PTX_WARP_IDENTITY, []))
+                continue
+            topleft = [ri(0, hw + 1), ri(0, hh + 1)]
+            topright = [ri(W - hw - 1, W), ri(0, hh + 1)]
+            botright = [ri(W - hw - 1, W), ri(H - hh - 1, H)]
+            botleft = [ri(0, hw + 1), ri(H - hh - 1, H)]
+            start = [[0, 0], [W - 1, 0], [W - 1, H - 1], [0, H - 1]]
+            rows.append((_lib.PTX_WARP_PERSPECTIVE, perspective_coefficients(start, [topleft, topright, botright, botleft])))
+        return self._pack(rows)
 
 
 # ---------------------------------------------------------------------------------------------
