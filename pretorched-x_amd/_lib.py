@@ -23,6 +23,7 @@ NL_KS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_nl_
 LINEAR_BF16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_linear_bf16.h")  # Linear layers with bf16 weights
 BN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_bn.h")            # batch-statistics BatchNorm (update_bn)
 WARP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_warp.h")        # interpolated affine / perspective warps
+BLUR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_blur.h")        # GaussianBlur on uint8 frames
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -208,6 +209,14 @@ class WarpDesc(C.Structure):
 
 PTX_WARP_IDENTITY, PTX_WARP_AFFINE, PTX_WARP_PERSPECTIVE = range(3)
 PTX_WARP_COEFFS = 8
+
+
+class BlurDesc(C.Structure):
+    """ptx_blur_desc (ptx_amd_blur.h): the frames of a GaussianBlur launch, the tap counts of its two passes, its output mode."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "H", "W", "kx", "ky", "out_mode")]
+
+
+PTX_BLUR_MAX_TAPS = 33
 
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
@@ -503,6 +512,14 @@ SIGNATURES_WARP = {
 }
 
 
+# include/ptx_amd_blur.h: per-clip GaussianBlur of uint8 frames (csrc/blur_frames.h), bound the same way
+# (tests/test_blur_frames_host.py)
+SIGNATURES_BLUR = {
+    "ptx_gaussian_blur_supported": (C.c_int, [C.POINTER(BlurDesc), _P, _P, _P]),
+    "ptx_gaussian_blur_frames": (C.c_int, [C.POINTER(BlurDesc), _P, _P, _P, _P, _P, C.POINTER(NormDesc), _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -540,7 +557,7 @@ def lib():
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
                 list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()) + \
                 list(SIGNATURES_NL_KS.items()) + list(SIGNATURES_LINEAR_BF16.items()) + list(SIGNATURES_BN.items()) + \
-                list(SIGNATURES_WARP.items()):
+                list(SIGNATURES_WARP.items()) + list(SIGNATURES_BLUR.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

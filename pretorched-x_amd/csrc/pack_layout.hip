@@ -1447,3 +1447,7 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 // So are the interpolated per-clip warps (include/ptx_amd_warp.h): affine and perspective transforms of uint8 frames with
 // Pillow's bilinear / bicubic interpolation in fp64, one launch per batch.
 #include "warp_frames.h"
+
+// So is the per-clip GaussianBlur (include/ptx_amd_blur.h): a separable fp64 blur with reflect padding over LDS tiles, one launch
+// per batch, whose plane output is ptx_frames_u8_to_ncdhw's value of the blurred byte.
+#include "blur_frames.h"

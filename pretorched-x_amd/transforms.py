@@ -51,6 +51,11 @@ uint8 frames:
   writes the NCDHW clip once, equal bit for bit to `batch_mix_torch`, the torch statement of the contract.  As
   `TransformFrames(.., mix=bm)` / `SampleClips(.., mix=bm)` it is the last stage; `bm.targets` gives the soft targets.
 
+* `GaussianBlur` is torchvision's GaussianBlur (inside RandomApply with `p=`) on uint8 frames, one draw per clip: a separable
+  float64 blur with reflect padding whose result is a pure function of the bytes and the fp32 weights (`gaussian_blur_numpy` is
+  the numpy statement of the contract, `gaussian_kernel1d` torchvision's weights).  As `TransformFrames(.., blur=gb)` /
+  `SampleClips(.., blur=gb)` it runs behind `color=` and in front of `augment=` / `mix=`, the view recipes' order.
+
 Image loading and video decoding stay host work and are not on this path.
 """
 import collections
@@ -1065,6 +1070,301 @@ def _check_color(color, who):
     if color is not None and not isinstance(color, ColorJitter):
         raise PtxError("%s: color must be a pretorched.transforms.ColorJitter or None, got %r" % (who, color))
     return color
+
+
+# ---------------------------------------------------------------------------------------------
+# GaussianBlur per clip (include/ptx_amd_blur.h): torchvision's weights, the arithmetic contract in numpy, the draw, the launch
+# ---------------------------------------------------------------------------------------------
+BLUR_MAX_TAPS = _lib.PTX_BLUR_MAX_TAPS
+
+
+def _blur_kernel_size(kernel_size, who="GaussianBlur"):
+    """(kx, ky) of `kernel_size` (an int or a pair (kx, ky), torchvision's order): odd, 1 .. PTX_BLUR_MAX_TAPS."""
+    ks = (kernel_size, kernel_size) if isinstance(kernel_size, int) and not isinstance(kernel_size, bool) else kernel_size
+    try:
+        ks = tuple(ks)
+        ok = len(ks) == 2 and all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in ks)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise PtxError("%s: kernel_size must be an int or a pair (kx, ky) of ints, got %r" % (who, kernel_size))
+    for k in ks:
+        if k < 1 or k % 2 == 0 or k > BLUR_MAX_TAPS:
+            raise PtxError("%s: kernel_size=%r: every size must be odd and 1 .. %d (PTX_BLUR_MAX_TAPS)" % (who, kernel_size, BLUR_MAX_TAPS))
+    return int(ks[0]), int(ks[1])
+
+
+def gaussian_kernel1d(k, sigma):
+    """torchvision's `_get_gaussian_kernel1d(k, sigma)` in float32, with the same torch CPU ops and therefore the same bits: a
+    CPU float32 tensor [k].  k: odd, >= 1; sigma > 0."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k % 2 == 0:
+        raise PtxError("gaussian_kernel1d: k must be an odd integer >= 1, got %r" % (k,))
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.floating)) or not (sigma > 0) or not math.isfinite(sigma):
+        raise PtxError("gaussian_kernel1d: sigma must be a finite number > 0, got %r" % (sigma,))
+    sigma = float(sigma)
+    half = (int(k) - 1) * 0.5
+    x = torch.linspace(-half, half, steps=int(k), dtype=torch.float32)
+    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
+    return pdf / pdf.sum()
+
+
+def _blur_reflect(i, n):
+    """torch's "reflect" padding index for i in (-n, 2 n - 1)."""
+    i = np.where(i < 0, -i, i)
+    return np.where(i >= n, 2 * (n - 1) - i, i)
+
+
+def _blur_rows(apply, wx, wy, N, who):
+    """(apply int32 [N], wx float32 [N, kx], wy float32 [N, ky]) as contiguous numpy arrays; a 1-D weight row serves every clip."""
+    arrs = []
+    for name, a in (("apply", apply), ("wx", wx), ("wy", wy)):
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                raise PtxError("%s: %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
+            a = a.numpy()
+        arrs.append(np.asarray(a))
+    ap, wx, wy = arrs
+    if ap.dtype.kind not in "iub" or ap.ndim != 1 or ap.shape[0] != N:
+        raise PtxError("%s: apply must hold N = %d integer flags, got dtype %s shape %s" % (who, N, ap.dtype, ap.shape))
+    out = [np.ascontiguousarray(ap.astype(np.int32))]
+    for name, w in (("wx", wx), ("wy", wy)):
+        if w.dtype.kind != "f":
+            raise PtxError("%s: %s must hold floats, got dtype %s" % (who, name, w.dtype))
+        if w.ndim == 1:
+            w = np.broadcast_to(w, (N, w.shape[0]))
+        if w.ndim != 2 or w.shape[0] != N or w.shape[1] < 1:
+            raise PtxError("%s: %s must be [N, k] or [k] with N = %d, got shape %s" % (who, name, N, w.shape))
+        w32 = np.ascontiguousarray(w.astype(np.float32))
+        if not np.array_equal(w32.astype(w.dtype), w, equal_nan=True):
+            raise PtxError("%s: %s must hold float32 values (the device reads fp32 weights)" % (who, name))
+        out.append(w32)
+    return tuple(out)
+
+
+def _blur_supported(apply, wx, wy, H, W, who, mode=_lib.PTX_RESIZE_OUT_U8, T=1):
+    """The library's host-side check of a launch (no device is touched), with its reason as a PtxError; the reflect condition is
+    named in the caller's terms first."""
+    kx, ky = wx.shape[1], wy.shape[1]
+    if kx // 2 >= W or ky // 2 >= H:
+        raise PtxError("%s: kernel_size=(%d, %d) does not fit frames of H=%d, W=%d: reflect padding needs kx // 2 < W and "
+                       "ky // 2 < H (torch raises there too)" % (who, kx, ky, H, W))
+    desc = _lib.BlurDesc(apply.shape[0], T, H, W, kx, ky, mode)
+    if not _lib.lib().ptx_gaussian_blur_supported(C.byref(desc), C.c_void_p(apply.ctypes.data), C.c_void_p(wx.ctypes.data),
+                                                  C.c_void_p(wy.ctypes.data)):
+        raise PtxError("%s: %s" % (who, _lib.lib().ptx_last_error().decode(errors="replace")))
+
+
+def gaussian_blur_numpy(frames, apply, wx, wy, return_real=False):
+    """The kernel's arithmetic in numpy: uint8 frames [N,T,H,W,3], flags [N], float32 weights wx [N, kx] and wy [N, ky] (a 1-D row
+    serves every clip) -> uint8 [N,T,H,W,3].  Per frame and channel, in float64, the taps in ascending order from 0.0, every
+    product and every add rounded on its own: the horizontal pass h = sum_j wx[j] * p[y][refl(x + j - kx // 2)], the vertical
+    pass v = sum_i wy[i] * h[refl(y + i - ky // 2)][x], out = clip(round_half_to_even(v), 0, 255); a clip whose flag is 0 is
+    copied.  return_real=True returns (out, v) with v float64 (the bytes themselves for a copied clip).  The host-side model
+    the tests compare the device with; not a fallback (GaussianBlur never calls it)."""
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[-1] != 3:
+        raise PtxError("gaussian_blur_numpy: frames must be uint8 [N,T,H,W,3], got %s %s" % (frames.dtype, frames.shape))
+    N, T, H, W, _ = frames.shape
+    if frames.size == 0:
+        raise PtxError("gaussian_blur_numpy: empty batch")
+    apply, wx, wy = _blur_rows(apply, wx, wy, N, "gaussian_blur_numpy")
+    _blur_supported(apply, wx, wy, H, W, "gaussian_blur_numpy")
+    kx, ky = wx.shape[1], wy.shape[1]
+    xi = _blur_reflect(np.arange(W)[None, :] + np.arange(kx)[:, None] - kx // 2, W)           # [kx, W]
+    yi = _blur_reflect(np.arange(H)[None, :] + np.arange(ky)[:, None] - ky // 2, H)           # [ky, H]
+    out = np.empty_like(frames)
+    real = np.empty(frames.shape, np.float64) if return_real else None
+    for n in range(N):
+        p = frames[n].astype(np.float64)
+        if apply[n]:
+            h = np.zeros_like(p)
+            for j in range(kx):
+                h = h + np.float64(wx[n, j]) * p[:, :, xi[j], :]
+            v = np.zeros_like(p)
+            for i in range(ky):
+                v = v + np.float64(wy[n, i]) * h[:, yi[i], :, :]
+            out[n] = np.clip(np.rint(v), 0.0, 255.0).astype(np.uint8)
+        else:
+            v = p
+            out[n] = frames[n]
+        if return_real:
+            real[n] = v
+    return (out, real) if return_real else out
+
+
+class GaussianBlur:
+    """torchvision's GaussianBlur (inside RandomApply when `p` is given) on decoded uint8 frames on the device, one draw per CLIP:
+    the blur of the SimCLR / MoCo / BYOL view recipes and their video forms.  include/ptx_amd_blur.h states the arithmetic (a
+    separable float64 blur with reflect padding, rounded half to even), `gaussian_blur_numpy` restates it; it is torchvision's
+    result up to one level where the real value lies within fp32 summation error of a tie.
+
+    kernel_size: an odd int or a pair (kx, ky), each 1 .. 33; sigma: a number > 0 or a range (lo, hi) with 0 < lo <= hi, one
+    value per clip for both axes; p: None (every clip is blurred) or the probability of RandomApply; generator: a CPU
+    torch.Generator (None: torch's default one).
+
+    `gb(frames)` blurs uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3] (one draw per clip: N, or one) and keeps the draw as
+    `last_params` = (apply CPU int32 [N], sigma CPU float64 [N]; 0.0 where a clip is not blurred).  `gb(frames, params=p)`
+    applies a given draw.  A call is one small upload (flags and weights) and one launch."""
+
+    def __init__(self, kernel_size, sigma=(0.1, 2.0), p=None, generator=None):
+        self.kernel_size = _blur_kernel_size(kernel_size)
+        if isinstance(sigma, bool):
+            raise PtxError("GaussianBlur: sigma must be a number > 0 or a range (lo, hi), got %r" % (sigma,))
+        if isinstance(sigma, (int, float)):
+            lo = hi = float(sigma)
+            self.sigma_range = None
+        else:
+            try:
+                lo, hi = (float(v) for v in sigma)
+            except (TypeError, ValueError):
+                raise PtxError("GaussianBlur: sigma must be a number > 0 or a range (lo, hi), got %r" % (sigma,))
+            self.sigma_range = (lo, hi)
+        if not (0.0 < lo <= hi) or not math.isfinite(hi):
+            raise PtxError("GaussianBlur: sigma=%r: values must be finite, > 0 and ordered" % (sigma,))
+        self.sigma = (lo, hi)
+        if p is not None and (isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0):
+            raise PtxError("GaussianBlur: p must be None or a probability in [0, 1], got %r" % (p,))
+        self.p = None if p is None else float(p)
+        if generator is not None and not isinstance(generator, torch.Generator):
+            raise PtxError("GaussianBlur: generator must be a torch.Generator or None, got %r" % (generator,))
+        self.generator, self.last_params = generator, None
+
+    def draw(self, n):
+        """The draw of n clips: (apply CPU int32 [n], sigma CPU float64 [n]).  Per clip, in clip order, from `generator`: with p
+        given, u = torch.rand(1) and the clip is blurred iff u <= p (torchvision's RandomApply skips when p < u); only a blurred
+        clip draws a sigma, torch.empty(1).uniform_(lo, hi).item() (torchvision's GaussianBlur.get_params), when sigma is a
+        range.  p=None and a scalar sigma consume nothing.  A clip that is not blurred has sigma 0.0."""
+        g = self.generator
+        apply = torch.ones(int(n), dtype=torch.int32)
+        sigma = torch.zeros(int(n), dtype=torch.float64)
+        for i in range(int(n)):
+            if self.p is not None and not bool(torch.rand(1, generator=g) <= self.p):
+                apply[i] = 0
+                continue
+            if self.sigma_range is None:
+                sigma[i] = self.sigma[0]
+            else:
+                sigma[i] = torch.empty(1).uniform_(self.sigma[0], self.sigma[1], generator=g).item()
+        return apply, sigma
+
+    def weights(self, params):
+        """(wx CPU float32 [N, kx], wy CPU float32 [N, ky]) of a checked draw: `gaussian_kernel1d` per blurred clip, the one-hot
+        centre row for a clip that is not blurred (the launch does not read it)."""
+        apply, sigma = params
+        kx, ky = self.kernel_size
+        wx, wy = torch.zeros((len(apply), kx), dtype=torch.float32), torch.zeros((len(apply), ky), dtype=torch.float32)
+        wx[:, kx // 2], wy[:, ky // 2] = 1.0, 1.0
+        for i in range(len(apply)):
+            if int(apply[i]):
+                wx[i], wy[i] = gaussian_kernel1d(kx, float(sigma[i])), gaussian_kernel1d(ky, float(sigma[i]))
+        return wx, wy
+
+    def check_params(self, params, N=None, H=None, W=None):
+        """`params` = (apply [N] integers, sigma [N] numbers) -- arrays or CPU tensors -- as (CPU int32, CPU float64) tensors, or
+        PtxError: N does not match, a flag is not 0 or 1, the sigma of a blurred clip is not finite and > 0, and, with H and W
+        given, a kernel_size that reflect padding cannot serve on H x W frames.  No device is touched."""
+        try:
+            apply, sigma = params
+        except (TypeError, ValueError):
+            raise PtxError("GaussianBlur: params must be a pair (apply [N], sigma [N]), got %r" % (params,))
+        arrs = []
+        for name, a in (("apply", apply), ("sigma", sigma)):
+            if isinstance(a, torch.Tensor):
+                if a.is_cuda:
+                    raise PtxError("GaussianBlur: params: %s must be an array or a CPU tensor, got a CUDA tensor" % name)
+                a = a.numpy()
+            arrs.append(np.asarray(a))
+        ap, sg = arrs
+        if ap.dtype.kind not in "iu" or ap.ndim != 1:
+            raise PtxError("GaussianBlur: params: apply must be [N] integers, got dtype %s shape %s" % (ap.dtype, ap.shape))
+        if sg.dtype.kind not in "fiu" or sg.shape != ap.shape:
+            raise PtxError("GaussianBlur: params: sigma must be [N] numbers like apply, got dtype %s shape %s" % (sg.dtype, sg.shape))
+        if N is not None and ap.shape[0] != N:
+            raise PtxError("GaussianBlur: params hold %d clips, the frames hold N = %d" % (ap.shape[0], N))
+        if ap.shape[0] == 0:
+            raise PtxError("GaussianBlur: params: empty batch")
+        sg = sg.astype(np.float64)
+        for i, (a, s) in enumerate(zip(ap.tolist(), sg.tolist())):
+            if a not in (0, 1):
+                raise PtxError("GaussianBlur: params[%d]: the apply flag must be 0 or 1, got %d" % (i, a))
+            if a and not (s > 0.0 and math.isfinite(s)):
+                raise PtxError("GaussianBlur: params[%d]: sigma must be finite and > 0, got %r" % (i, s))
+        out = torch.from_numpy(ap.astype(np.int32)), torch.from_numpy(np.where(ap != 0, sg, 0.0))
+        kx, ky = self.kernel_size
+        wx, wy = self.weights(out)
+        _blur_supported(out[0].numpy(), wx.numpy(), wy.numpy(), ky // 2 + 1 if H is None else int(H), kx // 2 + 1 if W is None else int(W),
+                        "GaussianBlur")
+        return out
+
+    def _params_for(self, N, H, W, params):
+        if params is None:
+            self.last_params = self.draw(N)
+            return self.check_params(self.last_params, N, H, W)
+        return self.check_params(params, N, H, W)
+
+    def _launch(self, f5, params, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+        """The launch on contiguous uint8 CUDA frames f5 [N,T,H,W,3] with checked params: uint8 [N,T,H,W,3] or the normalised
+        [N,3,T,H,W] of `dtype`."""
+        N, T, H, W, _ = f5.shape
+        kx, ky = self.kernel_size
+        wx, wy = self.weights(params)
+        with torch.cuda.device(f5.device):
+            rows = torch.cat([params[0].reshape(-1).view(torch.uint8), wx.reshape(-1).view(torch.uint8),
+                              wy.reshape(-1).view(torch.uint8)]).to(f5.device)                       # one upload
+            base = rows.data_ptr()
+            if mode == _lib.PTX_RESIZE_OUT_U8:
+                y = torch.empty((N, T, H, W, 3), device=f5.device, dtype=torch.uint8)
+            else:
+                y = torch.empty((N, 3, T, H, W), device=f5.device, dtype=dtype)
+            desc = _lib.BlurDesc(N, T, H, W, kx, ky, mode)
+            check(_lib.lib().ptx_gaussian_blur_frames(C.byref(desc), C.c_void_p(f5.data_ptr()), C.c_void_p(base),
+                                                      C.c_void_p(base + 4 * N), C.c_void_p(base + 4 * N * (1 + kx)),
+                                                      C.c_void_p(y.data_ptr()), C.byref(norm) if norm is not None else None,
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "ptx_gaussian_blur_frames")
+        return y
+
+    def __call__(self, frames, params=None):
+        if not isinstance(frames, torch.Tensor):
+            raise PtxError("GaussianBlur: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
+        if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
+            raise PtxError("GaussianBlur: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (tuple(frames.shape),))
+        N, H, W = (frames.shape[0] if frames.dim() == 5 else 1), frames.shape[-3], frames.shape[-2]
+        if frames.numel() == 0:
+            raise PtxError("GaussianBlur: empty batch")
+        kx, ky = self.kernel_size
+        if kx // 2 >= W or ky // 2 >= H:                             # before a draw and before a device is touched
+            raise PtxError("GaussianBlur: kernel_size=(%d, %d) does not fit frames of H=%d, W=%d: reflect padding needs "
+                           "kx // 2 < W and ky // 2 < H (torch raises there too)" % (kx, ky, H, W))
+        if params is not None:                                       # validated before a device is touched
+            params = self.check_params(params, N, H, W)
+        if not frames.is_cuda or frames.dtype != torch.uint8:
+            raise PtxError("GaussianBlur: frames must be a uint8 CUDA tensor (no CPU fallback)")
+        f5 = frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
+        return self._launch(f5, self._params_for(N, H, W, params)).view(frames.shape)
+
+
+def _apply_blur(blur, frames_u8, out, dtype, norm, blur_params):
+    """The blur stage of TransformFrames / SampleClips with blur=: `frames_u8` is the uint8 output of the stage in front
+    ([N,T,S,S,3] or a lower rank, one clip), the result the requested output of the call."""
+    lead = frames_u8.dim()
+    f5 = frames_u8.view((1,) * (5 - lead) + tuple(frames_u8.shape))
+    p = blur._params_for(f5.shape[0], f5.shape[2], f5.shape[3], blur_params)
+    if out == "frames":
+        return blur._launch(f5, p).view(frames_u8.shape)
+    mode = _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+    y = blur._launch(f5, p, mode, norm, dtype)
+    if lead == 5:
+        return y
+    return y[0] if lead == 4 else y[0, :, 0]
+
+
+def _check_blur(blur, size, who):
+    if blur is not None and not isinstance(blur, GaussianBlur):
+        raise PtxError("%s: blur must be a pretorched.transforms.GaussianBlur or None, got %r" % (who, blur))
+    if blur is not None and max(blur.kernel_size) // 2 >= size:
+        raise PtxError("%s: blur: kernel_size=%r does not fit the %dx%d output (H=%d, W=%d): reflect padding needs "
+                       "kernel_size // 2 < H, W" % (who, blur.kernel_size, size, size, size, size))
+    return blur
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2327,9 +2627,22 @@ def _check_mix(mix, out, who):
     return mix
 
 
-def _apply_stages(color, augment, u8, out, dtype, norm, color_params, augment_params, mix=None, mix_params=None):
-    """The stages behind the resize of TransformFrames / SampleClips: colour, then augment, then mix; the last one writes the
-    call's output."""
+def _apply_stages(color, augment, u8, out, dtype, norm, color_params, augment_params, mix=None, mix_params=None, blur=None,
+                  blur_params=None):
+    """The stages behind the resize of TransformFrames / SampleClips: colour, then blur, then augment, then mix (the recipes'
+    order); the last one writes the call's output, the ones in front of it uint8 scratch.  Every stage draws when it runs."""
+    if blur is not None:
+        stages = []
+        if color is not None:
+            stages.append(lambda u, o, d: _apply_color(color, u, o, d, norm, color_params))
+        stages.append(lambda u, o, d: _apply_blur(blur, u, o, d, norm, blur_params))
+        if augment is not None:
+            stages.append(lambda u, o, d: _apply_augment(augment, u, o, d, norm, augment_params))
+        if mix is not None:
+            stages.append(lambda u, o, d: _apply_mix(mix, u, d, norm, mix_params))
+        for stage in stages[:-1]:
+            u8 = stage(u8, "frames", torch.float32)
+        return stages[-1](u8, out, dtype)
     if mix is not None:
         if color is not None or augment is not None:
             u8 = _apply_stages(color, augment, u8, "frames", torch.float32, norm, color_params, augment_params)
@@ -2386,6 +2699,12 @@ class TransformFrames:
     same geometry, colour and augment draws with and without it) and is kept as `mix.last_params`; `tf(frames, mix_params=p)`
     applies a given draw instead.
 
+    blur: a `GaussianBlur` (None: off, the code path without it), run behind `color` and in front of `augment` and `mix`, the view
+    recipes' order (RandomResizedCrop, flip, ColorJitter, RandomGrayscale, GaussianBlur).  The stage in front writes uint8 scratch
+    and the blur launch writes the output of `out` / `dtype` when it is the last stage.  Its draw comes in execution order: after
+    the colour draw (a seed gives the same geometry and colour lists with and without it), before the augment's and the mix's;
+    it is kept as `blur.last_params`; `tf(frames, blur_params=p)` applies a given draw instead.
+
     interpolation: the resize filter, Pillow's `Image.resize(size, filter)` bit for bit: "nearest" | "box" | "bilinear" (the
     default) | "hamming" | "bicubic" | "lanczos", Pillow's integer code, or an enum of either (PIL.Image.Resampling,
     torchvision's InterpolationMode); kept as the canonical string `interpolation`.  The contract stays crop-then-resize
@@ -2397,7 +2716,7 @@ class TransformFrames:
     def __init__(self, opts, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, out="tensor",
                  dtype=torch.float32, *, random_crop=False, random_hflip=False, random_vflip=False, vflip=False,
                  generator=None, random_short_side=None, random_resized_crop=False, color=None, augment=None,
-                 interpolation="bilinear", mix=None):
+                 interpolation="bilinear", mix=None, blur=None):
         self.interpolation = check_interpolation(interpolation, "TransformFrames")
         self.color = _check_color(color, "TransformFrames")
         self.augment = _check_augment(augment, "TransformFrames")
@@ -2428,6 +2747,7 @@ class TransformFrames:
         self.random = self.random_crop or self.random_hflip or self.random_vflip
         self.generator, self.last_params = generator, None
         self.size = int(max(self.input_size))
+        self.blur = _check_blur(blur, self.size, "TransformFrames")
         if not isinstance(crop, str):
             crop_window(1 << 30, 1 << 30, self.size, crop)          # a malformed or negative window fails here
         elif crop != "center":
@@ -2482,16 +2802,20 @@ class TransformFrames:
         if self.per_clip_geometry:
             self._device_filter("random_short_side / random_resized_crop")
         self._resize = None
-        if self.color is not None or self.augment is not None or self.mix is not None:   # the resize half of a call with colour /
-            self._resize = copy.copy(self)                           # augment / mix: this transform, writing uint8 frames (tables cache and generator shared)
+        if self.color is not None or self.augment is not None or self.mix is not None or self.blur is not None:   # the resize half of a call with colour /
+            self._resize = copy.copy(self)                           # blur / augment / mix: this transform, writing uint8 frames (tables cache and generator shared)
             self._resize.color, self._resize.augment, self._resize.out, self._resize.dtype = None, None, "frames", torch.float32
-            self._resize.mix = None
+            self._resize.mix, self._resize.blur = None, None
 
-    def _call_color(self, frames, params, geometry, color_params, augment_params=None, mix_params=None):
-        """A call with color=, augment= and / or mix=: the resize writes uint8 frames into scratch (every draw of the plain call, in
-        its order), then the colour lists are drawn clip by clip and applied, then the augment's draw, then the mix's; the last
-        stage writes the requested output, the stages in front of it uint8 scratch."""
+    def _call_color(self, frames, params, geometry, color_params, augment_params=None, mix_params=None, blur_params=None):
+        """A call with color=, blur=, augment= and / or mix=: the resize writes uint8 frames into scratch (every draw of the plain
+        call, in its order), then the colour lists are drawn clip by clip and applied, then the blur's draw, then the augment's,
+        then the mix's; the last stage writes the requested output, the stages in front of it uint8 scratch."""
         rs = self._resize
+        if blur_params is not None:                                  # validated before a device is touched
+            if self.blur is None:
+                raise PtxError("TransformFrames: blur_params= needs a transform built with blur=GaussianBlur(..)")
+            blur_params = self.blur.check_params(blur_params, None, self.size, self.size)
         if mix_params is not None:                                   # validated before a device is touched
             if self.mix is None:
                 raise PtxError("TransformFrames: mix_params= needs a transform built with mix=BatchMix(..)")
@@ -2507,7 +2831,7 @@ class TransformFrames:
         u8 = rs(frames, params=params, geometry=geometry)
         self.last_params, self.last_geometry = rs.last_params, rs.last_geometry
         return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params, self.mix,
-                             mix_params)
+                             mix_params, self.blur, blur_params)
 
     def _device_filter(self, what):
         """The PTX_RESAMPLE_* code of this transform's filter for the device table builder, or PtxError: a per-clip
@@ -2684,7 +3008,7 @@ class TransformFrames:
             self._cache.popitem(last=False)
         return hit
 
-    def __call__(self, frames, params=None, geometry=None, color_params=None, augment_params=None, mix_params=None):
+    def __call__(self, frames, params=None, geometry=None, color_params=None, augment_params=None, mix_params=None, blur_params=None):
         """uint8 CUDA frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3], any H, W  ->
         out="tensor": [N,3,T,S,S] | [3,T,S,S] | [3,S,S] (fp32 or bf16);  out="frames": uint8, same rank, H, W -> S, S.
         A `YUV420` source is taken in place of the frames (converted while the kernel stages its rows: the same bits as
@@ -2703,9 +3027,13 @@ class TransformFrames:
         applies a given draw instead.
         With mix= (a `BatchMix`) its launch runs last, behind the resize, the colour launch and the augment, reads their uint8
         frames and writes the erased and mixed normalised clip; its draw comes after every other draw of the call and is kept as
-        `mix.last_params` (`mix.targets(labels, K)` gives the matching soft targets); mix_params applies a given draw instead."""
-        if self.color is not None or self.augment is not None or self.mix is not None:
-            return self._call_color(frames, params, geometry, color_params, augment_params, mix_params)
+        `mix.last_params` (`mix.targets(labels, K)` gives the matching soft targets); mix_params applies a given draw instead.
+        With blur= (a `GaussianBlur`) its launch runs behind the colour launch and in front of the augment and the mix; its draw
+        comes in that order too (after the colour draw) and is kept as `blur.last_params`; blur_params applies a given draw."""
+        if self.color is not None or self.augment is not None or self.mix is not None or self.blur is not None:
+            return self._call_color(frames, params, geometry, color_params, augment_params, mix_params, blur_params)
+        if blur_params is not None:
+            raise PtxError("TransformFrames: blur_params= needs a transform built with blur=GaussianBlur(..)")
         if mix_params is not None:
             raise PtxError("TransformFrames: mix_params= needs a transform built with mix=BatchMix(..)")
         if color_params is not None:
@@ -3161,13 +3489,14 @@ class SampleClips:
     color: a `ColorJitter` applied behind the resize, one list per output clip, as for `TransformFrames(.., color=)`.
     augment: a `RandAugment` applied behind the resize and the colour, one draw per output clip, as for `TransformFrames(.., augment=)`.
     mix: a `BatchMix` applied last, across the output clips of the call, as for `TransformFrames(.., mix=)` (out="tensor" only).
+    blur: a `GaussianBlur` applied behind the colour and in front of the augment, one draw per output clip, as for `TransformFrames(.., blur=)`.
     interpolation: the resize filter, passed to `spatial`; every clip's tables are built on the device, so nearest, box,
     bilinear and bicubic (see TransformFrames)."""
 
     def __init__(self, opts, num_frames=16, frame_stride=4, clips=1, sampling="dense", random_start=True, scale=0.875,
                  preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False, random_crop=False, random_hflip=False,
                  random_vflip=False, random_short_side=None, random_resized_crop=False, out="tensor", dtype=torch.float32,
-                 generator=None, color=None, augment=None, interpolation="bilinear", mix=None):
+                 generator=None, color=None, augment=None, interpolation="bilinear", mix=None, blur=None):
         self.color = _check_color(color, "SampleClips")
         self.augment = _check_augment(augment, "SampleClips")
         self.mix = _check_mix(mix, out, "SampleClips")
@@ -3185,12 +3514,13 @@ class SampleClips:
         self.num_frames, self.frame_stride, self.clips, self.sampling = num_frames, frame_stride, clips, sampling
         self.random_start, self.generator = bool(random_start), generator
         self.out, self.dtype, self.size, self.norm = out, dtype, self.spatial.size, self.spatial.norm
+        self.blur = _check_blur(blur, self.size, "SampleClips")
         self.last_indices, self.last_geometry = None, None
         self._resize = None
-        if self.color is not None or self.augment is not None or self.mix is not None:   # the resize half of a call with colour / augment / mix (see TransformFrames)
+        if self.color is not None or self.augment is not None or self.mix is not None or self.blur is not None:   # the resize half of a call with colour / blur / augment / mix (see TransformFrames)
             self._resize = copy.copy(self)
             self._resize.color, self._resize.augment, self._resize.out, self._resize.dtype = None, None, "frames", torch.float32
-            self._resize.mix = None
+            self._resize.mix, self._resize.blur = None, None
 
     # ---- host only: no device is touched -------------------------------------------------------
     @staticmethod
@@ -3341,7 +3671,7 @@ class SampleClips:
             raise PtxError("SampleClips: videos[%d] is on %s, videos[0] on %s: a batch lives on one device" % (i, devs[i], devs[0]))
         return videos
 
-    def __call__(self, videos, indices=None, geometry=None, color_params=None, augment_params=None, mix_params=None):
+    def __call__(self, videos, indices=None, geometry=None, color_params=None, augment_params=None, mix_params=None, blur_params=None):
         """videos: a list / tuple of uint8 CUDA tensors [Tv_i,H_i,W_i,3] of any sizes and lengths on one device | one
         [N,Tv,H,W,3] tensor (N videos) | one [Tv,H,W,3] tensor | a list of `YUV420` sources with planes [Tv,H,W] | one
         `YUV420` with planes [N,Tv,H,W] or [Tv,H,W]  ->  out="tensor": [N*clips,3,T,S,S] (fp32 or bf16); out="frames": uint8
@@ -3353,14 +3683,20 @@ class SampleClips:
         list per output clip, drawn after every other draw of the call and kept as `color.last_params`; color_params applies
         given lists instead.  With augment= (a `RandAugment`) its positions run behind the resize and the colour launch, one draw
         per output clip after every other draw of the call (`augment.last_params`); augment_params applies a given draw instead.
-        With mix= (a `BatchMix`) its launch runs last across the output clips (`mix.last_params`); mix_params applies a given draw."""
+        With mix= (a `BatchMix`) its launch runs last across the output clips (`mix.last_params`); mix_params applies a given draw.
+        With blur= (a `GaussianBlur`) its launch runs behind the colour launch, one draw per output clip after the colour draw
+        (`blur.last_params`); blur_params applies a given draw."""
+        if blur_params is not None and self.blur is None:
+            raise PtxError("SampleClips: blur_params= needs a sampler built with blur=GaussianBlur(..)")
         if mix_params is not None and self.mix is None:
             raise PtxError("SampleClips: mix_params= needs a sampler built with mix=BatchMix(..)")
         if color_params is not None and self.color is None:
             raise PtxError("SampleClips: color_params= needs a sampler built with color=ColorJitter(..)")
         if augment_params is not None and self.augment is None:
             raise PtxError("SampleClips: augment_params= needs a sampler built with augment=RandAugment(..)")
-        if self.color is not None or self.augment is not None or self.mix is not None:
+        if self.color is not None or self.augment is not None or self.mix is not None or self.blur is not None:
+            if blur_params is not None:                              # validated before a device is touched
+                blur_params = self.blur.check_params(blur_params, None, self.size, self.size)
             if color_params is not None:                             # validated before a device is touched
                 color_params = self.color.check_params(color_params)
             if augment_params is not None:
@@ -3371,7 +3707,7 @@ class SampleClips:
             u8 = rs(videos, indices=indices, geometry=geometry)
             self.last_indices, self.last_geometry = rs.last_indices, rs.last_geometry
             return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params, self.mix,
-                                 mix_params)
+                                 mix_params, self.blur, blur_params)
         if (indices is None) != (geometry is None):
             raise PtxError("SampleClips: indices= and geometry= are given together (a replay) or not at all (a draw)")
         vids = self._videos(videos)
