@@ -23,7 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 SOURCES = ["conv_igemm.hip", "conv_chain.hip", "conv_program.hip", "pack_layout.hip", "pool_head.hip", "nonlocal_attn.hip",
            "conv_stem_x3.hip", "conv_stem_f32.hip", "conv_body_f32.hip", "gen_stage_f16.hip"]
-HEADERS = ["ptx_common.h", "conv_igemm_kernel.h", "resize_common.h", "conv_stem_patch_f32.h", "color_jitter.h", "rand_augment.h", "batch_mix.h", "warp_frames.h", "blur_frames.h", os.path.join("..", "..", "include", "ptx_amd.h"),
+HEADERS = ["ptx_common.h", "conv_igemm_kernel.h", "conv_ws_kernel.h", "resize_common.h", "conv_stem_patch_f32.h", "color_jitter.h", "rand_augment.h", "batch_mix.h", "warp_frames.h", "blur_frames.h", os.path.join("..", "..", "include", "ptx_amd.h"),
            os.path.join("..", "..", "include", "ptx_amd_wino4.h"), os.path.join("..", "..", "include", "ptx_amd_tfir.h"),
            os.path.join("..", "..", "include", "ptx_amd_yuv16.h"), os.path.join("..", "..", "include", "ptx_amd_color.h"),
            os.path.join("..", "..", "include", "ptx_amd_randaug.h"), os.path.join("..", "..", "include", "ptx_amd_resample.h"),

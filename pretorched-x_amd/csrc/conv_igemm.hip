@@ -29,6 +29,7 @@
 // the logical one -- harmless because A and B use the same permutation.
 // fp32 in, fp32 accumulate, bit-exact k-ordered fma chain (cdna_hip_programming.md section 3).
 #include "conv_igemm_kernel.h"
+#include "conv_ws_kernel.h"
 
 namespace ptx {
 
@@ -150,6 +151,45 @@ static int launch_cfg_re(const ConvArgs& a, dim3 grid, hipStream_t st) {
     if ((a.kA % BK) || (a.kB % BK) || (a.dual && ((a.kA2 % BK) || (a.wcol2 % BK))))
         return launch_one<BM, BN, BK, WM, WN, MT, true, false, true, NSTAGE, false, X3, 0, true>(a, grid, st);
     return launch_one<BM, BN, BK, WM, WN, MT, false, false, true, NSTAGE, false, X3, 0, true>(a, grid, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// Persistent weight-stationary tiles (".../ws", conv_ws_kernel.h): fp32 1x1x1 unit-stride convs with a short K whose
+// filter slice, ring and parking area fit one CU's LDS.  ptx_conv3d_config_supported says which problems they take; a /ws
+// index launched outside that rule (a split-K factor, a batched GEMM, PTX_CONV_WS=0) runs the generic row-major tile of the
+// same shape, so every index of the table still computes every fp32 problem.
+// ------------------------------------------------------------------------------------------
+// PTX_CONV_WS=0: no problem is eligible.  Read per call: one binary does the A/B.
+static bool ws_enabled() {
+    const char* e = getenv("PTX_CONV_WS");
+    return !(e && atoi(e) == 0);
+}
+constexpr unsigned kWsFlags = PTX_EPI_RELU | PTX_EPI_RES_ADD | PTX_SPLITK_FUSED;      // (the last only asks for a fused split-K reduction)
+
+template <int BM, int BN, int MT>
+static int launch_ws(const ConvArgs& a, dim3 grid, hipStream_t st) {
+    using G = WsGeom<BM, BN, MT>;
+    const bool eligible = ws_enabled() && a.unit_pointwise && !a.dual && a.groups <= 1 && !a.f16 && !a.x3 && grid.y == 1 &&
+                          a.split_k == 1 && !(a.flags & ~(kWsFlags | kNoSkipEarly)) && a.kA == a.kB && a.kB % kWsBK == 0 &&
+                          G::lds_bytes(a.kB / kWsBK) <= kWsLdsMax;
+    if (!eligible) return launch_cfg_re<BM, BN, kWsBK, 2, 2, MT, 2>(a, grid, st);
+    const size_t lds = G::lds_bytes(a.kchunks);
+    // workers per column block: what fits the chip at this LDS size (at most four workgroups of four waves per CU)
+    const int per_cu = (int)std::min<size_t>(kWsLdsMax / lds, 4);
+    int workers = std::max(kNumCU * per_cu / a.n_tiles, 1);
+    const char* e = getenv("PTX_WS_WORKERS");              // a cap, read per call (tests force several row tiles per worker)
+    const int cap = e ? atoi(e) : 0;
+    workers = cap > 0 ? std::min(workers, cap) : std::min(workers, a.m_tiles);
+    auto kern = conv_ws_kernel<BM, BN, MT>;
+    static bool attr_set[64] = {};   // per device; benign race (idempotent call)
+    int dev = 0;
+    PTX_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        PTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWsLdsMax));
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)(workers * a.n_tiles)), dim3(G::NT), lds, st, a, workers);
+    return hip_check(hipGetLastError(), "conv_ws launch");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -302,6 +342,7 @@ struct ConvConfig {
     bool x3;          // split fp32 operands on the fp16 matrix cores (PTX_F16X3_OPERANDS)
     int kwr;          // kw-reuse tile (3-wide stride-1 filters, BM a whole number of output rows)
     bool bf16;        // with f16: bfloat16 operands (PTX_BF16_OPERANDS)
+    bool ws;          // persistent weight-stationary tile (conv_ws_kernel.h): eligibility in ptx_conv3d_config_supported
 };
 
 #define PTX_CFG(BM, BN, BK, WM, WN, MT) \
@@ -337,6 +378,8 @@ struct ConvConfig {
 #define PTX_CFG_KWR_F16(BM, BN, BK, WM, WN, MT) \
     { BM, BN, BK, WM, WN, MT, #BM "x" #BN "x" #BK "/" #WM "x" #WN "/m" #MT "/dma/kwr/f16", \
       launch_cfg_kwr<BM, BN, BK, WM, WN, MT, true, false, 3>, false, true, false, 3 }
+#define PTX_CFG_WS(BM, BN, MT) \
+    { BM, BN, 32, 2, 2, MT, #BM "x" #BN "x32/2x2/m" #MT "/dma/ws", launch_ws<BM, BN, MT>, false, false, false, 0, false, true }
 #define PTX_CFG_X3R(BM, BN, BK, WM, WN, MT, NS) \
     { BM, BN, BK, WM, WN, MT, #BM "x" #BN "x" #BK "/" #WM "x" #WN "/m" #MT "/dma" #NS "/x3", \
       launch_cfg<BM, BN, BK, WM, WN, MT, true, NS, false, true>, false, false, true, 0 }
@@ -516,23 +559,27 @@ static const ConvConfig kConfigs[] = {
     PTX_CFG_X3RE(32, 64, 64, 2, 2, 16, 3),    // 150
     PTX_CFG_X3RE(32, 128, 64, 2, 2, 16, 2),   // 151
     PTX_CFG_X3RE(128, 64, 32, 2, 2, 32, 2),   // 152
+    // persistent weight-stationary tile for the short-K pointwise convs: filter slice resident in LDS, rows through a
+    // two-tile LDS-DMA ring, row-major epilogue under the next tile's loads (conv_ws_kernel.h; BK names the 32-float chunk;
+    // K up to 288).  64x64, 64x128 and 32x128 were built, measured and dropped: DESIGN.md 3.42
+    PTX_CFG_WS(32, 64, 16),                   // 153
     // bf16 operands (the bf16 video ResNets): the f16 tile family on v_mfma_f32_32x32x16_bf16 / 16x16x32_bf16.  BK counts
     // 32-bit words (2 channels); BK 16 serves the folded stem (kH*kW*3 = 147 -> 160 channels = 5 chunks of 16 words)
-    PTX_CFG_BF16(128, 128, 32, 4, 2, 32),  // 153
-    PTX_CFG_BF16(128, 64, 32, 4, 2, 32),   // 154
-    PTX_CFG_BF16(64, 64, 32, 2, 2, 32),    // 155
-    PTX_CFG_BF16(64, 128, 32, 2, 2, 32),   // 156
-    PTX_CFG_BF16(256, 128, 32, 4, 2, 32),  // 157
-    PTX_CFG_BF16(256, 64, 32, 4, 1, 32),   // 158
-    PTX_CFG_BF16(128, 64, 32, 2, 2, 32),   // 159
-    PTX_CFG_BF16(32, 64, 32, 2, 2, 16),    // 160 small M
-    PTX_CFG_BF16(32, 128, 32, 2, 2, 16),   // 161 small M, wide
-    PTX_CFG_BF16(64, 32, 32, 2, 2, 16),    // 162 narrow outputs ((2+1)D mid widths)
-    PTX_CFG_BF16(128, 128, 16, 4, 2, 32),  // 163
-    PTX_CFG_BF16(128, 64, 16, 4, 2, 32),   // 164 stem
-    PTX_CFG_BF16(256, 64, 16, 4, 1, 32),   // 165 stem
-    PTX_CFG_BF16(64, 64, 16, 2, 2, 32),    // 166
-    PTX_CFG_BF16(128, 32, 16, 4, 1, 32),   // 167 the (2+1)D spatial stem (83 channels: 3 x 32 columns)
+    PTX_CFG_BF16(128, 128, 32, 4, 2, 32),  // 154
+    PTX_CFG_BF16(128, 64, 32, 4, 2, 32),   // 155
+    PTX_CFG_BF16(64, 64, 32, 2, 2, 32),    // 156
+    PTX_CFG_BF16(64, 128, 32, 2, 2, 32),   // 157
+    PTX_CFG_BF16(256, 128, 32, 4, 2, 32),  // 158
+    PTX_CFG_BF16(256, 64, 32, 4, 1, 32),   // 159
+    PTX_CFG_BF16(128, 64, 32, 2, 2, 32),   // 160
+    PTX_CFG_BF16(32, 64, 32, 2, 2, 16),    // 161 small M
+    PTX_CFG_BF16(32, 128, 32, 2, 2, 16),   // 162 small M, wide
+    PTX_CFG_BF16(64, 32, 32, 2, 2, 16),    // 163 narrow outputs ((2+1)D mid widths)
+    PTX_CFG_BF16(128, 128, 16, 4, 2, 32),  // 164
+    PTX_CFG_BF16(128, 64, 16, 4, 2, 32),   // 165 stem
+    PTX_CFG_BF16(256, 64, 16, 4, 1, 32),   // 166 stem
+    PTX_CFG_BF16(64, 64, 16, 2, 2, 32),    // 167
+    PTX_CFG_BF16(128, 32, 16, 4, 1, 32),   // 168 the (2+1)D spatial stem (83 channels: 3 x 32 columns)
 };
 constexpr int kNumConfigs = sizeof(kConfigs) / sizeof(kConfigs[0]);
 
@@ -650,6 +697,18 @@ extern "C" int ptx_conv3d_config_supported(const ptx_conv3d_desc* d, int config)
             return 0;
     }
     if (groups > 1 && !c.direct && ((d->Co / groups) % c.BN || dual)) return 0;  // an MFMA tile stays inside one group
+    if (c.ws) {
+        // fp32 1x1x1 unit-stride single-source conv, bias / residual / ReLU only, whole 32-float chunks of K in every row,
+        // filter slice + ring + parking area within one CU's LDS, every operand below 2 GiB (32-bit buffer offsets)
+        if (!ws_enabled() || (d->flags & ~kWsFlags) || d->kT * d->kH * d->kW != 1 || d->sT * d->sH * d->sW != 1 ||
+            d->pT || d->pH || d->pW || groups > 1 || dual || d->Kc % kWsBK || d->ldx < d->Kc ||
+            ws_lds_bytes(c.BM, c.BN, c.MT, d->Kc / kWsBK) > kWsLdsMax)
+            return 0;
+        const uint64_t M = (uint64_t)d->N * d->To * d->Ho * d->Wo, lim = 0x80000000ull;
+        if (M * d->ldx * 4ull >= lim || M * d->ldy * 4ull >= lim || (uint64_t)d->Co_pad * d->Kc * 4ull >= lim ||
+            ((d->flags & PTX_EPI_RES_ADD) && M * d->ldr * 4ull >= lim))
+            return 0;
+    }
     return 1;
 }
 

@@ -207,11 +207,11 @@ def _best_conv_tile(t, stp, key, kind, split_k=True):
         if cands and not (any(c in name for c in cands) or (inc is not None and cfg == inc[0])):
             continue
         tile = admissible(name, d, kind, M, ncol, stp.macs if stp is t.plan.stem_bf16_step else None)
-        if tile is None:
-            continue
-        blocks = ((M + tile[0] - 1) // tile[0]) * ((ncol + tile[1] - 1) // tile[1])
+        if tile is None or not lib.ptx_conv3d_config_supported(C.byref(d), cfg):
+            continue                         # (a tile the plan compiler would drop again; a "/ws" tile outside its rule)
+        blocks =((M + tile[0] - 1) // tile[0]) * ((ncol + tile[1] - 1) // tile[1])
         splits = [1]
-        if blocks < 512 and split_k:
+        if blocks < 512 and split_k and not name.endswith("/ws"):      # (a persistent tile has no split-K form)
             splits += [s for s in (2, 3, 4, 6, 8) if steps_k // s >= 4 and blocks * s <= 2048]
         for sk in splits:
             if sk > 1 and lib.ptx_conv3d_workspace_bytes(C.byref(d), sk) > t.plan.ws_bytes:
