@@ -24,6 +24,7 @@ from .heads import relation_mlp
 from . import transforms  # noqa: F401
 from . import models, utils  # noqa: F401  (utils.Identity: README.md:543-546; models.Identity: models/__init__.py:79)
 from .adopt import accelerate  # noqa: F401
+from .cam import CamResult  # noqa: F401
 from .biggan import BigGANDeepGenerator, biggan_deep  # noqa: F401
 from .i3d import InceptionI3d, i3d  # noqa: F401
 from . import slowfast  # noqa: F401  (reference: `from .models import slowfast`, pretorched/__init__.py:83)

@@ -24,6 +24,7 @@ LINEAR_BF16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_a
 BN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_bn.h")            # batch-statistics BatchNorm (update_bn)
 WARP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_warp.h")        # interpolated affine / perspective warps
 BLUR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_blur.h")        # GaussianBlur on uint8 frames
+CAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_cam.h")          # class activation maps + overlay
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -217,6 +218,15 @@ class BlurDesc(C.Structure):
 
 
 PTX_BLUR_MAX_TAPS = 33
+
+
+class CamOverlayDesc(C.Structure):
+    """ptx_cam_overlay_desc (ptx_amd_cam.h): the maps and the frames of an overlay launch, the tables' pitches, the mode, alpha."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "k", "Tm", "h", "w", "T", "H", "W", "taps_h", "taps_w", "mode")] + [("alpha", C.c_float)]
+
+
+PTX_CAM_MAX_CLASSES, PTX_CAM_MAX_LDS_BYTES, PTX_CAM_MAX_MAP_BYTES = 8, 65536, 40960
+PTX_CAM_OUT_OVERLAY, PTX_CAM_OUT_HEAT, PTX_CAM_OUT_MAP = range(3)
 
 PTX_POOL_SAME, PTX_POOL_PAD_ZERO, PTX_POOL_BF16 = 1, 2, 4
 PTX_REL_MAX_SETS, PTX_REL_MAX_FRAMES = 8, 16
@@ -520,6 +530,17 @@ SIGNATURES_BLUR = {
 }
 
 
+# include/ptx_amd_cam.h: class activation maps of the pool + Linear heads and their overlay on uint8 frames (csrc/cam.h), bound
+# the same way (tests/test_cam_host.py)
+SIGNATURES_CAM = {
+    "ptx_cam_scores_supported": (C.c_int, [_I, _L, _I, _I, _I, _I, _I]),
+    "ptx_cam_scores": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P]),
+    "ptx_cam_quantize": (C.c_int, [_P, _P, _L, _L, _P]),
+    "ptx_cam_overlay_supported": (C.c_int, [C.POINTER(CamOverlayDesc), _P, _P]),
+    "ptx_cam_overlay": (C.c_int, [C.POINTER(CamOverlayDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
+
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
     text = open(path).read()
@@ -557,7 +578,7 @@ def lib():
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
                 list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()) + \
                 list(SIGNATURES_NL_KS.items()) + list(SIGNATURES_LINEAR_BF16.items()) + list(SIGNATURES_BN.items()) + \
-                list(SIGNATURES_WARP.items()) + list(SIGNATURES_BLUR.items()):
+                list(SIGNATURES_WARP.items()) + list(SIGNATURES_BLUR.items()) + list(SIGNATURES_CAM.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

@@ -124,6 +124,7 @@ class AdoptedResNet(VideoResNet):
 
 
 _METHODS = ("features", "logits", "forward")
+_CAM_METHODS = ("cam", "cam_frames", "logits_map")       # not offered on adopted instances: bound to raise with the supported set
 
 
 def _twin_of(model):
@@ -160,6 +161,9 @@ class _Bound:
 
     def __call__(self, *a, **k):
         model, name = self.model, self.name
+        if name in _CAM_METHODS:
+            from .cam import unsupported
+            raise unsupported(_twin_of(model) if "_ptx_twin" in model.__dict__ else model)
         if name == "engine":
             return _twin_of(model)._engine
         if name == "_replicate_for_data_parallel":
@@ -185,6 +189,8 @@ def _bind(model):
     for name in _METHODS:
         if callable(getattr(cls, name, None)):
             object.__setattr__(model, name, _Bound(model, name))
+    for name in _CAM_METHODS:
+        object.__setattr__(model, name, _Bound(model, name))
     object.__setattr__(model, "engine", _Bound(model, "engine"))
     object.__setattr__(model, "_replicate_for_data_parallel", _Bound(model, "_replicate_for_data_parallel"))
 

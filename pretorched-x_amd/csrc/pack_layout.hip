@@ -1451,3 +1451,7 @@ extern "C" int ptx_bf16_to_f32(const void* x, float* y, int64_t n, ptx_stream_t 
 // So is the per-clip GaussianBlur (include/ptx_amd_blur.h): a separable fp64 blur with reflect padding over LDS tiles, one launch
 // per batch, whose plane output is ptx_frames_u8_to_ncdhw's value of the blurred byte.
 #include "blur_frames.h"
+
+// So are the class activation maps (include/ptx_amd_cam.h): the classifier rows applied at every position of the final feature
+// map, one uint8 map per class, and its Pillow-exact overlay on uint8 frames through the resize tables above.
+#include "cam.h"

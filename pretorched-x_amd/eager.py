@@ -162,6 +162,29 @@ def resnet_forward(model, x):
     return resnet_logits(model, resnet_features(model, x))
 
 
+def resnet_cam(model, x, classes=None, topk=1):
+    """VideoResNet.cam outside the engine's contract (CPU, train()): the same definition in plain torch (cam.scores_expression)."""
+    from . import cam
+    from .transforms import cam_quantize_numpy
+    head = cam.check_model(model)
+    feats = resnet_features(model, x)
+    logits = resnet_logits(model, feats)
+    cl = cam.class_list(classes, topk, logits, head.out_features)
+    scores = cam.scores_expression(feats.float(), head.weight.float(), None if head.bias is None else head.bias.float(), cl)
+    maps = torch.from_numpy(cam_quantize_numpy(scores.detach().cpu().numpy())).to(scores.device)
+    return cam.CamResult(logits, cl, scores, maps, None)
+
+
+def resnet_logits_map(model, feats):
+    """VideoResNet.logits_map on that path: the classifier at every position."""
+    from . import cam
+    head = cam.check_model(model, "logits maps")
+    out = torch.einsum("kc,nc...->nk...", head.weight, feats)
+    if head.bias is not None:
+        out = out + head.bias.reshape((1, -1) + (1,) * (feats.dim() - 2))
+    return out
+
+
 def relation(rel, x):
     """Relation.forward (trn.py:39-56)."""
     _count()

@@ -649,6 +649,42 @@ class Engine:
                 self._to_ncdhw(f, out, 3)
         return out
 
+    def _frames_input(self, model, frames, opts, transform, who="forward_frames"):
+        """What forward_frames (and cam_frames) run on: the transform applied, the frames checked and made contiguous, the NCDHW /
+        NCHW view of their shape and the NormDesc of `opts` (default: the model's own pretrained settings)."""
+        from .transforms import YUV420, apply_frames_transform
+        if transform is not None or isinstance(frames, YUV420):
+            frames = apply_frames_transform(transform, frames)
+        opts = model if opts is None else opts
+        get = (lambda k: opts[k]) if isinstance(opts, dict) else (lambda k: getattr(opts, k))
+        try:
+            norm = NormDesc.make(get("mean"), get("std"), get("input_space"), get("input_range"))
+        except (AttributeError, KeyError):
+            raise PtxError("%s: no mean/std/input_space/input_range on the model (they exist only for "
+                           "pretrained models, torchvision_models.py:162-166): pass opts=pretrained_settings[...]" % who)
+        if model.training:
+            raise PtxError("pretorched-x_amd is a forward-only (inference) engine: call model.eval() first")
+        prec = model_precision(model)
+        if prec != "fp32" and not (prec == "bf16" and self._bf16_stem == "direct"):
+            raise PtxError("%s runs float32 models only (this model's parameters are %s)%s" % (
+                who, prec, "; engine().bf16_stem = 'direct' lets a bfloat16 model read the frames in its stem" if prec == "bf16" else ""))
+        dims = model.arch.dims
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
+            raise PtxError("%s: frames must be a uint8 CUDA tensor" % who)
+        if frames.dim() != dims + 2:
+            raise PtxError("%s: expected %s, got shape %s" % (
+                who, "[N,T,H,W,C]" if dims == 3 else "[N,H,W,C]", tuple(frames.shape)))
+        if frames.shape[-1] != 3:
+            raise PtxError("%s: the stems take 3 channels" % who)
+        frames = frames.contiguous()
+        if dims == 3:
+            N, T, H, W, Cc = frames.shape
+            shape = (N, Cc, T, H, W)
+        else:
+            N, H, W, Cc = frames.shape
+            shape = (N, Cc, H, W)
+        return frames, shape, norm
+
     def forward_frames(self, model, frames, opts=None, transform=None):
         """Decoded uint8 frames [N,T,H,W,C] (NHWC for 2-D models) -> logits.  The tensor half of the
         reference's TransformImage (ToTensor, ToSpaceBGR, ToRange255, Normalize; transforms/utils.py:72-75)
@@ -660,37 +696,8 @@ class Engine:
         already have the input size.
         `frames` may be a `transforms.YUV420` source (NV12 / I420 planes); it needs a transform, whose kernel converts
         the colours while it stages the rows."""
-        from .transforms import YUV420, apply_frames_transform
-        if transform is not None or isinstance(frames, YUV420):
-            frames = apply_frames_transform(transform, frames)
-        opts = model if opts is None else opts
-        get = (lambda k: opts[k]) if isinstance(opts, dict) else (lambda k: getattr(opts, k))
-        try:
-            norm = NormDesc.make(get("mean"), get("std"), get("input_space"), get("input_range"))
-        except (AttributeError, KeyError):
-            raise PtxError("forward_frames: no mean/std/input_space/input_range on the model (they exist only for "
-                           "pretrained models, torchvision_models.py:162-166): pass opts=pretrained_settings[...]")
-        if model.training:
-            raise PtxError("pretorched-x_amd is a forward-only (inference) engine: call model.eval() first")
-        prec = model_precision(model)
-        if prec != "fp32" and not (prec == "bf16" and self._bf16_stem == "direct"):
-            raise PtxError("forward_frames runs float32 models only (this model's parameters are %s)%s" % (
-                prec, "; engine().bf16_stem = 'direct' lets a bfloat16 model read the frames in its stem" if prec == "bf16" else ""))
-        dims = model.arch.dims
-        if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
-            raise PtxError("forward_frames: frames must be a uint8 CUDA tensor")
-        if frames.dim() != dims + 2:
-            raise PtxError("forward_frames: expected %s, got shape %s" % (
-                "[N,T,H,W,C]" if dims == 3 else "[N,H,W,C]", tuple(frames.shape)))
-        if frames.shape[-1] != 3:
-            raise PtxError("forward_frames: the stems take 3 channels")
-        frames = frames.contiguous()
-        if dims == 3:
-            N, T, H, W, Cc = frames.shape
-            shape = (N, Cc, T, H, W)
-        else:
-            N, H, W, Cc = frames.shape
-            shape = (N, Cc, H, W)
+        frames, shape, norm = self._frames_input(model, frames, opts, transform)
+        N = frames.shape[0]
         mb = self._max_batch(model, shape[1:])
         if N > mb:
             size = -(-N // (-(-N // mb)))
@@ -836,6 +843,19 @@ class EngineOwner:
         """Recompute the running statistics of every BatchNorm with a forward-only pass over `loader` on the HIP engine
         (Engine.update_bn; `pretorched_x_amd.update_bn(loader, model, device)` is torch.optim.swa_utils.update_bn's signature)."""
         return self._engine.update_bn(self, loader, momentum=momentum, reset=reset)
+
+    # class activation maps (cam.py): defined for a global average pool + one Linear, which VideoResNet overrides these for
+    def cam(self, *a, **k):
+        from .cam import unsupported
+        raise unsupported(self)
+
+    def cam_frames(self, *a, **k):
+        from .cam import unsupported
+        raise unsupported(self)
+
+    def logits_map(self, *a, **k):
+        from .cam import unsupported
+        raise unsupported(self, "logits maps")
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)

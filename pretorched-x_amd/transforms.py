@@ -56,6 +56,10 @@ uint8 frames:
   the numpy statement of the contract, `gaussian_kernel1d` torchvision's weights).  As `TransformFrames(.., blur=gb)` /
   `SampleClips(.., blur=gb)` it runs behind `color=` and in front of `augment=` / `mix=`, the view recipes' order.
 
+* `CamOverlay` draws the class activation maps of `model.cam` / `model.cam_frames` over the frames they explain in one launch: the
+  map resized through the resize tables, coloured through a 256-entry table and blended in, equal to Pillow's resize + `Image.blend`
+  bit for bit (`cam_overlay_numpy` is the numpy statement of the contract, `cam_quantize_numpy` that of the uint8 maps).
+
 Image loading and video decoding stay host work and are not on this path.
 """
 import collections
@@ -3776,3 +3780,225 @@ class SampleClips:
         if indices is None:
             self.last_indices, self.last_geometry = idx, geo
         return y
+
+
+# ---------------------------------------------------------------------------------------------
+# Class activation maps (include/ptx_amd_cam.h): the uint8 map of a score field, its overlay on uint8 frames
+# ---------------------------------------------------------------------------------------------
+CAM_OUT = ("overlay", "heat", "map")                   # the PTX_CAM_OUT_* codes, by index
+
+
+def cam_quantize_numpy(scores):
+    """ptx_cam_quantize in numpy: float32 scores [N, k, *positions] -> uint8 of the same shape, one map per (n, j).  With mn / mx
+    the smallest / largest score of the map that is not a NaN: v = 255 * ((s - mn) / (mx - mn)), every operation rounded to
+    float32; 255 if v >= 255, trunc(v) if v > 0, else 0 (a NaN gives 0).  A flat map (mx == mn, or NaN throughout) is all zeros."""
+    s = np.ascontiguousarray(np.asarray(scores), dtype=np.float32)
+    if s.ndim < 2:
+        raise PtxError("cam_quantize_numpy: scores must be [N, k, *positions] (got shape %s)" % (s.shape,))
+    flat = s.reshape(s.shape[0] * s.shape[1], -1)
+    out = np.zeros(flat.shape, np.uint8)
+    with np.errstate(all="ignore"):
+        for i, row in enumerate(flat):
+            mn, mx = np.fmin.reduce(row), np.fmax.reduce(row)        # NaN only when every score is one
+            if not mx > mn:
+                continue
+            v = np.float32(255.0) * ((row - mn) / (mx - mn))
+            out[i] = np.where(v >= 255, 255, np.where(v > 0, np.trunc(v), 0)).astype(np.uint8)
+    return out.reshape(s.shape)
+
+
+def jet_colormap():
+    """The default colour table, uint8 [256, 3]: level i at x = i / 255 is round(255 * clip(1.5 - |4 x - p|, 0, 1)) with p = 3, 2, 1
+    for red, green, blue -- the piecewise-linear "jet" (blue, cyan, yellow, red).  Data, not a contract: any uint8 [256, 3] serves."""
+    x = np.arange(256, dtype=np.float64)[:, None] / 255.0
+    return np.floor(255.0 * np.clip(1.5 - np.abs(4.0 * x - np.array([3.0, 2.0, 1.0])[None, :]), 0.0, 1.0) + 0.5).astype(np.uint8)
+
+
+CAM_COLORMAPS = {"jet": jet_colormap}
+
+
+def _cam_colormap(colormap, who="CamOverlay"):
+    if isinstance(colormap, str):
+        if colormap not in CAM_COLORMAPS:
+            raise PtxError("%s: colormap %r is not one of %s (or pass a uint8 [256, 3] array)" % (who, colormap, sorted(CAM_COLORMAPS)))
+        return CAM_COLORMAPS[colormap]()
+    lut = colormap.detach().cpu().numpy() if isinstance(colormap, torch.Tensor) else np.asarray(colormap)
+    if lut.dtype != np.uint8 or lut.shape != (256, 3):
+        raise PtxError("%s: a colour table must be uint8 [256, 3] (got %s %s)" % (who, lut.dtype, lut.shape))
+    return np.ascontiguousarray(lut)
+
+
+def cam_default_steps(T, Tm):
+    """The map step every frame shows: floor(t * Tm / T), int32 [T]."""
+    return (np.arange(T, dtype=np.int64) * int(Tm) // int(T)).astype(np.int32)
+
+
+def _cam_steps(steps, T, Tm, who="CamOverlay"):
+    if steps is None:
+        return cam_default_steps(T, Tm)
+    st = np.asarray(steps.cpu() if isinstance(steps, torch.Tensor) else steps)
+    if st.shape != (T,) or st.dtype.kind not in "iu" or st.min() < 0 or st.max() >= Tm:
+        raise PtxError("%s: steps must be %d integers in [0, %d) (got %r)" % (who, T, Tm, steps))
+    return st.astype(np.int32)
+
+
+def _cam_mode(out, who="CamOverlay"):
+    if out not in CAM_OUT:
+        raise PtxError("%s: out=%r is not one of %s" % (who, out, CAM_OUT))
+    return CAM_OUT.index(out)
+
+
+def _cam_alpha(alpha, who="CamOverlay"):
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
+        raise PtxError("%s: alpha must be a number in [0, 1] (got %r)" % (who, alpha))
+    return float(alpha)
+
+
+def cam_overlay_numpy(maps, frames, lut=None, alpha=0.4, steps=None, out="overlay"):
+    """ptx_cam_overlay in numpy: maps uint8 [N, k, Tm, h, w], frames uint8 [N, T, H, W, 3] (out="heat" / "map": only their shape is
+    read; a tuple (T, H, W) serves) -> uint8 [N, k, T, H, W, 3] ([N, k, T, H, W] for out="map").  Per frame t the map of step
+    steps[t] (default `cam_default_steps`) is resized as Pillow resizes an "L" image with BILINEAR (`resize_axis_table` +
+    `apply_tables_numpy`: horizontal pass, uint8 intermediate, vertical pass), coloured through `lut` (default `jet_colormap()`) and
+    blended as `Image.blend(frame, heat, alpha)` blends (`color_blend_numpy(frame, heat, alpha)`)."""
+    maps = np.asarray(maps)
+    mode = _cam_mode(out, "cam_overlay_numpy")
+    alpha = _cam_alpha(alpha, "cam_overlay_numpy")
+    lut = _cam_colormap("jet" if lut is None else lut, "cam_overlay_numpy")
+    if maps.dtype != np.uint8 or maps.ndim != 5:
+        raise PtxError("cam_overlay_numpy: maps must be uint8 [N, k, Tm, h, w] (got %s %s)" % (maps.dtype, maps.shape))
+    N, k, Tm, h, w = maps.shape
+    if isinstance(frames, tuple):
+        T, H, W = frames
+        frames = None
+    else:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[0] != N or frames.shape[4] != 3:
+            raise PtxError("cam_overlay_numpy: frames must be uint8 [%d, T, H, W, 3] (got %s %s)" % (N, frames.dtype, frames.shape))
+        T, H, W = frames.shape[1:4]
+    if mode == _lib.PTX_CAM_OUT_OVERLAY and frames is None:
+        raise PtxError("cam_overlay_numpy: out=\"overlay\" needs the frames")
+    steps = _cam_steps(steps, T, Tm, "cam_overlay_numpy")
+    tables = {"rows": resize_axis_table(h, H), "cols": resize_axis_table(w, W)}
+    y = np.empty((N, k, T, H, W) + (() if mode == _lib.PTX_CAM_OUT_MAP else (3,)), np.uint8)
+    for n in range(N):
+        for j in range(k):
+            big = {}
+            for t in range(T):
+                s = int(steps[t])
+                if s not in big:
+                    big[s] = apply_tables_numpy(maps[n, j, s][:, :, None], tables)[:, :, 0]
+                if mode == _lib.PTX_CAM_OUT_MAP:
+                    y[n, j, t] = big[s]
+                elif mode == _lib.PTX_CAM_OUT_HEAT:
+                    y[n, j, t] = lut[big[s]]
+                else:
+                    y[n, j, t] = color_blend_numpy(frames[n, t], lut[big[s]], alpha).astype(np.uint8)
+    return y
+
+
+def _cam_overlay_desc(N, k, Tm, h, w, T, H, W, taps_h, taps_w, mode, alpha):
+    return _lib.CamOverlayDesc(N, k, Tm, h, w, T, H, W, taps_h, taps_w, mode, alpha)
+
+
+def _cam_overlay_supported(desc, rows=None, cols=None, who="CamOverlay"):
+    """The library's host-side check of an overlay launch (no device is touched), with its reason as a PtxError.  rows / cols: the
+    host tables, whose coefficients are then checked too."""
+    rk = None if rows is None else np.ascontiguousarray(rows[2], dtype=np.int32)
+    ck = None if cols is None else np.ascontiguousarray(cols[2], dtype=np.int32)
+    if not _lib.lib().ptx_cam_overlay_supported(C.byref(desc), C.c_void_p(None if rk is None else rk.ctypes.data),
+                                                C.c_void_p(None if ck is None else ck.ctypes.data)):
+        raise PtxError("%s: %s" % (who, _lib.lib().ptx_last_error().decode(errors="replace")))
+
+
+class CamOverlay:
+    """Draws class activation maps over the frames they explain, on the device, equal to Pillow bit for bit:
+    `Image.blend(frame, Image.fromarray(lut[np.asarray(Image.fromarray(map, "L").resize((W, H), BILINEAR))]), alpha)` per frame,
+    in one launch per batch (`ptx_cam_overlay`; `cam_overlay_numpy` is its numpy statement).
+    alpha: the weight of the heat image, 0 .. 1.  colormap: "jet" (`jet_colormap`) or any uint8 [256, 3] table.
+    out: "overlay" (the blend), "heat" (the coloured map alone; the frames give the size only) or "map" (the resized map, one byte
+    per pixel).  Called as `(frames_u8, maps_u8, steps=None)`:
+      frames uint8 CUDA [N, T, H, W, 3], maps uint8 CUDA [N, k, T', h, w]  ->  uint8 [N, k, T, H, W, 3]  ("map": [N, k, T, H, W]);
+      frames [N, H, W, 3],               maps [N, k, h, w] (the 2-D nets)  ->  uint8 [N, k, H, W, 3]     ("map": [N, k, H, W]).
+    steps: which map step every frame shows, T integers (default floor(t * T' / T)).  The tables are built once per
+    (h, w, H, W) and kept on the device.  `model.cam_frames(..)` returns both arguments: `ov(r.frames, r.maps)`."""
+    CACHE_SIZE = 8
+    LIMIT_BYTES = (1 << 31) - 1
+
+    def __init__(self, alpha=0.4, colormap="jet", out="overlay"):
+        self.alpha = _cam_alpha(alpha)
+        self.out = out
+        self.mode = _cam_mode(out)
+        self.lut = _cam_colormap(colormap)
+        self._cache = collections.OrderedDict()
+        self._luts = {}
+
+    def tables(self, h, w, H, W):
+        """Host tables of the map's resize, in build_tables' form: `rows` for h -> H and `cols` for w -> W."""
+        return {"rows": resize_axis_table(h, H), "cols": resize_axis_table(w, W)}
+
+    def _device_tables(self, h, w, H, W, device):
+        key = (h, w, H, W, str(device))
+        hit = self._cache.get(key)
+        if hit is not None:
+            self._cache.move_to_end(key)
+            return hit
+        t = self.tables(h, w, H, W)
+        _cam_overlay_supported(_cam_overlay_desc(1, 1, 1, h, w, 1, H, W, t["rows"][2].shape[1], t["cols"][2].shape[1], self.mode,
+                                                 self.alpha), t["rows"], t["cols"])
+        parts = [a.reshape(-1) for a in t["rows"] + t["cols"]]
+        offs = np.cumsum([0] + [p.size for p in parts])
+        buf = torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(device)         # one small upload per geometry
+        hit = (buf, [int(o) * 4 for o in offs[:-1]], t["rows"][2].shape[1], t["cols"][2].shape[1])
+        self._cache[key] = hit
+        while len(self._cache) > self.CACHE_SIZE:
+            self._cache.popitem(last=False)
+        return hit
+
+    def _device_lut(self, device):
+        hit = self._luts.get(str(device))
+        if hit is None:
+            hit = self._luts[str(device)] = torch.from_numpy(self.lut).to(device)
+        return hit
+
+    def __call__(self, frames, maps, steps=None):
+        for name, t in (("frames", frames), ("maps", maps)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+                raise PtxError("CamOverlay: %s must be a uint8 CUDA tensor (no CPU fallback; cam_overlay_numpy states the result)" % name)
+        if frames.device != maps.device:
+            raise PtxError("CamOverlay: frames on %s but maps on %s" % (frames.device, maps.device))
+        flat = maps.dim() == 4 and frames.dim() == 4                                     # the 2-D nets: one frame, one step
+        if flat:
+            frames, maps = frames.unsqueeze(1), maps.unsqueeze(2)
+        if maps.dim() != 5 or frames.dim() != 5 or frames.shape[4] != 3 or frames.shape[0] != maps.shape[0]:
+            raise PtxError("CamOverlay: expected frames [N,T,H,W,3] with maps [N,k,T',h,w], or frames [N,H,W,3] with maps [N,k,h,w] "
+                           "(got %s and %s)" % (tuple(frames.shape), tuple(maps.shape)))
+        frames, maps = frames.contiguous(), maps.contiguous()
+        N, k, Tm, h, w = maps.shape
+        T, H, W = frames.shape[1:4]
+        st = _cam_steps(steps, T, Tm)
+        dev = frames.device
+        bpp = 1 if self.mode == _lib.PTX_CAM_OUT_MAP else 3
+        with torch.cuda.device(dev):
+            buf, offs, taps_h, taps_w = self._device_tables(h, w, H, W, dev)
+            lut = self._device_lut(dev)
+            step = torch.from_numpy(st).to(dev)
+            y = torch.empty((N, k, T, H, W) + ((3,) if bpp == 3 else ()), device=dev, dtype=torch.uint8)
+            per_map = T * H * W * bpp
+            fit = self.LIMIT_BYTES // per_map                                             # maps of one launch
+            if fit < 1:
+                raise PtxError("CamOverlay: one map over %d frames of %dx%d exceeds the 2 GiB per-launch limit" % (T, H, W))
+            base = buf.data_ptr()
+            tabs = [C.c_void_p(base + o) for o in offs]
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            # ranges of (n, j): whole clips while k maps fit a launch, else runs of one clip's classes
+            if fit >= k:
+                ranges = [(n0, min(n0 + fit // k, N), 0, k) for n0 in range(0, N, fit // k)]
+            else:
+                ranges = [(n, n + 1, j0, min(j0 + fit, k)) for n in range(N) for j0 in range(0, k, fit)]
+            for n0, n1, j0, j1 in ranges:
+                desc = _cam_overlay_desc(n1 - n0, j1 - j0, Tm, h, w, T, H, W, taps_h, taps_w, self.mode, self.alpha)
+                _cam_overlay_supported(desc)
+                check(_lib.lib().ptx_cam_overlay(C.byref(desc), C.c_void_p(maps[n0, j0].data_ptr()), C.c_void_p(frames[n0].data_ptr()),
+                                                 C.c_void_p(lut.data_ptr()), *tabs, C.c_void_p(step.data_ptr()),
+                                                 C.c_void_p(y[n0, j0].data_ptr()), stream), "ptx_cam_overlay")
+        return y[:, :, 0] if flat else y

@@ -23,7 +23,9 @@ from typing import Optional, Sequence
 import torch
 import torch.nn as nn
 
+from . import cam as _cam
 from . import eager
+from ._lib import PtxError
 from .engine import Engine, EngineOwner  # noqa: F401
 
 
@@ -437,6 +439,31 @@ class VideoResNet(EngineOwner, nn.Module):
         per launch (default: as many as the per-launch size limit allows).  See Engine.forward_views."""
         return self._engine.forward_views(self, video, opts, views, reduce, chunk)
 
+    # -- class activation maps (cam.py): "where and when" for the global-average-pool + Linear head --
+    def cam(self, input, classes=None, topk=1):
+        """One forward plus the class activation maps of `classes` -- None: the top-`topk` classes of every clip's logits; an int:
+        that class for every clip; [N][k] indices: a list of its own per clip -- as a `cam.CamResult` (logits, classes, scores,
+        maps, frames=None).  scores[n, j] is the classifier row of classes[n, j] applied at every position of the final feature
+        map (its mean over the positions is the logit), maps its uint8 stretch.  bf16 models read bf16 features and the fp32
+        classifier copy their head keeps.  A head that is not an nn.Linear raises."""
+        if eager.wanted(self, input):
+            return eager.resnet_cam(self, input, classes, topk)
+        return _cam.cam(self._engine, self, input, classes, topk)
+
+    def cam_frames(self, frames, opts=None, transform=None, classes=None, topk=1):
+        """`cam` from decoded uint8 frames, through the route `forward_frames` takes; `result.frames` holds the uint8 frames the
+        model saw (the transform's output), what `transforms.CamOverlay` draws the maps on."""
+        return _cam.cam_frames(self._engine, self, frames, opts, transform, classes, topk)
+
+    def logits_map(self, features):
+        """Every class at every position: NCDHW float32 features -> [N, classes, T', H', W'] ([N, classes, H', W'] for the 2-D
+        nets); `cam(x).scores` are its rows of the chosen classes, up to the summation order."""
+        if isinstance(features, torch.Tensor) and features.dtype == torch.bfloat16:
+            raise PtxError("logits_map takes float32 features (bf16 models: model.cam(x) reads the bf16 map with the fp32 classifier)")
+        if eager.wanted(self, features):
+            return eager.resnet_logits_map(self, features)
+        return _cam.logits_map(self._engine, self, features)
+
 
 # ---------------------------------------------------------------------------------------------
 # TRN relation heads (reference trn.py:20-113): standalone modules, HIP-executed MLPs
@@ -668,6 +695,15 @@ class TRN(nn.Module):
         mb = eng._max_batch(self.base_model, (3, S, S))
         return run_views(video, views, lambda fr: self.forward_frames(fr, opts), max(1, mb // self.num_segments), reduce,
                          chunk, "TRN.forward_views")
+
+    def cam(self, *a, **k):
+        raise _cam.unsupported(self)
+
+    def cam_frames(self, *a, **k):
+        raise _cam.unsupported(self)
+
+    def logits_map(self, *a, **k):
+        raise _cam.unsupported(self, "logits maps")
 
     @property
     def crop_size(self):
