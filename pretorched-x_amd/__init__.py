@@ -329,6 +329,26 @@ def nonlocal_r2plus1d50(num_classes=339):
     return _build("nonlocal_r2plus1d50", num_classes)
 
 
+def _csn_factory(name):
+    def factory(num_classes=400, pretrained=None, shortcut_type="B"):
+        if pretrained is not None:
+            raise PtxError("no pretrained weights are published for %s: pretrained must be None" % name)
+        return _build(name, num_classes, shortcut_type)
+    factory.__name__ = name
+    factory.__doc__ = ("Constructs %s: a channel-separated network (Tran et al., ICCV 2019) -- ResNet3D bottlenecks whose 3x3x3 conv "
+                       "is depthwise (ir-CSN), optionally behind one more 1x1x1 conv (ip-CSN).  Builder-defined: the reference has "
+                       "no CSN source." % name)
+    return factory
+
+
+ir_csn50 = _csn_factory("ir_csn50")
+ir_csn101 = _csn_factory("ir_csn101")
+ir_csn152 = _csn_factory("ir_csn152")
+ip_csn50 = _csn_factory("ip_csn50")
+ip_csn101 = _csn_factory("ip_csn101")
+ip_csn152 = _csn_factory("ip_csn152")
+
+
 def _resnet2d_factory(name):
     def factory(num_classes=1000, pretrained="imagenet"):
         model = _build(name, num_classes)
@@ -371,4 +391,5 @@ model_names = ["resnet3d10", "resnet3d18", "resnet3d34", "resnet3d50", "resnet3d
                "resnet101", "resnet152", "trn", "i3d", "resnext3d10", "resnext3d18", "resnext3d34", "resnext3d50",
                "resnext3d101", "resnext3d152", "resnext3d200", "wideresnet3d50", "preact_resnet3d10", "preact_resnet3d18", "preact_resnet3d34",
                "preact_resnet3d50", "preact_resnet3d101", "preact_resnet3d152", "preact_resnet3d200",
-               "mvresnet10", "mvresnet18", "mvresnet34", "mvresnet50", "mvresnet101", "mvresnet152", "mvresnet200"]
+               "mvresnet10", "mvresnet18", "mvresnet34", "mvresnet50", "mvresnet101", "mvresnet152", "mvresnet200",
+               "ir_csn50", "ir_csn101", "ir_csn152", "ip_csn50", "ip_csn101", "ip_csn152"]

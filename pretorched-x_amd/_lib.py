@@ -25,6 +25,7 @@ BN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_bn.h")
 WARP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_warp.h")        # interpolated affine / perspective warps
 BLUR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_blur.h")        # GaussianBlur on uint8 frames
 CAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_cam.h")          # class activation maps + overlay
+DW_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ptx_amd_dw.h")            # depthwise 3-D convolution (CSN)
 
 PTX_EPI_RELU = 1
 PTX_EPI_RES_ADD = 2
@@ -540,6 +541,16 @@ SIGNATURES_CAM = {
     "ptx_cam_overlay": (C.c_int, [C.POINTER(CamOverlayDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# include/ptx_amd_dw.h: the fp32 depthwise 3-D convolution of the channel-separated networks (csrc/conv_dw_f32.h), bound the same
+# way (tests/test_csn_host.py)
+SIGNATURES_DW = {
+    "ptx_conv3d_dw_f32_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "ptx_pack_dw_weight_f32": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P]),
+    "ptx_conv3d_dw_f32_fwd": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P]),
+    "ptx_conv3d_dw_f32_force_form": (C.c_int, [_I]),
+}
+PTX_DW_FORM_STRIP4, PTX_DW_FORM_STRIP8, PTX_DW_FORM_LDS = 4, 8, 16
+
 
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/ptx_amd.h (used by the no-GPU ABI test)."""
@@ -578,7 +589,8 @@ def lib():
                 list(SIGNATURES_YUV16.items()) + list(SIGNATURES_COLOR.items()) + list(SIGNATURES_RANDAUG.items()) + \
                 list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_MIX.items()) + list(SIGNATURES_STEM_STRIDED.items()) + \
                 list(SIGNATURES_NL_KS.items()) + list(SIGNATURES_LINEAR_BF16.items()) + list(SIGNATURES_BN.items()) + \
-                list(SIGNATURES_WARP.items()) + list(SIGNATURES_BLUR.items()) + list(SIGNATURES_CAM.items()):
+                list(SIGNATURES_WARP.items()) + list(SIGNATURES_BLUR.items()) + list(SIGNATURES_CAM.items()) + \
+                list(SIGNATURES_DW.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is missing: loud by design
             fn.restype = res
             fn.argtypes = args

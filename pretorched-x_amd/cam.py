@@ -23,8 +23,8 @@ from . import _lib
 from ._lib import PtxError, check
 from .steps import _dense16, _ptr, _stream
 
-SUPPORTED = ("the VideoResNet families (3-D, (2+1)D, ResNeXt / wide / pre-activation / multi-view, the non-local nets and the "
-             "2-D ResNets) with an nn.Linear head")
+SUPPORTED = ("the VideoResNet families (3-D, (2+1)D, ResNeXt / wide / pre-activation / multi-view, the non-local nets, the "
+             "channel-separated nets and the 2-D ResNets) with an nn.Linear head")
 
 CamResult = collections.namedtuple("CamResult", ("logits", "classes", "scores", "maps", "frames"))
 CamResult.__doc__ = """What `model.cam` / `model.cam_frames` return.

@@ -23,14 +23,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 SOURCES = ["conv_igemm.hip", "conv_chain.hip", "conv_program.hip", "pack_layout.hip", "pool_head.hip", "nonlocal_attn.hip",
            "conv_stem_x3.hip", "conv_stem_f32.hip", "conv_body_f32.hip", "gen_stage_f16.hip"]
-HEADERS = ["ptx_common.h", "conv_igemm_kernel.h", "conv_ws_kernel.h", "resize_common.h", "conv_stem_patch_f32.h", "color_jitter.h", "rand_augment.h", "batch_mix.h", "warp_frames.h", "blur_frames.h", "cam.h", os.path.join("..", "..", "include", "ptx_amd.h"),
+HEADERS = ["ptx_common.h", "conv_igemm_kernel.h", "conv_ws_kernel.h", "resize_common.h", "conv_stem_patch_f32.h", "color_jitter.h", "rand_augment.h", "batch_mix.h", "warp_frames.h", "blur_frames.h", "cam.h", "conv_dw_f32.h", os.path.join("..", "..", "include", "ptx_amd.h"),
            os.path.join("..", "..", "include", "ptx_amd_wino4.h"), os.path.join("..", "..", "include", "ptx_amd_tfir.h"),
            os.path.join("..", "..", "include", "ptx_amd_yuv16.h"), os.path.join("..", "..", "include", "ptx_amd_color.h"),
            os.path.join("..", "..", "include", "ptx_amd_randaug.h"), os.path.join("..", "..", "include", "ptx_amd_resample.h"),
            os.path.join("..", "..", "include", "ptx_amd_mix.h"), os.path.join("..", "..", "include", "ptx_amd_stem_strided.h"),
            os.path.join("..", "..", "include", "ptx_amd_nl_ks.h"), os.path.join("..", "..", "include", "ptx_amd_linear_bf16.h"),
            os.path.join("..", "..", "include", "ptx_amd_bn.h"), os.path.join("..", "..", "include", "ptx_amd_warp.h"),
-           os.path.join("..", "..", "include", "ptx_amd_blur.h"), os.path.join("..", "..", "include", "ptx_amd_cam.h")]
+           os.path.join("..", "..", "include", "ptx_amd_blur.h"), os.path.join("..", "..", "include", "ptx_amd_cam.h"),
+           os.path.join("..", "..", "include", "ptx_amd_dw.h")]
 LIB = os.path.join(PKG, "libptx_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
@@ -47,7 +48,7 @@ def source_hash():
     binary was built from (the .so travels prebuilt to the GPU box; VERDICT r3 #10)."""
     h = hashlib.sha256()
     files = sorted(f for f in os.listdir(HERE) if f.endswith((".hip", ".h")))
-    for path in [os.path.join(HERE, f) for f in files] + [os.path.join(HERE, "..", "..", "include", h) for h in ("ptx_amd.h", "ptx_amd_wino4.h", "ptx_amd_tfir.h", "ptx_amd_yuv16.h", "ptx_amd_color.h", "ptx_amd_randaug.h", "ptx_amd_resample.h", "ptx_amd_mix.h", "ptx_amd_stem_strided.h", "ptx_amd_nl_ks.h", "ptx_amd_linear_bf16.h", "ptx_amd_bn.h", "ptx_amd_warp.h", "ptx_amd_blur.h", "ptx_amd_cam.h")]:
+    for path in [os.path.join(HERE, f) for f in files] + [os.path.join(HERE, "..", "..", "include", h) for h in ("ptx_amd.h", "ptx_amd_wino4.h", "ptx_amd_tfir.h", "ptx_amd_yuv16.h", "ptx_amd_color.h", "ptx_amd_randaug.h", "ptx_amd_resample.h", "ptx_amd_mix.h", "ptx_amd_stem_strided.h", "ptx_amd_nl_ks.h", "ptx_amd_linear_bf16.h", "ptx_amd_bn.h", "ptx_amd_warp.h", "ptx_amd_blur.h", "ptx_amd_cam.h", "ptx_amd_dw.h")]:
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:
             h.update(f.read())

@@ -1166,3 +1166,7 @@ extern "C" int ptx_views_mean(const void* logits, float* y, int32_t N, int32_t V
 
 // ... and so are the batch-statistics BatchNorm passes (include/ptx_amd_bn.h: what update_bn runs).
 #include "bn_batch.hip"
+
+// ... and the depthwise 3-D convolution (include/ptx_amd_dw.h: the 3x3x3 conv of the channel-separated networks), one more
+// streaming kernel next to the pools.
+#include "conv_dw_f32.h"

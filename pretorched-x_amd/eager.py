@@ -130,7 +130,9 @@ def block(arch, blk, x):
             out = conv(blk.conv3, F.relu(blk.bn3(out)))
         return out + _residual(arch, blk, x)
     out = F.relu(blk.bn1(conv(blk.conv1, x)))
-    if arch.block in ("bottleneck", "resnext", "wide"):
+    if arch.block == "csn_ip":                          # ip-CSN: one more pointwise conv + BN, no ReLU, ahead of the depthwise conv
+        out = blk.bn2_pw(blk.conv2_pw(out))
+    if arch.block in ("bottleneck", "resnext", "wide", "csn_ir", "csn_ip"):
         out = F.relu(blk.bn2(conv(blk.conv2, out)))
         out = blk.bn3(conv(blk.conv3, out))
     else:

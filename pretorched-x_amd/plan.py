@@ -23,6 +23,7 @@ from ._lib import (ConvDesc, ConvFusedExt, ConvProgramInfo, ConvStage, NonlocalD
                    PTX_SPLITK_FUSED, PTX_STEM_SRC_BF16_NCDHW, PTX_STEM_SRC_U8_NTHWC, PtxError, check)
 from ._lib import BnApplyDesc
 from .steps import BnApplyStep, BnStatsStep, BnUpdateStep
+from .steps import DwConvStep, PackedDw
 from .steps import (Act, AltStep, ChainStep, ConvStep, Packed, PackedDual, PatchConvStep, ProgramStep, RawInput, StemBf16Step, StemF32Step, StemTfirStep, TFIR_SCHEMES, Wino4Step, WinoStep, _WinoExec,
                     StemStep, _ConcatRowsPack, _Ref, _device_ctx, _geom, _ptr, _r4, _r8, _r128, _same_geometry, _stem_ld, _stream,
                     _t3, _tag)
@@ -89,6 +90,8 @@ def check_batch_stats_scope(model):
         why = "it holds non-local blocks"
     elif arch.conv == "mv":
         why = "its convs are MultiViewConv"
+    elif arch.block.startswith("csn"):
+        why = "its 3x3x3 convs are depthwise (channel-separated)"
     if why is not None:
         raise PtxError("update_bn does not cover %s (%s): it runs %s" % (name, why, BATCH_STATS_SCOPE))
 
@@ -701,6 +704,8 @@ class Plan:
             kt, st_, pt = _geom(conv.temporal_conv)
             return self.conv(mid, self.pack(conv.temporal_conv, bn), st_, pt, relu=relu, res=res,
                              res_kind=res_kind, res_stride=res_stride, label=label + ".temporal", y=y)
+        if isinstance(conv, nn.Conv3d) and conv.groups > 1 and conv.groups == conv.in_channels == conv.out_channels:
+            return self.conv_dw(x, conv, bn, relu=relu, res=res, label=label, y=y)
         k, s, p = _geom(conv)
         same = bool(getattr(conv, "tf_same", False))       # I3D's Unit3D: explicit "SAME" padding
         fold = _foldable(conv, x)
@@ -717,6 +722,42 @@ class Plan:
             s, p = (s[0], s[1], 1), (p[0], p[1], 0)
         return self.conv(x, self.pack(conv, bn, fold), s, p, relu=relu, res=res, res_kind=res_kind,
                          res_stride=res_stride, label=label, y=y, same=same)
+
+    def conv_dw(self, x, conv, bn, relu=False, res=None, label="conv_dw", y=None):
+        """A depthwise nn.Conv3d (groups == in_channels == out_channels) + `bn` (+ ReLU): one ptx_conv3d_dw_f32_fwd launch on
+        its own tap-major pack (include/ptx_amd_dw.h).  fp32 whatever the plan's precision: an "x3" plan runs the same kernel."""
+        if self.bf16 or not isinstance(x, Act) or x.f16:
+            raise PtxError("%s: the depthwise conv runs on float32 channels-last activations only" % label)
+        if res is not None:
+            raise PtxError("%s: the depthwise conv takes no residual" % label)
+        key = ("dw", id(conv), id(bn))
+        if key not in self._pack_cache:
+            self._pack_cache[key] = PackedDw(self, conv, bn)
+            self.packs.append(self._pack_cache[key])
+        pk = self._pack_cache[key]
+        k, s, p = _geom(conv)
+        if x.C != pk.C:
+            raise PtxError("%s: a %d-channel depthwise conv on a %d-channel input" % (label, pk.C, x.C))
+        out = tuple((i + 2 * p_ - k_) // s_ + 1 for i, p_, k_, s_ in zip((x.T, x.H, x.W), p, k, s))
+        if y is None:
+            y = self.act(x.N, out[0], out[1], out[2], pk.C)
+        if (y.N, y.T, y.H, y.W, y.C) != (x.N,) + out + (pk.C,) or y.f16:
+            raise PtxError("%s: output target %s does not match the conv result %s" % (
+                label, (y.N, y.T, y.H, y.W, y.C), (x.N,) + out + (pk.C,)))
+        d = ConvDesc()
+        d.N, d.Ti, d.Hi, d.Wi, d.Ci, d.ldx = x.N, x.T, x.H, x.W, x.C, x.ld
+        (d.To, d.Ho, d.Wo), d.Co, d.ldy = out, pk.C, y.ld
+        (d.kT, d.kH, d.kW), (d.sT, d.sH, d.sW), (d.pT, d.pH, d.pW) = k, s, p
+        d.groups, d.flags = pk.C, (PTX_EPI_RELU if relu else 0)
+        if min(out) < 1 or not self.lib.ptx_conv3d_dw_f32_supported(C.byref(d)):
+            raise PtxError("%s: %s" % (label, self.lib.ptx_last_error().decode(errors="replace") if min(out) >= 1 else "empty output"))
+        st = DwConvStep()
+        st.d, st.x, st.w, st.b, st.y, st.label = d, _ptr(x.t), _ptr(pk.w), _ptr(pk.b), _ptr(y.t), label
+        npos = x.N * out[0] * out[1] * out[2]
+        st.macs = npos * pk.C * k[0] * k[1] * k[2]
+        st.hbm_bytes = 4 * pk.C * (x.N * x.S + npos)
+        self.steps.append(st)
+        return y
 
     def _conv_bn_batch(self, x, conv, bn, relu, res, res_kind, res_stride, label, y):
         """conv_bn of a batch-statistics plan: the raw conv (bn=None: no fold, no activation, no residual -- on whatever
@@ -1412,7 +1453,7 @@ class Plan:
             N, Cin, T, H, W = shp
         raw = RawInput(N, Cin, T, H, W, norm=self.norm)
         x = self.conv_bn(raw, model.conv1, model.bn1, relu=True, label="conv1")
-        if arch.dims == 2:
+        if arch.dims == 2 or arch.block.startswith("csn"):       # (the CSN stem keeps every frame: MaxPool3d((1,3,3), (1,2,2), (0,1,1)))
             x = self.maxpool(x, (1, 3, 3), (1, 2, 2), (0, 1, 1))
         else:
             x = self.maxpool(x, (3, 3, 3), (2, 2, 2), (1, 1, 1))
@@ -1429,6 +1470,8 @@ class Plan:
         s = blk.stride
         if arch.block.startswith("preact"):
             return self._block_preact(arch, blk, x, name)
+        if arch.block.startswith("csn"):
+            return self._block_csn(arch, blk, x, name, out)
         # (bf16 plans: shortcut B runs as its own conv + a fused residual add -- the dual-source GEMM is fp32 / x3 only)
         fuse = (self.fuse_shortcut and not self.bf16 and blk.has_shortcut and arch.shortcut == "B" and arch.block in ("bottleneck", "resnext", "wide")
                 and isinstance(blk.conv3, (nn.Conv3d, nn.Conv2d)) and isinstance(blk.downsample[0], (nn.Conv3d, nn.Conv2d)))
@@ -1478,6 +1521,26 @@ class Plan:
         if blk.has_nl:
             o = self.nonlocal_block(o, blk.nonlocalblock, name + ".nonlocalblock")
         return o
+
+    def _block_csn(self, arch, blk, x, name, out=None):
+        """A channel-separated bottleneck (Tran et al., ICCV 2019): conv1 1x1x1 + bn1 + ReLU -> [ip-CSN: conv2_pw 1x1x1 + bn2_pw]
+        -> conv2 DEPTHWISE 3x3x3 (the block's stride) + bn2 + ReLU -> conv3 1x1x1 + bn3 + residual + ReLU.  The pointwise convs
+        are the GEMMs every bottleneck runs -- shortcut B folded into conv3's K axis where the plan fuses shortcuts -- and the
+        depthwise conv is one streaming launch (conv_dw)."""
+        o = self.conv_bn(x, blk.conv1, blk.bn1, relu=True, label=name + ".conv1")
+        if arch.block == "csn_ip":
+            o = self.conv_bn(o, blk.conv2_pw, blk.bn2_pw, label=name + ".conv2_pw")
+        o = self.conv_bn(o, blk.conv2, blk.bn2, relu=True, label=name + ".conv2")
+        if blk.has_shortcut and self.fuse_shortcut and arch.shortcut == "B":
+            pk = self.pack_dual(blk.conv3, blk.bn3, blk.downsample[0], blk.downsample[1])
+            return self.conv(o, pk, (1, 1, 1), (0, 0, 0), relu=True, x2=x, x2_stride=_geom(blk.downsample[0])[1], y=out,
+                             label=name + ".conv3+downsample")
+        if blk.has_shortcut and arch.shortcut == "B":
+            res, kind = self.conv_bn(x, blk.downsample[0], blk.downsample[1], label=name + ".downsample"), None
+        else:
+            res, kind = x, ("padA" if blk.has_shortcut else None)
+        return self.conv_bn(o, blk.conv3, blk.bn3, relu=True, res=res, res_kind=kind, res_stride=blk.stride,
+                            label=name + ".conv3", y=out)
 
     def bn_relu(self, x, bn, label):
         """Eval-mode BN -> ReLU as one HBM pass ahead of a conv (pre-activation blocks): the BN is folded to

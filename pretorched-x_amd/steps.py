@@ -332,6 +332,43 @@ class PackedDual:
                   "ptx_pack_conv_weight (dual)")
 
 
+class PackedDw:
+    """BN-folded filter of a depthwise conv (groups == in_channels == out_channels), tap-major [kT*kH*kW][C], + fp32 bias: the
+    operands of ptx_conv3d_dw_f32_fwd (include/ptx_amd_dw.h); refreshable in place like `Packed`.  Always fp32 -- the launch has
+    nothing for the matrix cores, so a split-operand ("x3") plan packs it the same way."""
+
+    def __init__(self, plan, conv, bn):
+        self.plan = plan
+        self.convs, self.bn = [plan.ref(conv)], (plan.ref(bn) if bn is not None else None)
+        self.x3 = False                    # (what readers of plan.packs ask of every pack)
+        self.C = conv.out_channels
+        self.k_eff = _geom(conv)[0]
+        if self.C % 4:
+            raise PtxError("depthwise conv: %d channels -- the kernel takes multiples of 4" % self.C)
+        taps = self.k_eff[0] * self.k_eff[1] * self.k_eff[2]
+        self.w = torch.empty(taps * self.C, device=plan.dev, dtype=torch.float32)
+        self.b = torch.empty(self.C, device=plan.dev, dtype=torch.float32)
+
+    def refresh(self):
+        get = self.plan.get
+        conv, bn = get(self.convs[0]), (get(self.bn) if self.bn is not None else None)
+        w = conv.weight.detach().contiguous()
+        cb = conv.bias.detach().contiguous() if conv.bias is not None else None
+        if w.dtype != torch.float32 or not w.is_cuda:
+            raise PtxError("weights must be fp32 CUDA tensors on the plan's device")
+        null = C.c_void_p(0)
+        args, eps, keep = [null] * 4, 0.0, [w, cb]
+        if bn is not None:
+            ts = [t.contiguous() for t in (bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var)]
+            keep += ts
+            args, eps = [_ptr(t) for t in ts], float(bn.eps)
+        kT, kH, kW = self.k_eff
+        check(_lib.lib().ptx_pack_dw_weight_f32(self.C, kT, kH, kW, _ptr(w), _ptr(cb) if cb is not None else null, args[0], args[1],
+                                                args[2], args[3], C.c_float(eps), _ptr(self.w), _ptr(self.b), _stream()),
+              "ptx_pack_dw_weight_f32")
+        return keep
+
+
 def _tile_dims(name):
     """(BM, BN, BK) of an MFMA tile configuration name ("32x64x64/2x2/m16/dma/re"), or None for the direct (VALU) tiles."""
     m = re.match(r"^(\d+)x(\d+)x(\d+)/", name)
@@ -448,6 +485,17 @@ class ConvStep(_Step):
         else:
             check(_lib.lib().ptx_conv3d_fwd(C.byref(self.d), self.x, self.w, self.b, self.res, self.y,
                                             p.ws_ptr, p.ws_bytes, self.cfg, self.split, st), self.label)
+
+
+class DwConvStep(_Step):
+    """One ptx_conv3d_dw_f32_fwd launch (include/ptx_amd_dw.h): a depthwise conv + folded BN (+ ReLU).  A plain streaming launch:
+    no tile, no split, no workspace -- it is not part of Plan.conv_steps, so the tuner, the Winograd forms and the body-kernel
+    selection never see it; `macs` / `hbm_bytes` (compulsory reads + writes) feed the per-launch rows like a tagged closure's."""
+    __slots__ = ("d", "x", "w", "b", "y", "label", "macs", "hbm_bytes")
+    kernel = "conv_dw_f32"
+
+    def __call__(self, st):
+        check(_lib.lib().ptx_conv3d_dw_f32_fwd(C.byref(self.d), self.x, self.w, self.b, self.y, st), self.label)
 
 
 class ChainStep(_Step):

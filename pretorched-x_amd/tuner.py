@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import PtxError
+from .steps import DwConvStep
 from .steps import (AltStep, ChainStep, ConvStep, PatchConvStep, ProgramStep, StemBf16Step, StemF32Step, StemStep, StemTfirStep, _WinoExec, _dense16,
                     _r4, _stream, issued_conv_flop)
 from .tuned import (BODY_SHAPES, _flags_kind, _tile_kind, alt_lookup, alt_store, body_lookup, body_store, chain_lookup,
@@ -532,7 +533,7 @@ def profile_steps(engine, plan, iters=5, isolated=None):
             rows.append((stp.label, "chain", 0, stp.macs, ms, stp.kernel))
         else:                                               # a tagged closure (steps._tag), or a caller's own callable
             nb, macs = getattr(stp, "hbm_bytes", 0), getattr(stp, "macs", 0)
-            kind = "mem" if nb and not macs else "mfma" if macs else "other"
+            kind = "mem" if nb and (not macs or isinstance(stp, DwConvStep)) else "mfma" if macs else "other"       # (depthwise: streaming)
             rows.append((getattr(stp, "label", getattr(stp, "__name__", "step")), kind, nb, macs, ms, ""))
     return rows
 

@@ -40,10 +40,11 @@ class Arch:
     dims: int = 3
     cardinality: int = 32            # 'resnext' blocks only (resnext3D.py:126)
     k: int = 1                       # 'wide' blocks only: width multiplier (wideresnet3D.py:113)
+    bn_eps: float = 1e-5             # eps of every BatchNorm the builder creates (the CSN family: 1e-3)
 
     @property
     def expansion(self):
-        return {"bottleneck": 4, "resnext": 2, "wide": 2, "preact_bottleneck": 4}.get(self.block, 1)
+        return {"bottleneck": 4, "resnext": 2, "wide": 2, "preact_bottleneck": 4, "csn_ir": 4, "csn_ip": 4}.get(self.block, 1)
 
     @property
     def widths(self):
@@ -97,6 +98,16 @@ ARCHS = {
     "mvresnet101": Arch("bottleneck", (3, 4, 23, 3), "B", conv="mv", head="fc"),
     "mvresnet152": Arch("bottleneck", (3, 8, 36, 3), "B", conv="mv", head="fc"),
     "mvresnet200": Arch("bottleneck", (3, 24, 36, 3), "B", conv="mv", head="fc"),
+    # channel-separated networks (Tran et al., "Video Classification with Channel-Separated Convolutional Networks", ICCV 2019):
+    # a ResNet3D bottleneck whose 3x3x3 conv is DEPTHWISE (ir-CSN), optionally behind one more 1x1x1 conv (ip-CSN); the stem keeps
+    # every frame ((3,7,7) conv, (1,3,3) pool), every stage after the first halves T, H and W.  Builder-defined, like I3D: the
+    # reference snapshot has no CSN source
+    "ir_csn50": Arch("csn_ir", (3, 4, 6, 3), "B", bn_eps=1e-3),
+    "ir_csn101": Arch("csn_ir", (3, 4, 23, 3), "B", bn_eps=1e-3),
+    "ir_csn152": Arch("csn_ir", (3, 8, 36, 3), "B", bn_eps=1e-3),
+    "ip_csn50": Arch("csn_ip", (3, 4, 6, 3), "B", bn_eps=1e-3),
+    "ip_csn101": Arch("csn_ip", (3, 4, 23, 3), "B", bn_eps=1e-3),
+    "ip_csn152": Arch("csn_ip", (3, 8, 36, 3), "B", bn_eps=1e-3),
     "resnet18": Arch("basic", (2, 2, 2, 2), "B", dims=2),
     "resnet34": Arch("basic", (3, 4, 6, 3), "B", dims=2),
     "resnet50": Arch("bottleneck", (3, 4, 6, 3), "B", dims=2),
@@ -191,7 +202,7 @@ def _conv(arch, cin, cout, k, stride=1, padding=0, bias=False):
 
 
 def _bn(arch, c):
-    return nn.BatchNorm2d(c) if arch.dims == 2 else nn.BatchNorm3d(c)
+    return nn.BatchNorm2d(c, eps=arch.bn_eps) if arch.dims == 2 else nn.BatchNorm3d(c, eps=arch.bn_eps)
 
 
 def _nonlocal(channels):
@@ -328,6 +339,16 @@ def _block(arch, cin, planes, stride, with_down, with_nl):
         blk.bn2 = nn.BatchNorm3d(planes)
         blk.conv3 = nn.Conv3d(planes, planes * 2, 1, bias=False)
         blk.bn3 = nn.BatchNorm3d(planes * 2)
+    elif arch.block in ("csn_ir", "csn_ip"):     # the bottleneck with a depthwise 3x3x3 (ip-CSN: behind one more pointwise conv)
+        blk.conv1 = nn.Conv3d(cin, planes, 1, bias=False)
+        blk.bn1 = _bn(arch, planes)
+        if arch.block == "csn_ip":
+            blk.conv2_pw = nn.Conv3d(planes, planes, 1, bias=False)
+            blk.bn2_pw = _bn(arch, planes)
+        blk.conv2 = nn.Conv3d(planes, planes, 3, stride, 1, groups=planes, bias=False)
+        blk.bn2 = _bn(arch, planes)
+        blk.conv3 = nn.Conv3d(planes, planes * 4, 1, bias=False)
+        blk.bn3 = _bn(arch, planes * 4)
     elif arch.block == "bottleneck":
         blk.conv1 = _conv(arch, cin, planes, 1)
         blk.bn1 = _bn(arch, planes)
@@ -365,14 +386,18 @@ class VideoResNet(EngineOwner, nn.Module):
         arch = ARCHS[arch_name]
         self.arch_name = arch_name
         self.arch = arch
+        csn = arch.block.startswith("csn")
         if arch.dims == 2:
             self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        elif csn:                                # the stem keeps every frame
+            self.conv1 = nn.Conv3d(3, 64, (3, 7, 7), (1, 2, 2), (1, 3, 3), bias=False)
         else:
             self.conv1 = _conv(arch, 3, 64, 7, (1, 2, 2), (3, 3, 3))
         self.bn1 = _bn(arch, 64)
         # parameterless members of the reference trees, kept for structural familiarity only
         self.relu = nn.ReLU(inplace=True)
-        self.maxpool = (nn.MaxPool2d(3, 2, 1) if arch.dims == 2 else nn.MaxPool3d(3, 2, 1))
+        self.maxpool = (nn.MaxPool2d(3, 2, 1) if arch.dims == 2 else nn.MaxPool3d((1, 3, 3), (1, 2, 2), (0, 1, 1)) if csn
+                        else nn.MaxPool3d(3, 2, 1))
         cin = 64
         for li, (planes, nblocks) in enumerate(zip(arch.widths, arch.layers)):
             stride = 1 if li == 0 else 2
