@@ -193,6 +193,8 @@ extern "C" int ptx_conv3d_chain_fwd(const ptx_conv3d_desc* conv, const ptx_conv3
     if ((tail->flags & PTX_EPI_RES_ADD) && !res) return fail(PTX_ERR_INVALID, "conv3d_chain: residual flag set but res == NULL");
     if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)w2_packed | (uintptr_t)y | (uintptr_t)res) & 15)
         return fail(PTX_ERR_INVALID, "conv3d_chain: pointers must be 16-byte aligned");
+    if ((uintptr_t)bias2 & 15)            // the tail's row-major epilogue reads four biases with one 16-byte load (bias: scalar loads)
+        return fail(PTX_ERR_INVALID, "conv3d_chain: bias2 must be 16-byte aligned");
     if (config < 0) config = ptx_conv3d_chain_pick_config(conv, tail);
     if (config < 0 || config >= kNumChain || !ptx_conv3d_chain_supported(conv, tail, config))
         return fail(PTX_ERR_UNSUPPORTED, "conv3d_chain: no chained tile holds %d intermediate channels (config %d)", conv->Co, config);

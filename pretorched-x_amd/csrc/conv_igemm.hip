@@ -929,6 +929,8 @@ int make_conv_args(const ptx_conv3d_desc* d, const float* x, const float* x2, co
         return fail(PTX_ERR_INVALID, "conv3d: residual flag set but res == NULL");
     if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)res) & 15)
         return fail(PTX_ERR_INVALID, "conv3d: pointers must be 16-byte aligned");
+    // the row-major epilogues, the direct kernel and the split-K reduction read four biases with one 16-byte load
+    if ((uintptr_t)bias & 15) return fail(PTX_ERR_INVALID, "conv3d: bias must be 16-byte aligned");
     if (d->flags & PTX_PRO_RELU)
         return fail(PTX_ERR_UNSUPPORTED, "conv3d: PTX_PRO_RELU is only implemented by ptx_linear_fwd");
     if (d->flags & PTX_EPI_RES_ADD) {

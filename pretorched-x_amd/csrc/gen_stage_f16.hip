@@ -930,6 +930,8 @@ static int c3_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed,
     if ((d->flags & PTX_EPI_AFFINE) && (!ext || !ext->scale || !ext->shift || ext->ld_affine < d->Co || ext->ld_affine % 4))
         return fail(PTX_ERR_INVALID, "%s: PTX_EPI_AFFINE needs scale / shift tables with a row stride that is a multiple of 4", nm);
     if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)bias) & 15) return fail(PTX_ERR_INVALID, "%s: misaligned pointer", nm);
+    if ((d->flags & PTX_EPI_AFFINE) && (((uintptr_t)ext->scale | (uintptr_t)ext->shift) & 15))       // read four channels per load
+        return fail(PTX_ERR_INVALID, "%s: PTX_EPI_AFFINE needs 16-byte aligned scale / shift tables", nm);
     const bool up2 = (d->flags & PTX_PRO_UP2) != 0;
     C3Args a{};
     a.x = static_cast<const _Float16*>(x); a.w = static_cast<const _Float16*>(w_packed); a.bias = bias;
@@ -1023,6 +1025,8 @@ static int c1_fwd(const ptx_conv3d_desc* d, const void* x, const void* w_packed,
         return fail(PTX_ERR_INVALID, "%s: PTX_EPI_DUAL_RAW needs ext->y_raw with a row stride that is a multiple of 8 elements", nm);
     if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)(ext ? ext->y_raw : nullptr)) & 15)
         return fail(PTX_ERR_INVALID, "%s: misaligned pointer", nm);
+    if ((d->flags & PTX_EPI_AFFINE) && (((uintptr_t)ext->scale | (uintptr_t)ext->shift) & 15))       // read four channels per load
+        return fail(PTX_ERR_INVALID, "%s: PTX_EPI_AFFINE needs 16-byte aligned scale / shift tables", nm);
     if ((d->flags & PTX_EPI_DUAL_RAW) && (uint64_t)d->N * d->Hi * d->Wi * ext->ld_raw * 2ull >= 0x80000000ull)
         return fail(PTX_ERR_UNSUPPORTED, "%s: the raw output of one launch must be < 2 GiB", nm);
     C1Args a{};
@@ -1109,6 +1113,8 @@ extern "C" int ptx_conv1x1_pro_f16_fwd(const ptx_conv3d_desc* d, const void* x, 
         return fail(PTX_ERR_INVALID, "conv1x1_pro_f16: PTX_EPI_AFFINE needs scale / shift tables with a row stride that is a multiple of 4");
     if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)ext_in->scale | (uintptr_t)ext_in->shift) & 15)
         return fail(PTX_ERR_INVALID, "conv1x1_pro_f16: misaligned pointer");
+    if ((d->flags & PTX_EPI_AFFINE) && (((uintptr_t)ext->scale | (uintptr_t)ext->shift) & 15))       // read four channels per load
+        return fail(PTX_ERR_INVALID, "conv1x1_pro_f16: PTX_EPI_AFFINE needs 16-byte aligned scale / shift tables");
     P1Args a{};
     a.x = static_cast<const _Float16*>(x); a.w = static_cast<const _Float16*>(w_packed); a.bias = bias;
     a.scale1 = ext_in->scale; a.shift1 = ext_in->shift; a.ld1 = ext_in->ld_affine;
