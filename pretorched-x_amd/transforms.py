@@ -80,6 +80,68 @@ def _opt(opts, key):
     return opts[key] if isinstance(opts, dict) else getattr(opts, key)
 
 
+# ---------------------------------------------------------------------------------------------
+# The front door of every transform, in small steps that each __call__ puts in its own order; `who` names the caller
+# ---------------------------------------------------------------------------------------------
+def _frames_shape(frames, who):
+    """(N, T, H, W) of frames [N,T,H,W,3] | [T,H,W,3] | [H,W,3] (a missing N or T is 1), or PtxError: type, rank, channels."""
+    if not isinstance(frames, torch.Tensor):
+        raise PtxError("%s: frames must be a uint8 CUDA tensor, got %s" % (who, type(frames).__name__))
+    if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
+        raise PtxError("%s: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (who, tuple(frames.shape)))
+    return (1,) * (5 - frames.dim()) + tuple(int(n) for n in frames.shape[:-1])
+
+
+def _check_not_empty(x, who):
+    if x.numel() == 0:
+        raise PtxError("%s: empty batch" % who)
+
+
+def _u8_cuda_5d(frames, who):
+    """The contiguous [N,T,H,W,C] view of uint8 CUDA frames of rank 3, 4 or 5, or PtxError."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
+        raise PtxError("%s: frames must be a uint8 CUDA tensor (no CPU fallback)" % who)
+    return frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
+
+
+def _check_generator(generator, who, name="generator"):
+    if generator is not None and not isinstance(generator, torch.Generator):
+        raise PtxError("%s: %s must be a torch.Generator or None, got %r" % (who, name, generator))
+    return generator
+
+
+def _host_array(a, cuda_message):
+    """An array or a CPU tensor as a numpy array; a CUDA tensor raises PtxError(cuda_message)."""
+    if isinstance(a, torch.Tensor):
+        if a.is_cuda:
+            raise PtxError(cuda_message)
+        a = a.numpy()
+    return np.asarray(a)
+
+
+def _out_mode(dtype, out="tensor"):
+    """The PTX_RESIZE_OUT_* code of a call's output: uint8 frames, or the normalised clip of `dtype`."""
+    if out == "frames":
+        return _lib.PTX_RESIZE_OUT_U8
+    return _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
+
+
+def _alloc_out(mode, N, T, H, W, device, dtype):
+    """The output of a launch by mode: uint8 [N,T,H,W,3], or [N,3,T,H,W] of `dtype`."""
+    if mode == _lib.PTX_RESIZE_OUT_U8:
+        return torch.empty((N, T, H, W, 3), device=device, dtype=torch.uint8)
+    return torch.empty((N, 3, T, H, W), device=device, dtype=dtype)
+
+
+def _restore_rank(y, lead, mode):
+    """A 5-D output as the result of a call on frames of rank `lead`: the leading dimensions added for the launch go."""
+    if mode == _lib.PTX_RESIZE_OUT_U8:
+        return y.view(tuple(y.shape[5 - lead:]))
+    if lead == 5:
+        return y
+    return y[0] if lead == 4 else y[0, :, 0]
+
+
 class FramesToTensor:
     """opts: a model (after `pretrained=...`) or a `pretrained_settings[...]` dict -- anything with
     input_space / input_range / mean / std, as TransformImage takes (utils.py:36-45)."""
@@ -91,12 +153,9 @@ class FramesToTensor:
 
     def __call__(self, frames):
         """uint8 CUDA frames [N,T,H,W,C] | [T,H,W,C] | [H,W,C]  ->  fp32 [N,C,T,H,W] | [C,T,H,W] | [C,H,W]."""
-        if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
-            raise PtxError("FramesToTensor: frames must be a uint8 CUDA tensor (no CPU fallback)")
+        f5 = _u8_cuda_5d(frames, "FramesToTensor")
         if frames.dim() not in (3, 4, 5):
             raise PtxError("FramesToTensor: expected [N,T,H,W,C], [T,H,W,C] or [H,W,C]")
-        lead = frames.dim()
-        f5 = frames.contiguous().view((1,) * (5 - lead) + tuple(frames.shape))
         N, T, H, W, Cc = f5.shape
         with torch.cuda.device(frames.device):
             out = torch.empty((N, Cc, T, H, W), device=frames.device, dtype=torch.float32)
@@ -104,9 +163,7 @@ class FramesToTensor:
                                                     Cc, C.byref(self.norm),
                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                   "ptx_frames_u8_to_ncdhw")
-        if lead == 5:
-            return out
-        return out[0] if lead == 4 else out[0, :, 0]
+        return _restore_rank(out, frames.dim(), _lib.PTX_RESIZE_OUT_F32)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -870,11 +927,7 @@ def _color_rows(ops, N=None, who="ColorJitter"):
         raise PtxError("%s: params must be a pair (codes [N, %d], factors [N, %d]), got %r" % (who, COLOR_MAX_OPS, COLOR_MAX_OPS, type(ops).__name__))
     arrs = []
     for name, a, kinds in (("codes", codes, "iu"), ("factors", factors, "fiu")):
-        if isinstance(a, torch.Tensor):
-            if a.is_cuda:
-                raise PtxError("%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
-            a = a.numpy()
-        a = np.asarray(a)
+        a = _host_array(a, "%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
         if a.dtype.kind not in kinds:
             raise PtxError("%s: params %s must hold %s, got dtype %s" % (who, name, "integers" if kinds == "iu" else "numbers", a.dtype))
         if a.ndim != 2 or a.shape[1] != COLOR_MAX_OPS:
@@ -954,9 +1007,7 @@ class ColorJitter:
         if isinstance(grayscale, bool) or not isinstance(grayscale, (int, float)) or not 0.0 <= grayscale <= 1.0:
             raise PtxError("ColorJitter: grayscale must be a probability in [0, 1], got %r" % (grayscale,))
         self.grayscale = float(grayscale)
-        if generator is not None and not isinstance(generator, torch.Generator):
-            raise PtxError("ColorJitter: generator must be a torch.Generator or None, got %r" % (generator,))
-        self.generator, self.last_params, self.last_launches = generator, None, ()
+        self.generator, self.last_params, self.last_launches = _check_generator(generator, "ColorJitter"), None, ()
 
     @staticmethod
     def _range(value, name, center=1.0, bound=(0.0, float("inf")), clip=True):
@@ -1006,7 +1057,7 @@ class ColorJitter:
         """See `check_color_params`."""
         return check_color_params(params, N)
 
-    def _launch(self, f5, params, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+    def _launch(self, f5, params, mode, norm, dtype):
         """The launches on contiguous uint8 CUDA frames f5 [N,T,H,W,3] with checked params: uint8 [N,T,H,W,3] or the
         normalised [N,3,T,H,W] of `dtype`."""
         codes, factors = params
@@ -1023,57 +1074,26 @@ class ColorJitter:
                 sums = torch.empty(N * T, device=f5.device, dtype=torch.int64)
                 check(lib.ptx_color_jitter_stats(C.byref(desc), C.c_void_p(f5.data_ptr()), ops_p, fac_p, C.c_void_p(sums.data_ptr()),
                                                  stream), "ptx_color_jitter_stats")
-            if mode == _lib.PTX_RESIZE_OUT_U8:
-                y = torch.empty((N, T, H, W, 3), device=f5.device, dtype=torch.uint8)
-            else:
-                y = torch.empty((N, 3, T, H, W), device=f5.device, dtype=dtype)
+            y = _alloc_out(mode, N, T, H, W, f5.device, dtype)
             check(lib.ptx_color_jitter_apply(C.byref(desc), C.c_void_p(f5.data_ptr()), ops_p, fac_p,
                                              C.c_void_p(sums.data_ptr()) if contrast else None, C.c_void_p(y.data_ptr()),
                                              C.byref(norm) if norm is not None else None, stream), "ptx_color_jitter_apply")
         self.last_launches = ("stats", "apply") if contrast else ("apply",)
         return y
 
-    def _params_for(self, N, params):
+    def _run(self, f5, params, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+        """The stage on contiguous uint8 frames f5 [N,T,H,W,3]: `params`, or a draw that is kept as `last_params`; see `_launch`."""
         if params is None:
-            self.last_params = self.draw(N)
-            return self.check_params(self.last_params, N)
-        return self.check_params(params, N)
+            params = self.last_params = self.draw(f5.shape[0])
+        return self._launch(f5, self.check_params(params, f5.shape[0]), mode, norm, dtype)
 
     def __call__(self, frames, params=None):
-        if not isinstance(frames, torch.Tensor):
-            raise PtxError("ColorJitter: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
-        if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
-            raise PtxError("ColorJitter: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (tuple(frames.shape),))
-        N = frames.shape[0] if frames.dim() == 5 else 1
+        N = _frames_shape(frames, "ColorJitter")[0]
         if params is not None:                                       # validated before a device is touched
             params = self.check_params(params, N)
-        if not frames.is_cuda or frames.dtype != torch.uint8:
-            raise PtxError("ColorJitter: frames must be a uint8 CUDA tensor (no CPU fallback)")
-        if frames.numel() == 0:
-            raise PtxError("ColorJitter: empty batch")
-        f5 = frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
-        return self._launch(f5, self._params_for(N, params)).view(frames.shape)
-
-
-def _apply_color(color, frames_u8, out, dtype, norm, color_params):
-    """The colour half of TransformFrames / SampleClips with color=: `frames_u8` is the resize's uint8 output ([N,T,S,S,3] or
-    a lower rank, one clip), the result the requested output of the call."""
-    lead = frames_u8.dim()
-    f5 = frames_u8.view((1,) * (5 - lead) + tuple(frames_u8.shape))
-    p = color._params_for(f5.shape[0], color_params)
-    if out == "frames":
-        return color._launch(f5, p).view(frames_u8.shape)
-    mode = _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
-    y = color._launch(f5, p, mode, norm, dtype)
-    if lead == 5:
-        return y
-    return y[0] if lead == 4 else y[0, :, 0]
-
-
-def _check_color(color, who):
-    if color is not None and not isinstance(color, ColorJitter):
-        raise PtxError("%s: color must be a pretorched.transforms.ColorJitter or None, got %r" % (who, color))
-    return color
+        f5 = _u8_cuda_5d(frames, "ColorJitter")
+        _check_not_empty(frames, "ColorJitter")
+        return self._run(f5, params).view(frames.shape)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1122,11 +1142,7 @@ def _blur_rows(apply, wx, wy, N, who):
     """(apply int32 [N], wx float32 [N, kx], wy float32 [N, ky]) as contiguous numpy arrays; a 1-D weight row serves every clip."""
     arrs = []
     for name, a in (("apply", apply), ("wx", wx), ("wy", wy)):
-        if isinstance(a, torch.Tensor):
-            if a.is_cuda:
-                raise PtxError("%s: %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
-            a = a.numpy()
-        arrs.append(np.asarray(a))
+        arrs.append(_host_array(a, "%s: %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name)))
     ap, wx, wy = arrs
     if ap.dtype.kind not in "iub" or ap.ndim != 1 or ap.shape[0] != N:
         raise PtxError("%s: apply must hold N = %d integer flags, got dtype %s shape %s" % (who, N, ap.dtype, ap.shape))
@@ -1229,9 +1245,7 @@ class GaussianBlur:
         if p is not None and (isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0):
             raise PtxError("GaussianBlur: p must be None or a probability in [0, 1], got %r" % (p,))
         self.p = None if p is None else float(p)
-        if generator is not None and not isinstance(generator, torch.Generator):
-            raise PtxError("GaussianBlur: generator must be a torch.Generator or None, got %r" % (generator,))
-        self.generator, self.last_params = generator, None
+        self.generator, self.last_params = _check_generator(generator, "GaussianBlur"), None
 
     def draw(self, n):
         """The draw of n clips: (apply CPU int32 [n], sigma CPU float64 [n]).  Per clip, in clip order, from `generator`: with p
@@ -1273,11 +1287,7 @@ class GaussianBlur:
             raise PtxError("GaussianBlur: params must be a pair (apply [N], sigma [N]), got %r" % (params,))
         arrs = []
         for name, a in (("apply", apply), ("sigma", sigma)):
-            if isinstance(a, torch.Tensor):
-                if a.is_cuda:
-                    raise PtxError("GaussianBlur: params: %s must be an array or a CPU tensor, got a CUDA tensor" % name)
-                a = a.numpy()
-            arrs.append(np.asarray(a))
+            arrs.append(_host_array(a, "GaussianBlur: params: %s must be an array or a CPU tensor, got a CUDA tensor" % name))
         ap, sg = arrs
         if ap.dtype.kind not in "iu" or ap.ndim != 1:
             raise PtxError("GaussianBlur: params: apply must be [N] integers, got dtype %s shape %s" % (ap.dtype, ap.shape))
@@ -1306,7 +1316,11 @@ class GaussianBlur:
             return self.check_params(self.last_params, N, H, W)
         return self.check_params(params, N, H, W)
 
-    def _launch(self, f5, params, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+    def _run(self, f5, params, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+        """The stage on contiguous uint8 frames f5 [N,T,H,W,3]: `params`, or a draw that is kept as `last_params`; see `_launch`."""
+        return self._launch(f5, self._params_for(f5.shape[0], f5.shape[2], f5.shape[3], params), mode, norm, dtype)
+
+    def _launch(self, f5, params, mode, norm, dtype):
         """The launch on contiguous uint8 CUDA frames f5 [N,T,H,W,3] with checked params: uint8 [N,T,H,W,3] or the normalised
         [N,3,T,H,W] of `dtype`."""
         N, T, H, W, _ = f5.shape
@@ -1316,10 +1330,7 @@ class GaussianBlur:
             rows = torch.cat([params[0].reshape(-1).view(torch.uint8), wx.reshape(-1).view(torch.uint8),
                               wy.reshape(-1).view(torch.uint8)]).to(f5.device)                       # one upload
             base = rows.data_ptr()
-            if mode == _lib.PTX_RESIZE_OUT_U8:
-                y = torch.empty((N, T, H, W, 3), device=f5.device, dtype=torch.uint8)
-            else:
-                y = torch.empty((N, 3, T, H, W), device=f5.device, dtype=dtype)
+            y = _alloc_out(mode, N, T, H, W, f5.device, dtype)
             desc = _lib.BlurDesc(N, T, H, W, kx, ky, mode)
             check(_lib.lib().ptx_gaussian_blur_frames(C.byref(desc), C.c_void_p(f5.data_ptr()), C.c_void_p(base),
                                                       C.c_void_p(base + 4 * N), C.c_void_p(base + 4 * N * (1 + kx)),
@@ -1328,47 +1339,15 @@ class GaussianBlur:
         return y
 
     def __call__(self, frames, params=None):
-        if not isinstance(frames, torch.Tensor):
-            raise PtxError("GaussianBlur: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
-        if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
-            raise PtxError("GaussianBlur: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (tuple(frames.shape),))
-        N, H, W = (frames.shape[0] if frames.dim() == 5 else 1), frames.shape[-3], frames.shape[-2]
-        if frames.numel() == 0:
-            raise PtxError("GaussianBlur: empty batch")
+        N, _, H, W = _frames_shape(frames, "GaussianBlur")
+        _check_not_empty(frames, "GaussianBlur")
         kx, ky = self.kernel_size
         if kx // 2 >= W or ky // 2 >= H:                             # before a draw and before a device is touched
             raise PtxError("GaussianBlur: kernel_size=(%d, %d) does not fit frames of H=%d, W=%d: reflect padding needs "
                            "kx // 2 < W and ky // 2 < H (torch raises there too)" % (kx, ky, H, W))
         if params is not None:                                       # validated before a device is touched
             params = self.check_params(params, N, H, W)
-        if not frames.is_cuda or frames.dtype != torch.uint8:
-            raise PtxError("GaussianBlur: frames must be a uint8 CUDA tensor (no CPU fallback)")
-        f5 = frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
-        return self._launch(f5, self._params_for(N, H, W, params)).view(frames.shape)
-
-
-def _apply_blur(blur, frames_u8, out, dtype, norm, blur_params):
-    """The blur stage of TransformFrames / SampleClips with blur=: `frames_u8` is the uint8 output of the stage in front
-    ([N,T,S,S,3] or a lower rank, one clip), the result the requested output of the call."""
-    lead = frames_u8.dim()
-    f5 = frames_u8.view((1,) * (5 - lead) + tuple(frames_u8.shape))
-    p = blur._params_for(f5.shape[0], f5.shape[2], f5.shape[3], blur_params)
-    if out == "frames":
-        return blur._launch(f5, p).view(frames_u8.shape)
-    mode = _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
-    y = blur._launch(f5, p, mode, norm, dtype)
-    if lead == 5:
-        return y
-    return y[0] if lead == 4 else y[0, :, 0]
-
-
-def _check_blur(blur, size, who):
-    if blur is not None and not isinstance(blur, GaussianBlur):
-        raise PtxError("%s: blur must be a pretorched.transforms.GaussianBlur or None, got %r" % (who, blur))
-    if blur is not None and max(blur.kernel_size) // 2 >= size:
-        raise PtxError("%s: blur: kernel_size=%r does not fit the %dx%d output (H=%d, W=%d): reflect padding needs "
-                       "kernel_size // 2 < H, W" % (who, blur.kernel_size, size, size, size, size))
-    return blur
+        return self._run(_u8_cuda_5d(frames, "GaussianBlur"), params).view(frames.shape)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1465,11 +1444,7 @@ def _randaug_params(params, N=None, who="RandAugment"):
         raise PtxError("%s: params must be a pair (codes [N, num_ops], magnitudes [N, num_ops]), got %r" % (who, type(params).__name__))
     arrs = []
     for name, a, kinds in (("codes", codes, "iu"), ("magnitudes", mags, "fiu")):
-        if isinstance(a, torch.Tensor):
-            if a.is_cuda:
-                raise PtxError("%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
-            a = a.numpy()
-        a = np.asarray(a)
+        a = _host_array(a, "%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
         if a.dtype.kind not in kinds:
             raise PtxError("%s: params %s must hold %s, got dtype %s" % (who, name, "integers" if kinds == "iu" else "numbers", a.dtype))
         if a.ndim != 2 or not 1 <= a.shape[1] <= RANDAUG_MAX_OPS:
@@ -1697,8 +1672,7 @@ class RandAugment:
             raise PtxError("RandAugment: num_magnitude_bins must be at least 2, got %d" % num_magnitude_bins)
         if not 0 <= magnitude < num_magnitude_bins:
             raise PtxError("RandAugment: magnitude must be a bin 0..%d, got %d" % (num_magnitude_bins - 1, magnitude))
-        if generator is not None and not isinstance(generator, torch.Generator):
-            raise PtxError("RandAugment: generator must be a torch.Generator or None, got %r" % (generator,))
+        _check_generator(generator, "RandAugment")
         self.num_ops, self.magnitude, self.num_magnitude_bins = num_ops, magnitude, num_magnitude_bins
         self.fill = _randaug_fill(fill)
         self.interpolation = check_warp_interpolation(interpolation, "RandAugment")
@@ -1739,7 +1713,11 @@ class RandAugment:
         rows, warps = _randaug_plan(params, H, W, N, self.fill, self.interpolation)
         return rows if warps is None else _RandAugPlan(rows, warps)
 
-    def _launch(self, f5, rows, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+    def _run(self, f5, params, mode=_lib.PTX_RESIZE_OUT_U8, norm=None, dtype=torch.uint8):
+        """The stage on contiguous uint8 frames f5 [N,T,H,W,3]: `params`, or a draw that is kept as `last_params`; see `_launch`."""
+        return self._launch(f5, self._rows_for(f5.shape[0], f5.shape[2], f5.shape[3], params), mode, norm, dtype)
+
+    def _launch(self, f5, rows, mode, norm, dtype):
         """The launches on contiguous uint8 CUDA frames f5 [N,T,H,W,3] with checked host rows [N, K, 8]: uint8 [N,T,H,W,3] or the
         normalised [N,3,T,H,W] of `dtype`.  Positions ping-pong between two uint8 scratch buffers; the last one writes y.  `rows`
         may be a `_RandAugPlan`, whose warp launches run in front of their positions."""
@@ -1754,10 +1732,7 @@ class RandAugment:
             rows_p = C.c_void_p(dev_rows.data_ptr())
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             scratch = [torch.empty_like(f5) for _ in range(min(K - 1, 2))]
-            if mode == _lib.PTX_RESIZE_OUT_U8:
-                y = torch.empty((N, T, H, W, 3), device=f5.device, dtype=torch.uint8)
-            else:
-                y = torch.empty((N, 3, T, H, W), device=f5.device, dtype=dtype)
+            y = _alloc_out(mode, N, T, H, W, f5.device, dtype)
             stats = None
             cur = f5
             for k in range(K):
@@ -1801,10 +1776,7 @@ class RandAugment:
                 pool.append(torch.empty_like(f5))
                 return pool[-1]
 
-            if mode == _lib.PTX_RESIZE_OUT_U8:
-                y = torch.empty((N, T, H, W, 3), device=f5.device, dtype=torch.uint8)
-            else:
-                y = torch.empty((N, 3, T, H, W), device=f5.device, dtype=dtype)
+            y = _alloc_out(mode, N, T, H, W, f5.device, dtype)
             stats = None
             cur = f5
             for k in range(K):
@@ -1835,20 +1807,11 @@ class RandAugment:
         return y
 
     def __call__(self, frames, params=None):
-        if not isinstance(frames, torch.Tensor):
-            raise PtxError("RandAugment: frames must be a uint8 CUDA tensor, got %s" % type(frames).__name__)
-        if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
-            raise PtxError("RandAugment: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (tuple(frames.shape),))
-        N = frames.shape[0] if frames.dim() == 5 else 1
-        H, W = int(frames.shape[-3]), int(frames.shape[-2])
-        if frames.numel() == 0:
-            raise PtxError("RandAugment: empty batch")
+        N, _, H, W = _frames_shape(frames, "RandAugment")
+        _check_not_empty(frames, "RandAugment")
         if params is not None:                                       # validated before a device is touched
             params = self.check_params(params, N, H, W)
-        if not frames.is_cuda or frames.dtype != torch.uint8:
-            raise PtxError("RandAugment: frames must be a uint8 CUDA tensor (no CPU fallback)")
-        f5 = frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
-        return self._launch(f5, self._rows_for(N, H, W, params)).view(frames.shape)
+        return self._run(_u8_cuda_5d(frames, "RandAugment"), params).view(frames.shape)
 
 
 class _RandAugPlan:
@@ -1857,21 +1820,6 @@ class _RandAugPlan:
 
     def __init__(self, rows, warps):
         self.rows, self.warps = rows, warps
-
-
-def _apply_augment(augment, frames_u8, out, dtype, norm, augment_params):
-    """The RandAugment half of TransformFrames / SampleClips with augment=: `frames_u8` is the uint8 output of the stage in front
-    ([N,T,S,S,3] or a lower rank, one clip), the result the requested output of the call."""
-    lead = frames_u8.dim()
-    f5 = frames_u8.view((1,) * (5 - lead) + tuple(frames_u8.shape))
-    rows = augment._rows_for(f5.shape[0], f5.shape[2], f5.shape[3], augment_params)
-    if out == "frames":
-        return augment._launch(f5, rows).view(frames_u8.shape)
-    mode = _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
-    y = augment._launch(f5, rows, mode, norm, dtype)
-    if lead == 5:
-        return y
-    return y[0] if lead == 4 else y[0, :, 0]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1896,11 +1844,7 @@ def _warp_params(kinds, coeffs, N=None, who="warp"):
     PtxError (shapes and dtypes only; the values are ptx_warp_frames_supported's to check)."""
     arrs = []
     for name, a, ok, shape in (("kinds", kinds, "iu", "[N]"), ("coeffs", coeffs, "fiu", "[N, %d]" % _lib.PTX_WARP_COEFFS)):
-        if isinstance(a, torch.Tensor):
-            if a.is_cuda:
-                raise PtxError("%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
-            a = a.numpy()
-        a = np.asarray(a)
+        a = _host_array(a, "%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
         if a.dtype.kind not in ok:
             raise PtxError("%s: params %s must hold %s, got dtype %s" % (who, name, "integers" if ok == "iu" else "numbers", a.dtype))
         if a.ndim != (1 if name == "kinds" else 2) or (name == "coeffs" and a.shape[1] != _lib.PTX_WARP_COEFFS):
@@ -2044,9 +1988,7 @@ class _ClipWarp:
         who = type(self).__name__
         self.interpolation = check_warp_interpolation(interpolation, who)
         self.fill = _randaug_fill(fill, who)
-        if generator is not None and not isinstance(generator, torch.Generator):
-            raise PtxError("%s: generator must be a torch.Generator or None, got %r" % (who, generator))
-        self.generator, self.last_params, self.last_launches = generator, None, ()
+        self.generator, self.last_params, self.last_launches = _check_generator(generator, who), None, ()
 
     def check_params(self, params, N=None, H=None, W=None):
         """`params` as (CPU int32 [N], CPU float64 [N, 8]) tensors, or PtxError: shapes, N; with H and W also the library's own
@@ -2078,22 +2020,14 @@ class _ClipWarp:
 
     def __call__(self, frames, params=None):
         who = type(self).__name__
-        if not isinstance(frames, torch.Tensor):
-            raise PtxError("%s: frames must be a uint8 CUDA tensor, got %s" % (who, type(frames).__name__))
-        if frames.dim() not in (3, 4, 5) or frames.shape[-1] != 3:
-            raise PtxError("%s: expected [N,T,H,W,3], [T,H,W,3] or [H,W,3], got shape %s" % (who, tuple(frames.shape)))
-        N = frames.shape[0] if frames.dim() == 5 else 1
-        H, W = int(frames.shape[-3]), int(frames.shape[-2])
-        if frames.numel() == 0:
-            raise PtxError("%s: empty batch" % who)
+        N, _, H, W = _frames_shape(frames, who)
+        _check_not_empty(frames, who)
         if params is not None:                                       # validated before a device is touched
             params = self.check_params(params, N, H, W)
-        if not frames.is_cuda or frames.dtype != torch.uint8:
-            raise PtxError("%s: frames must be a uint8 CUDA tensor (no CPU fallback)" % who)
+        f5 = _u8_cuda_5d(frames, who)
         if params is None:
             params = self.last_params = self.draw(N, H, W)
         plan = self._plan(params[0].numpy(), params[1].numpy(), H, W)
-        f5 = frames.contiguous().view((1,) * (5 - frames.dim()) + tuple(frames.shape))
         with torch.cuda.device(f5.device):
             y = torch.empty_like(f5)
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -2246,11 +2180,7 @@ def _mix_params(params, N=None, who="BatchMix"):
         raise PtxError("%s: params must be a pair (rows [N, %d], lam [N]), got %r" % (who, len(MIX_FIELDS), params))
     out = []
     for name, a, kinds in (("rows", rows, "iu"), ("lam", lam, "f")):
-        if isinstance(a, torch.Tensor):
-            if a.is_cuda:
-                raise PtxError("%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
-            a = a.numpy()
-        a = np.asarray(a)
+        a = _host_array(a, "%s: params %s must be an array or a CPU tensor, got a CUDA tensor" % (who, name))
         if a.dtype.kind not in kinds:
             raise PtxError("%s: params %s must hold %s, got dtype %s" % (who, name, "integers" if kinds == "iu" else "floats", a.dtype))
         out.append(a)
@@ -2420,8 +2350,7 @@ class BatchMix:
                 raise PtxError("BatchMix: %s must be a pair lo <= hi (scale in [0, 1], ratio positive), got %r" % (name, v))
             pairs.append((lo_, hi_))
         for name, g in (("generator", generator), ("noise_generator", noise_generator)):
-            if g is not None and not isinstance(g, torch.Generator):
-                raise PtxError("BatchMix: %s must be a torch.Generator or None, got %r" % (name, g))
+            _check_generator(g, "BatchMix", name)
         if generator is not None and generator.device.type != "cpu":
             raise PtxError("BatchMix: generator must be a CPU torch.Generator (the draws are made on the host)")
         self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
@@ -2526,10 +2455,16 @@ class BatchMix:
             parts.append(torch.randn((3, T, h, w), device=device, generator=self.noise_generator).to(dtype).view(-1))
         return torch.cat(parts)
 
-    def _launch(self, src, src_mode, N, T, H, W, dtype, norm, rows, noise_elems, noise=None):
+    def _run(self, f5, params, mode, norm, dtype):
+        """The stage on contiguous uint8 frames f5 [N,T,H,W,3]: `params`, or a draw that is kept as `last_params`; see `_launch`.
+        The library refuses PTX_RESIZE_OUT_U8: erasing and mixing are defined on normalised values."""
+        N, T, H, W, _ = f5.shape
+        rows, noise_elems = self._rows_for(N, T, H, W, params, _lib.PTX_MIX_SRC_U8, mode)
+        return self._launch(f5, _lib.PTX_MIX_SRC_U8, mode, N, T, H, W, dtype, norm, rows, noise_elems)
+
+    def _launch(self, src, src_mode, out_mode, N, T, H, W, dtype, norm, rows, noise_elems, noise=None):
         """The launch on a contiguous CUDA source (uint8 [N,T,H,W,3] or a normalised [N,3,T,H,W]) with the checked host rows of
         `_rows_for`: the normalised [N,3,T,H,W] of `dtype`."""
-        out_mode = _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
         with torch.cuda.device(src.device):
             buf = self._noise(rows, noise_elems, T, src.device, dtype, noise)
             self.last_noise = buf
@@ -2566,14 +2501,13 @@ class BatchMix:
             dtype, norm = x.dtype, None
         else:
             raise PtxError("BatchMix: expected uint8 frames or an fp32 / bf16 clip, got dtype %s" % (x.dtype,))
-        if x.numel() == 0:
-            raise PtxError("BatchMix: empty batch")
+        _check_not_empty(x, "BatchMix")
+        out_mode = _out_mode(dtype)
         if params is not None or x.is_cuda:                          # given params are validated before a device is touched
-            rows, noise_elems = self._rows_for(N, T, H, W, params, src_mode,
-                                               _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16)
+            rows, noise_elems = self._rows_for(N, T, H, W, params, src_mode, out_mode)
         if not x.is_cuda:
             raise PtxError("BatchMix: expected a CUDA tensor (no CPU fallback; batch_mix_torch states the arithmetic)")
-        return self._launch(x.contiguous(), src_mode, N, T, H, W, dtype, norm, rows, noise_elems, noise)
+        return self._launch(x.contiguous(), src_mode, out_mode, N, T, H, W, dtype, norm, rows, noise_elems, noise)
 
     def targets(self, labels, num_classes, smoothing=0.0, params=None):
         """Soft targets fp32 [N, num_classes] of CUDA int64 labels [N] for the LAST call's draw (or `params`): one-hot rows with
@@ -2608,63 +2542,80 @@ class BatchMix:
         return y
 
 
-def _apply_mix(mix, frames_u8, dtype, norm, mix_params):
-    """The BatchMix stage of TransformFrames / SampleClips with mix=: `frames_u8` is the uint8 output of the stage in front
-    ([N,T,S,S,3] or a lower rank, one clip, which is its own partner), the result the normalised clip of the call."""
+# ---------------------------------------------------------------------------------------------
+# The clip stages behind the resize of TransformFrames / SampleClips
+# ---------------------------------------------------------------------------------------------
+_STAGES = ("color", "blur", "augment", "mix")            # the recipes' order: the stages run, and so draw, in it
+_STAGE_TYPES = {"color": ColorJitter, "blur": GaussianBlur, "augment": RandAugment, "mix": BatchMix}
+
+
+def _apply_stages(stages, frames_u8, out, dtype, norm, params):
+    """The stages behind a resize, in the order of `_STAGES`.  stages: name -> stage (None or missing: off), at least one on;
+    frames_u8: the resize's uint8 output [N,T,S,S,3] or of a lower rank (one clip); params: name -> checked params (None or
+    missing: the stage draws when it runs and keeps the draw as `last_params`).  The last stage writes the output of `out` /
+    `dtype` with `norm`, every stage in front of it uint8 frames."""
+    present = [name for name in _STAGES if stages.get(name) is not None]
     lead = frames_u8.dim()
     f5 = frames_u8.view((1,) * (5 - lead) + tuple(frames_u8.shape))
-    N, T, H, W, _ = f5.shape
-    rows, noise_elems = mix._rows_for(N, T, H, W, mix_params, _lib.PTX_MIX_SRC_U8,
-                                      _lib.PTX_RESIZE_OUT_F32 if dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16)
-    y = mix._launch(f5, _lib.PTX_MIX_SRC_U8, N, T, H, W, dtype, norm, rows, noise_elems)
-    if lead == 5:
-        return y
-    return y[0] if lead == 4 else y[0, :, 0]
+    for name in present[:-1]:
+        f5 = stages[name]._run(f5, params.get(name), _lib.PTX_RESIZE_OUT_U8, None, torch.uint8)
+    mode = _out_mode(dtype, out)
+    if out == "frames":
+        norm, dtype = None, torch.uint8
+    return _restore_rank(stages[present[-1]]._run(f5, params.get(present[-1]), mode, norm, dtype), lead, mode)
 
 
-def _check_mix(mix, out, who):
-    if mix is not None and not isinstance(mix, BatchMix):
-        raise PtxError("%s: mix must be a pretorched.transforms.BatchMix or None, got %r" % (who, mix))
-    if mix is not None and out != "tensor":
-        raise PtxError("%s: mix= needs out='tensor': erasing and mixing are defined on normalised values, out='frames' returns "
-                       "uint8 frames (forward_frames(.., transform=) takes those alone)" % who)
-    return mix
+class _ClipStages:
+    """What TransformFrames and SampleClips share: the stages `color`, `blur`, `augment` and `mix` behind their resize, the
+    checks of those arguments (`who` names the class in messages, `_NOUN` what it calls itself), the checks of a call's
+    `*_params`, and `_resize`, the resize half of a call with stages."""
+
+    def _init_stages(self, who, out, color, augment, mix):
+        for name, stage in (("color", color), ("augment", augment), ("mix", mix)):
+            if stage is not None and not isinstance(stage, _STAGE_TYPES[name]):
+                raise PtxError("%s: %s must be a pretorched.transforms.%s or None, got %r" % (who, name, _STAGE_TYPES[name].__name__, stage))
+        if mix is not None and out != "tensor":
+            raise PtxError("%s: mix= needs out='tensor': erasing and mixing are defined on normalised values, out='frames' returns "
+                           "uint8 frames (forward_frames(.., transform=) takes those alone)" % who)
+        self.color, self.augment, self.mix = color, augment, mix
+
+    def _init_blur(self, who, blur):
+        """After `size` is known: the kernel must fit the S x S output."""
+        if blur is not None and not isinstance(blur, GaussianBlur):
+            raise PtxError("%s: blur must be a pretorched.transforms.GaussianBlur or None, got %r" % (who, blur))
+        if blur is not None and max(blur.kernel_size) // 2 >= self.size:
+            raise PtxError("%s: blur: kernel_size=%r does not fit the %dx%d output (H=%d, W=%d): reflect padding needs "
+                           "kernel_size // 2 < H, W" % (who, blur.kernel_size, self.size, self.size, self.size, self.size))
+        self.blur = blur
+
+    def _init_resize_half(self):
+        """Last in a constructor.  `_resize` is this object without its stages, writing uint8 frames (the generator and the
+        tables cache are shared with it), or None when no stage is given."""
+        self._resize = None
+        if any(getattr(self, name) is not None for name in _STAGES):
+            rs = self._resize = copy.copy(self)
+            rs.color = rs.blur = rs.augment = rs.mix = None
+            rs.out, rs.dtype = "frames", torch.float32
+
+    def _checked_params(self, who, given, order, validate=True):
+        """`given` maps a stage's name to a call's `<name>_params`.  In `order`, a given one whose stage is missing is refused and,
+        with `validate`, every other given one is replaced by its checked form.  No device is touched."""
+        for name in order:
+            if given[name] is None:
+                continue
+            stage = getattr(self, name)
+            if stage is None:
+                raise PtxError("%s: %s_params= needs a %s built with %s=%s(..)" % (who, name, self._NOUN, name, _STAGE_TYPES[name].__name__))
+            if validate:
+                given[name] = stage.check_params(given[name], *(() if name == "color" else (None, self.size, self.size)))
+        return given
+
+    def _run_stages(self, frames_u8, given):
+        """The stages on `_resize`'s output with the checked `given` params: the output of `out` / `dtype`."""
+        return _apply_stages({name: getattr(self, name) for name in _STAGES}, frames_u8, self.out, self.dtype, self.norm, given)
 
 
-def _apply_stages(color, augment, u8, out, dtype, norm, color_params, augment_params, mix=None, mix_params=None, blur=None,
-                  blur_params=None):
-    """The stages behind the resize of TransformFrames / SampleClips: colour, then blur, then augment, then mix (the recipes'
-    order); the last one writes the call's output, the ones in front of it uint8 scratch.  Every stage draws when it runs."""
-    if blur is not None:
-        stages = []
-        if color is not None:
-            stages.append(lambda u, o, d: _apply_color(color, u, o, d, norm, color_params))
-        stages.append(lambda u, o, d: _apply_blur(blur, u, o, d, norm, blur_params))
-        if augment is not None:
-            stages.append(lambda u, o, d: _apply_augment(augment, u, o, d, norm, augment_params))
-        if mix is not None:
-            stages.append(lambda u, o, d: _apply_mix(mix, u, d, norm, mix_params))
-        for stage in stages[:-1]:
-            u8 = stage(u8, "frames", torch.float32)
-        return stages[-1](u8, out, dtype)
-    if mix is not None:
-        if color is not None or augment is not None:
-            u8 = _apply_stages(color, augment, u8, "frames", torch.float32, norm, color_params, augment_params)
-        return _apply_mix(mix, u8, dtype, norm, mix_params)
-    if augment is None:
-        return _apply_color(color, u8, out, dtype, norm, color_params)
-    if color is not None:
-        u8 = _apply_color(color, u8, "frames", torch.float32, norm, color_params)
-    return _apply_augment(augment, u8, out, dtype, norm, augment_params)
-
-
-def _check_augment(augment, who):
-    if augment is not None and not isinstance(augment, RandAugment):
-        raise PtxError("%s: augment must be a pretorched.transforms.RandAugment or None, got %r" % (who, augment))
-    return augment
-
-
-class TransformFrames:
+class TransformFrames(_ClipStages):
     """Resize + crop (+ flip) of decoded uint8 frames on the device, bit-exact with PIL's bilinear resize, then
     TransformImage's tensor half (`out="tensor"`) or nothing more (`out="frames"`).
 
@@ -2716,15 +2667,14 @@ class TransformFrames:
     geometry=) supports nearest, box, bilinear and bicubic: its tables are built on the device.  No draw depends on it."""
 
     CACHE_SIZE = 8
+    _NOUN = "transform"
 
     def __init__(self, opts, scale=0.875, preserve_aspect_ratio=True, crop="center", hflip=False, out="tensor",
                  dtype=torch.float32, *, random_crop=False, random_hflip=False, random_vflip=False, vflip=False,
                  generator=None, random_short_side=None, random_resized_crop=False, color=None, augment=None,
                  interpolation="bilinear", mix=None, blur=None):
         self.interpolation = check_interpolation(interpolation, "TransformFrames")
-        self.color = _check_color(color, "TransformFrames")
-        self.augment = _check_augment(augment, "TransformFrames")
-        self.mix = _check_mix(mix, out, "TransformFrames")
+        self._init_stages("TransformFrames", out, color, augment, mix)
         if out not in ("tensor", "frames"):
             raise PtxError("TransformFrames: out must be 'tensor' or 'frames', got %r" % (out,))
         if dtype not in (torch.float32, torch.bfloat16):
@@ -2746,12 +2696,10 @@ class TransformFrames:
             raise PtxError("TransformFrames: random_hflip=True draws the flip; it cannot be combined with hflip=True")
         if self.random_vflip and self.vflip:
             raise PtxError("TransformFrames: random_vflip=True draws the flip; it cannot be combined with vflip=True")
-        if generator is not None and not isinstance(generator, torch.Generator):
-            raise PtxError("TransformFrames: generator must be a torch.Generator or None, got %r" % (generator,))
         self.random = self.random_crop or self.random_hflip or self.random_vflip
-        self.generator, self.last_params = generator, None
+        self.generator, self.last_params = _check_generator(generator, "TransformFrames"), None
         self.size = int(max(self.input_size))
-        self.blur = _check_blur(blur, self.size, "TransformFrames")
+        self._init_blur("TransformFrames", blur)
         if not isinstance(crop, str):
             crop_window(1 << 30, 1 << 30, self.size, crop)          # a malformed or negative window fails here
         elif crop != "center":
@@ -2805,37 +2753,7 @@ class TransformFrames:
         self.per_clip_geometry = self.random_short_side is not None or self.random_resized_crop is not None
         if self.per_clip_geometry:
             self._device_filter("random_short_side / random_resized_crop")
-        self._resize = None
-        if self.color is not None or self.augment is not None or self.mix is not None or self.blur is not None:   # the resize half of a call with colour /
-            self._resize = copy.copy(self)                           # blur / augment / mix: this transform, writing uint8 frames (tables cache and generator shared)
-            self._resize.color, self._resize.augment, self._resize.out, self._resize.dtype = None, None, "frames", torch.float32
-            self._resize.mix, self._resize.blur = None, None
-
-    def _call_color(self, frames, params, geometry, color_params, augment_params=None, mix_params=None, blur_params=None):
-        """A call with color=, blur=, augment= and / or mix=: the resize writes uint8 frames into scratch (every draw of the plain
-        call, in its order), then the colour lists are drawn clip by clip and applied, then the blur's draw, then the augment's,
-        then the mix's; the last stage writes the requested output, the stages in front of it uint8 scratch."""
-        rs = self._resize
-        if blur_params is not None:                                  # validated before a device is touched
-            if self.blur is None:
-                raise PtxError("TransformFrames: blur_params= needs a transform built with blur=GaussianBlur(..)")
-            blur_params = self.blur.check_params(blur_params, None, self.size, self.size)
-        if mix_params is not None:                                   # validated before a device is touched
-            if self.mix is None:
-                raise PtxError("TransformFrames: mix_params= needs a transform built with mix=BatchMix(..)")
-            mix_params = self.mix.check_params(mix_params, None, self.size, self.size)
-        if color_params is not None:                                 # validated before a device is touched
-            if self.color is None:
-                raise PtxError("TransformFrames: color_params= needs a transform built with color=ColorJitter(..)")
-            color_params = self.color.check_params(color_params)
-        if augment_params is not None:
-            if self.augment is None:
-                raise PtxError("TransformFrames: augment_params= needs a transform built with augment=RandAugment(..)")
-            augment_params = self.augment.check_params(augment_params, None, self.size, self.size)
-        u8 = rs(frames, params=params, geometry=geometry)
-        self.last_params, self.last_geometry = rs.last_params, rs.last_geometry
-        return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params, self.mix,
-                             mix_params, self.blur, blur_params)
+        self._init_resize_half()
 
     def _device_filter(self, what):
         """The PTX_RESAMPLE_* code of this transform's filter for the device table builder, or PtxError: a per-clip
@@ -2884,11 +2802,7 @@ class TransformFrames:
     def check_params(self, params, N, H, W):
         """`params` ([N, 4] integers: an array or a CPU tensor) as a CPU int32 tensor, or PtxError: N does not match, a
         window does not fit the resized frame of H x W frames, a flip is not 0 / 1."""
-        if isinstance(params, torch.Tensor):
-            if params.is_cuda:
-                raise PtxError("TransformFrames: params must be an integer array or a CPU tensor [N, 4], got a CUDA tensor")
-            params = params.numpy()
-        p = np.asarray(params)
+        p = _host_array(params, "TransformFrames: params must be an integer array or a CPU tensor [N, 4], got a CUDA tensor")
         if p.dtype.kind not in "iu":
             raise PtxError("TransformFrames: params must hold integers, got dtype %s" % (p.dtype,))
         if p.ndim != 2 or p.shape[1] != 4:
@@ -2945,11 +2859,7 @@ class TransformFrames:
 
     def _checked_geometry(self, geometry, N, H, W):
         self._device_filter("geometry=")
-        if isinstance(geometry, torch.Tensor):
-            if geometry.is_cuda:
-                raise PtxError("TransformFrames: geometry must be an integer array or a CPU tensor [N, 10], got a CUDA tensor")
-            geometry = geometry.numpy()
-        p = np.asarray(geometry)
+        p = _host_array(geometry, "TransformFrames: geometry must be an integer array or a CPU tensor [N, 10], got a CUDA tensor")
         if p.dtype.kind not in "iu":
             raise PtxError("TransformFrames: geometry must hold integers, got dtype %s" % (p.dtype,))
         if p.ndim != 2 or p.shape[1] != 10:
@@ -3034,16 +2944,12 @@ class TransformFrames:
         `mix.last_params` (`mix.targets(labels, K)` gives the matching soft targets); mix_params applies a given draw instead.
         With blur= (a `GaussianBlur`) its launch runs behind the colour launch and in front of the augment and the mix; its draw
         comes in that order too (after the colour draw) and is kept as `blur.last_params`; blur_params applies a given draw."""
-        if self.color is not None or self.augment is not None or self.mix is not None or self.blur is not None:
-            return self._call_color(frames, params, geometry, color_params, augment_params, mix_params, blur_params)
-        if blur_params is not None:
-            raise PtxError("TransformFrames: blur_params= needs a transform built with blur=GaussianBlur(..)")
-        if mix_params is not None:
-            raise PtxError("TransformFrames: mix_params= needs a transform built with mix=BatchMix(..)")
-        if color_params is not None:
-            raise PtxError("TransformFrames: color_params= needs a transform built with color=ColorJitter(..)")
-        if augment_params is not None:
-            raise PtxError("TransformFrames: augment_params= needs a transform built with augment=RandAugment(..)")
+        given = self._checked_params("TransformFrames", {"blur": blur_params, "mix": mix_params, "color": color_params,
+                                                         "augment": augment_params}, ("blur", "mix", "color", "augment"))
+        if self._resize is not None:                                 # the resize (every draw of the plain call), then the stages
+            u8 = self._resize(frames, params=params, geometry=geometry)
+            self.last_params, self.last_geometry = self._resize.last_params, self._resize.last_geometry
+            return self._run_stages(u8, given)
         if params is not None and geometry is not None:
             raise PtxError("TransformFrames: params= and geometry= cannot be combined (a geometry row holds the window and flips)")
         if params is not None and self.per_clip_geometry:
@@ -3059,31 +2965,20 @@ class TransformFrames:
             raise PtxError("TransformFrames: frames must have 3 interleaved channels, got %d" % frames.shape[-1])
         if geometry is not None:                                     # validated before a device is touched
             geometry = self.check_geometry(geometry, frames.shape[0] if frames.dim() == 5 else 1, frames.shape[-3], frames.shape[-2])
-        if not frames.is_cuda or frames.dtype != torch.uint8:
-            raise PtxError("TransformFrames: frames must be a uint8 CUDA tensor (no CPU fallback)")
-        lead = frames.dim()
-        f5 = frames.contiguous().view((1,) * (5 - lead) + tuple(frames.shape))
+        f5 = _u8_cuda_5d(frames, "TransformFrames")
         N, T, H, W, Cc = f5.shape
         if N * T == 0:
             raise PtxError("TransformFrames: empty batch")
-        S = self.size
+        S, lead, mode = self.size, frames.dim(), _out_mode(self.dtype, self.out)
         if params is not None or geometry is not None or self.random or self.per_clip_geometry:
             if geometry is not None or self.per_clip_geometry:
                 y = self._call_geometry(f5, None, N, T, H, W, frames.device, geometry)
             else:
                 y = self._call_windows(f5, None, N, T, H, W, frames.device, params)
-            if self.out == "frames":
-                return y.view(tuple(frames.shape[:-3]) + (S, S, Cc))
-            if lead == 5:
-                return y
-            return y[0] if lead == 4 else y[0, :, 0]
+            return _restore_rank(y, lead, mode)
         with torch.cuda.device(frames.device):
             buf, offs, taps_h, taps_w = self._device_tables(H, W, frames.device)
-            if self.out == "frames":
-                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((N, T, S, S, Cc), device=frames.device, dtype=torch.uint8)
-            else:
-                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
-                y = torch.empty((N, Cc, T, S, S), device=frames.device, dtype=self.dtype)
+            y = _alloc_out(mode, N, T, S, S, frames.device, self.dtype)
             desc = ResizeDesc(N, T, H, W, Cc, S, S, taps_h, taps_w, mode)
             base = buf.data_ptr()
             check(_lib.lib().ptx_resize_frames_u8(C.byref(desc), C.c_void_p(f5.data_ptr()),
@@ -3091,12 +2986,7 @@ class TransformFrames:
                                                   C.c_void_p(y.data_ptr()), C.byref(self.norm),
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                   "ptx_resize_frames_u8")
-        if self.out == "frames":
-            return y.view(tuple(frames.shape[:-3]) + (S, S, Cc))
-        if lead == 5:
-            return y
-        return y[0] if lead == 4 else y[0, :, 0]
-
+        return _restore_rank(y, lead, mode)
 
     def _call_windows(self, f5, ysrc, N, T, H, W, device, params):
         """The per-clip windows launch on frames f5 [N,T,H,W,3] or, when ysrc is given, on a YUV source: the drawn or the
@@ -3111,11 +3001,8 @@ class TransformFrames:
             buf, offs, taps_h, taps_w = self._device_tables(H, W, device, whole=True)
             h, w = resized_size(H, W, self.input_size, self.scale, self.preserve_aspect_ratio)
             wins = p.contiguous().to(device)
-            if self.out == "frames":
-                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((N, T, S, S, 3), device=device, dtype=torch.uint8)
-            else:
-                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
-                y = torch.empty((N, 3, T, S, S), device=device, dtype=self.dtype)
+            mode = _out_mode(self.dtype, self.out)
+            y = _alloc_out(mode, N, T, S, S, device, self.dtype)
             desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
             base = buf.data_ptr()
             name = "ptx_resize_frames_%s_windows" % ("u8" if ysrc is None else _abi_of(ysrc))
@@ -3140,11 +3027,8 @@ class TransformFrames:
             buf = torch.empty(sum(sizes), device=device, dtype=torch.int32)
             offs = np.cumsum([0] + sizes[:-1])
             tabs = [C.c_void_p(buf.data_ptr() + int(o) * 4) for o in offs]
-            if self.out == "frames":
-                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((N, T, S, S, 3), device=device, dtype=torch.uint8)
-            else:
-                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
-                y = torch.empty((N, 3, T, S, S), device=device, dtype=self.dtype)
+            mode = _out_mode(self.dtype, self.out)
+            y = _alloc_out(mode, N, T, S, S, device, self.dtype)
             desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             if code == _lib.PTX_RESAMPLE_BILINEAR:                   # the default: the launch it always was
@@ -3164,24 +3048,17 @@ class TransformFrames:
             geometry = self.check_geometry(geometry, src.N, src.H, src.W)
         ysrc, keep = src.source("TransformFrames")
         N, T, H, W, S = src.N, src.T, src.H, src.W, self.size
+        mode = _out_mode(self.dtype, self.out)
         if params is not None or geometry is not None or self.random or self.per_clip_geometry:
             if geometry is not None or self.per_clip_geometry:
                 y = self._call_geometry(None, ysrc, N, T, H, W, src.device, geometry)
             else:
                 y = self._call_windows(None, ysrc, N, T, H, W, src.device, params)
             del keep
-            if self.out == "frames":
-                return y.view(src.lead_shape + (S, S, 3))
-            if src.lead == 3:
-                return y
-            return y[0] if src.lead == 2 else y[0, :, 0]
+            return _restore_rank(y, src.lead + 2, mode)
         with torch.cuda.device(src.device):
             buf, offs, taps_h, taps_w = self._device_tables(H, W, src.device)
-            if self.out == "frames":
-                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((N, T, S, S, 3), device=src.device, dtype=torch.uint8)
-            else:
-                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
-                y = torch.empty((N, 3, T, S, S), device=src.device, dtype=self.dtype)
+            y = _alloc_out(mode, N, T, S, S, src.device, self.dtype)
             desc = ResizeDesc(N, T, H, W, 3, S, S, taps_h, taps_w, mode)
             base = buf.data_ptr()
             name = "ptx_resize_frames_" + src._ABI
@@ -3189,11 +3066,7 @@ class TransformFrames:
                                             C.c_void_p(y.data_ptr()), C.byref(self.norm),
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
             del keep                                                 # planes (copies included) stayed alive up to the launch
-        if self.out == "frames":
-            return y.view(src.lead_shape + (S, S, 3))
-        if src.lead == 3:
-            return y
-        return y[0] if src.lead == 2 else y[0, :, 0]
+        return _restore_rank(y, src.lead + 2, mode)
 
 
 def _abi_of(ysrc):
@@ -3385,8 +3258,7 @@ class SampleViews:
         for k in range(self.crops):
             d.row_off[k], d.col_off[k] = t["row_off"][k], t["col_off"][k]
         d.v0, d.nv = v0, nv
-        d.out_mode = _lib.PTX_RESIZE_OUT_U8 if self.out == "frames" else (
-            _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16)
+        d.out_mode = _out_mode(self.dtype, self.out)
         d.share = self._SHARE[self.share]
         return d
 
@@ -3476,7 +3348,7 @@ class SampleViews:
 _CLIP_SRC = np.dtype([("base", "<u8"), ("stride_t", "<i8"), ("H", "<i4"), ("W", "<i4"), ("Tv", "<i4"), ("reserved", "<i4")])
 
 
-class SampleClips:
+class SampleClips(_ClipStages):
     """Training clips from decoded videos of ANY sizes and lengths in one resize launch: `clips` clips of `num_frames`
     frames per video, every clip resized + cropped (+ flipped) exactly as `TransformFrames` with the same spatial switches
     does on the clip's gathered frames (bit-identical), read in place through a frame index row per clip.
@@ -3497,13 +3369,13 @@ class SampleClips:
     interpolation: the resize filter, passed to `spatial`; every clip's tables are built on the device, so nearest, box,
     bilinear and bicubic (see TransformFrames)."""
 
+    _NOUN = "sampler"
+
     def __init__(self, opts, num_frames=16, frame_stride=4, clips=1, sampling="dense", random_start=True, scale=0.875,
                  preserve_aspect_ratio=True, crop="center", hflip=False, vflip=False, random_crop=False, random_hflip=False,
                  random_vflip=False, random_short_side=None, random_resized_crop=False, out="tensor", dtype=torch.float32,
                  generator=None, color=None, augment=None, interpolation="bilinear", mix=None, blur=None):
-        self.color = _check_color(color, "SampleClips")
-        self.augment = _check_augment(augment, "SampleClips")
-        self.mix = _check_mix(mix, out, "SampleClips")
+        self._init_stages("SampleClips", out, color, augment, mix)
         for name, v in (("num_frames", num_frames), ("frame_stride", frame_stride), ("clips", clips)):
             if not isinstance(v, int) or isinstance(v, bool) or v < 1:
                 raise PtxError("SampleClips: %s must be a positive integer, got %r" % (name, v))
@@ -3518,13 +3390,9 @@ class SampleClips:
         self.num_frames, self.frame_stride, self.clips, self.sampling = num_frames, frame_stride, clips, sampling
         self.random_start, self.generator = bool(random_start), generator
         self.out, self.dtype, self.size, self.norm = out, dtype, self.spatial.size, self.spatial.norm
-        self.blur = _check_blur(blur, self.size, "SampleClips")
+        self._init_blur("SampleClips", blur)
         self.last_indices, self.last_geometry = None, None
-        self._resize = None
-        if self.color is not None or self.augment is not None or self.mix is not None or self.blur is not None:   # the resize half of a call with colour / blur / augment / mix (see TransformFrames)
-            self._resize = copy.copy(self)
-            self._resize.color, self._resize.augment, self._resize.out, self._resize.dtype = None, None, "frames", torch.float32
-            self._resize.mix, self._resize.blur = None, None
+        self._init_resize_half()
 
     # ---- host only: no device is touched -------------------------------------------------------
     @staticmethod
@@ -3585,12 +3453,7 @@ class SampleClips:
         NC = len(shapes) * K
         arrs = []
         for name, a, cols in (("indices", indices, T), ("geometry", geometry, 10)):
-            if isinstance(a, torch.Tensor):
-                if a.is_cuda:
-                    raise PtxError("SampleClips: %s must be an integer array or a CPU tensor [N*clips, %d], got a CUDA tensor" % (
-                        name, cols))
-                a = a.numpy()
-            a = np.asarray(a)
+            a = _host_array(a, "SampleClips: %s must be an integer array or a CPU tensor [N*clips, %d], got a CUDA tensor" % (name, cols))
             if a.dtype.kind not in "iu":
                 raise PtxError("SampleClips: %s must hold integers, got dtype %s" % (name, a.dtype))
             if a.ndim != 2 or a.shape[1] != cols:
@@ -3690,28 +3553,13 @@ class SampleClips:
         With mix= (a `BatchMix`) its launch runs last across the output clips (`mix.last_params`); mix_params applies a given draw.
         With blur= (a `GaussianBlur`) its launch runs behind the colour launch, one draw per output clip after the colour draw
         (`blur.last_params`); blur_params applies a given draw."""
-        if blur_params is not None and self.blur is None:
-            raise PtxError("SampleClips: blur_params= needs a sampler built with blur=GaussianBlur(..)")
-        if mix_params is not None and self.mix is None:
-            raise PtxError("SampleClips: mix_params= needs a sampler built with mix=BatchMix(..)")
-        if color_params is not None and self.color is None:
-            raise PtxError("SampleClips: color_params= needs a sampler built with color=ColorJitter(..)")
-        if augment_params is not None and self.augment is None:
-            raise PtxError("SampleClips: augment_params= needs a sampler built with augment=RandAugment(..)")
-        if self.color is not None or self.augment is not None or self.mix is not None or self.blur is not None:
-            if blur_params is not None:                              # validated before a device is touched
-                blur_params = self.blur.check_params(blur_params, None, self.size, self.size)
-            if color_params is not None:                             # validated before a device is touched
-                color_params = self.color.check_params(color_params)
-            if augment_params is not None:
-                augment_params = self.augment.check_params(augment_params, None, self.size, self.size)
-            if mix_params is not None:
-                mix_params = self.mix.check_params(mix_params, None, self.size, self.size)
-            rs = self._resize
-            u8 = rs(videos, indices=indices, geometry=geometry)
-            self.last_indices, self.last_geometry = rs.last_indices, rs.last_geometry
-            return _apply_stages(self.color, self.augment, u8, self.out, self.dtype, self.norm, color_params, augment_params, self.mix,
-                                 mix_params, self.blur, blur_params)
+        given = {"blur": blur_params, "mix": mix_params, "color": color_params, "augment": augment_params}
+        self._checked_params("SampleClips", given, ("blur", "mix", "color", "augment"), validate=False)   # every refusal first
+        if self._resize is not None:
+            given = self._checked_params("SampleClips", given, ("blur", "color", "augment", "mix"))
+            u8 = self._resize(videos, indices=indices, geometry=geometry)
+            self.last_indices, self.last_geometry = self._resize.last_indices, self._resize.last_geometry
+            return self._run_stages(u8, given)
         if (indices is None) != (geometry is None):
             raise PtxError("SampleClips: indices= and geometry= are given together (a replay) or not at all (a draw)")
         vids = self._videos(videos)
@@ -3760,11 +3608,8 @@ class SampleClips:
             sizes = [NC * S, NC * S, NC * S * taps_h, NC * S, NC * S, NC * S * taps_w]
             buf = torch.empty(sum(sizes), device=device, dtype=torch.int32)
             tabs = [C.c_void_p(buf.data_ptr() + int(o) * 4) for o in np.cumsum([0] + sizes[:-1])]
-            if self.out == "frames":
-                mode, y = _lib.PTX_RESIZE_OUT_U8, torch.empty((NC, T, S, S, 3), device=device, dtype=torch.uint8)
-            else:
-                mode = _lib.PTX_RESIZE_OUT_F32 if self.dtype == torch.float32 else _lib.PTX_RESIZE_OUT_BF16
-                y = torch.empty((NC, 3, T, S, S), device=device, dtype=self.dtype)
+            mode = _out_mode(self.dtype, self.out)
+            y = _alloc_out(mode, NC, T, S, S, device, self.dtype)
             desc = ResizeDesc(NC, T, Hm, Wm, 3, S, S, taps_h, taps_w, mode)
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             if self._filter == _lib.PTX_RESAMPLE_BILINEAR:           # the default: the launch it always was
